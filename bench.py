@@ -3,6 +3,13 @@
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   -> ONE JSON line on rank 0.
 
+A plain run does what the headline needs and nothing else: set up, W warm-up steps, K timed steps, and the line (`value`,
+`ms_per_step` = wall time of one timed step).  --full adds everything else described below (HIP events around the kernels of
+the timed steps and the roofline passes, the integrity checks, the CPU baseline, api_b1, end-to-end, the side workloads and their
+counter traffic; N > 1: the overlapped and voxel-sharded regions and the merge check); an explicit --api-b1 / --end-to-end /
+--cpu-frames count runs that pass without it.  --dump-outputs DIR writes the volume of the last timed step as DIR/<buffer>.npy
+(a fixed, seeded sample of its voxels; inputs are seeded, so two builds can be compared array by array).
+
 Workload (BASELINE.json metric / configs[3]): per rank 512 synthetic 640x480 RGB-D frames with
 random poses (SURVEY.md §8d, depth distribution A) fused into a per-rank 256^3 x 512 fp32 grid;
 ranks shard frames and merge their grids with one RCCL reduction at the end of the job.
@@ -27,11 +34,11 @@ and the merged voxel shard of a small sharded job against a single-rank fusion o
 
 Other passes: --query (BASELINE config 5: the text-query scans), --api-b1 N (one frame per integrate() call through the
 deferred window queue), --end-to-end N (a ViT-B/32-shaped backbone in front; 128 frames by default), --depth-kind B, --labels,
---feat-dtype bf16, --grid nx,ny,nz.  The default single-GPU run also reports `side_workloads` (BASELINE configs 2, 3 and 5, the
+--feat-dtype bf16, --grid nx,ny,nz.  The --full single-GPU run also reports `side_workloads` (BASELINE configs 2, 3 and 5, the
 coherent scene, config 3 end to end: about 40 s; --no-side skips them), `hbm_copy_GBps` (this box's copy rate, measured in the
 run) and `slab_by_slab_fuse` (the job fused into 8 x-slabs one after the other against one call).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline     : the dominant kernel (fuse_window_kernel): algorithmic bytes per launch (from the row / voxel counters
                  the kernels emit, SURVEY.md §8d formula) / its average launch duration, measured with HIP events on the
                  launch stream inside the timed region; `isolated`, `warm_volume`, `frame_at_a_time` beside it.
@@ -98,7 +105,7 @@ def parse():
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes of one job after the timed "
                          "regions, about a minute); the committed profiles/ figure is quoted instead")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side workloads of the default single-GPU run (configs 2, 3, 5, the coherent scene, the HBM copy rate)")
+                    help="skip the side workloads of the --full single-GPU run (configs 2, 3, 5, the coherent scene, the HBM copy rate)")
     ap.add_argument("--end-to-end", type=int, default=-1, metavar="FRAMES",
                     help="after the timed region, also time FRAMES frames through the reference-shaped API with a "
                          "ViT-B/32-shaped random-weight CLIP image tower in front of the fuse (reported separately)")
@@ -120,16 +127,25 @@ def parse():
                     help="benchmark the text-query scan instead (BASELINE config 5 and the reference's L = 5 / L = 63 scans)")
     ap.add_argument("--profile-stride", type=int, default=4,
                     help="record HIP events around the kernels of every n-th frame of the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the kernel events and roofline passes, the integrity checks, the CPU "
+                         "baseline, api_b1, end-to-end, the side workloads and counter traffic (N = 1), the other timed regions "
+                         "and the merge check (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the volume of the last step as DIR/<buffer>.npy (a fixed, seeded sample "
+                         "of its voxels, float32 / float64, under 64 MB in all)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.query or a.scene or a.side_traffic):
+        ap.error("--dump-outputs writes the fused volume: it does not go with --query, --scene or --side-traffic")
     g3 = tuple(int(x) for x in str(a.grid).split(","))
     if len(g3) == 1:
         g3 = g3 * 3
     assert len(g3) == 3 and min(g3) > 0, "--grid takes N or nx,ny,nz"
     a.grid3 = g3
-    if a.api_b1 < 0:  # default: on for the plain single-GPU run (the reference's call pattern, reported beside the bulk rate)
-        a.api_b1 = 512 if (a.gpus == 1 and not a.query and not a.scene and not a.no_side) else 0
-    if a.end_to_end < 0:  # default: on for the plain single-GPU run (128 frames, one frame per integrate() call, bf16 tower)
-        a.end_to_end = 128 if (a.gpus == 1 and not a.query and not a.labels and a.dim == 512 and not a.no_side) else 0
+    if a.api_b1 < 0:  # default: on for the --full single-GPU run (the reference's call pattern, reported beside the bulk rate)
+        a.api_b1 = 512 if (a.full and a.gpus == 1 and not a.query and not a.scene and not a.no_side) else 0
+    if a.end_to_end < 0:  # default: on for the --full single-GPU run (128 frames, one frame per integrate() call, bf16 tower)
+        a.end_to_end = 128 if (a.full and a.gpus == 1 and not a.query and not a.labels and a.dim == 512 and not a.no_side) else 0
     a.grid = g3[0] if g3[0] == g3[1] == g3[2] else "x".join(str(x) for x in g3)  # (label; cubic grids keep the integer)
     return a
 
@@ -273,15 +289,16 @@ def main():
     esz = 2 if a.feat_dtype == "bf16" else 4
 
     def new_volume(nvox=None, index_offset=(0, 0, 0), x_planes=None):
+        # (the buffers are created on the device: 34 GB of zeros through host memory would cost seconds of start-up)
         nvox = grid.nvox if nvox is None else nvox
         if a.labels:
             fz = ClipSeemFusion(grid.origin, grid.voxel_size, nvox, grid.trunc, False, a.height // 3,
                                 a.height // 6, ResidentFeatures(), None, keep_xyz_world=False, feat_dtype=fdt,
-                                index_offset=index_offset, x_planes=x_planes)
+                                index_offset=index_offset, x_planes=x_planes, device=device)
         else:
             fz = ClipFusion(grid.origin, grid.voxel_size, nvox, grid.trunc, False, ResidentFeatures(), None,
                             a.height // 3, a.height // 6, keep_xyz_world=False, feat_dtype=fdt, index_offset=index_offset,
-                            x_planes=x_planes)
+                            x_planes=x_planes, device=device)
         return fz.to(device)
 
     # N > 1 keeps two volumes: the second one lets job k+1 fuse while job k's merge drains (second timed
@@ -310,7 +327,7 @@ def main():
     merge_state = {"mode": a.merge, "fallback": None, "sparse": 0.0, "sparse_note": None, "last_merge": None}
     L = lib()
     prof = None
-    if not a.no_profile_events:
+    if a.full and not a.no_profile_events:  # (the event pairs are created up front, 3 per frame and step)
         prof = L.saf_profiler_create(3 * a.frames * max(1, a.steps))
         L.saf_profiler_set_stride(prof, a.profile_stride)
 
@@ -398,14 +415,17 @@ def main():
     st = fusion.stats()
     total_frames = world * a.frames * a.steps
     value = total_frames / dt
-    # integrity of the timed work (not timed): every frame of every step was fused, and the volume of the last
-    # step holds exactly one observation per valid (voxel, frame) pair -- over all ranks after the merge
+    # every frame of every step was fused (the count `value` divides by)
     assert st["frames"] == a.frames * a.steps, f"fused {st['frames']} frames, expected {a.frames * a.steps}"
+    # --dump-outputs: the volume of the last step, sampled before anything else touches it
+    dumps = {"serial_merge": sample_volume(fusion, n_vox, world, rank, dist)} if a.dump_outputs else {}
+    # --full: integrity of the timed work (not timed): the volume of the last step holds exactly one observation per valid
+    # (voxel, frame) pair -- over all ranks after the merge
     merge_check = None
-    if world == 1:
+    if world == 1 and a.full:
         w_sum = int(fusion.weight.sum(dtype=torch.int64))
         assert w_sum * a.steps == st["valid"], f"weight sum {w_sum} x {a.steps} steps != valid count {st['valid']}"
-    else:
+    elif world > 1 and a.full:
         own = fusion._shard_stripes if fusion._shard_stripes is not None else [(0, n_vox)]
         sums = torch.stack([sum(fusion.weight[f:f + c].sum(dtype=torch.int64) for f, c in own),
                             sum(fusion.tsdf_weight[f:f + c].sum(dtype=torch.int64) for f, c in own),
@@ -422,7 +442,7 @@ def main():
 
     # ---- timed region 2 (N > 1): the same jobs with each merge overlapped with the next job's fusion ----
     overlapped = None
-    if world > 1 and not a.no_overlap_merge:
+    if world > 1 and a.full and not a.no_overlap_merge:
         run_region(min(2, max(1, a.warmup)), True, None)
         dt2 = run_region(a.steps, True, None)
         overlapped = {"value": round(total_frames / dt2, 2), "unit": "frames/s", "ms_per_step": round(dt2 / a.steps * 1e3, 3),
@@ -431,7 +451,7 @@ def main():
 
     # ---- timed region 3 (N > 1): the same job VOXEL-sharded -- every rank fuses every frame into its x-slab, no merge ----
     voxel_sharded = None
-    if world > 1 and not a.no_voxel_sharded and int(grid.nvox[0]) >= world:
+    if world > 1 and a.full and not a.no_voxel_sharded and int(grid.nvox[0]) >= world:
         voxel_sharded = bench_voxel_sharded(a, dist, sdist, grid, fusions, (depth, rgb, poses, ks, feat, label_maps), new_volume,
                                             world, rank, device, L, stream, npy, npx)
 
@@ -457,25 +477,30 @@ def main():
         tmax = torch.tensor([dt4], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt4 = float(tmax.item())
-        st4 = fusion.stats()
-        # integrity: over all ranks, the weights of the owned stripes add up to the valid hits of all ranks' frames
-        own_w = sum(int(fusion.weight[f:f + c].sum(dtype=torch.int64)) for f, c in stripes)
-        sums = torch.tensor([own_w, st4["valid"]], dtype=torch.int64, device=device)
-        dist.all_reduce(sums)
-        w_all, v_all = (int(x) for x in sums.tolist())
-        if merge_state["mode"] == "all_reduce":
-            w_all //= world
-        assert w_all * a.steps == v_all, f"slab-pipelined merge: owned weights {w_all} x {a.steps} steps != valid hits {v_all}"
+        if a.dump_outputs:
+            dumps["slab_pipelined_merge"] = sample_volume(fusion, n_vox, world, rank, dist)
+        pipe_check = None
+        if a.full:
+            st4 = fusion.stats()
+            # integrity: over all ranks, the weights of the owned stripes add up to the valid hits of all ranks' frames
+            own_w = sum(int(fusion.weight[f:f + c].sum(dtype=torch.int64)) for f, c in stripes)
+            sums = torch.tensor([own_w, st4["valid"]], dtype=torch.int64, device=device)
+            dist.all_reduce(sums)
+            w_all, v_all = (int(x) for x in sums.tolist())
+            if merge_state["mode"] == "all_reduce":
+                w_all //= world
+            assert w_all * a.steps == v_all, f"slab-pipelined merge: owned weights {w_all} x {a.steps} steps != valid hits {v_all}"
+            pipe_check = {"owned_weight_sum_all_ranks": w_all, "valid_hits_all_ranks_per_step": v_all // a.steps}
         slab_pipe = {"value": round(total_frames / dt4, 2), "unit": "frames/s", "ms_per_step": round(dt4 / a.steps * 1e3, 3),
-                     "slabs": n_slabs, "merge_check": {"owned_weight_sum_all_ranks": w_all, "valid_hits_all_ranks_per_step": v_all // a.steps},
+                     "slabs": n_slabs, "merge_check": pipe_check,
                      "note": "the same single job as `value` (config 4's layout: frames sharded, one per-rank volume, one merge) with "
                              "the merge issued slab by slab on a communication stream while the next slab is fused; rank k ends "
                              "with the k-th part of every slab"}
         fusion.fuse_stats.zero_()
 
     # ---- N > 1: the headline is the better of the two forms of BASELINE config 4's job (frames sharded, one per-rank volume,
-    #      one merge per job) that have both just been timed over the same K steps and proved: merged after the fusion, or
-    #      merged slab by slab behind it.  Both are reported.
+    #      one merge per job) that have both just been timed over the same K steps (and proved, --full): merged after the fusion,
+    #      or merged slab by slab behind it.  Both are reported.
     headline_region, serial_merge = None, None
     if world > 1:
         headline_region = "serial_merge"
@@ -485,9 +510,11 @@ def main():
             headline_region = "slab_pipelined_merge"
             value = slab_pipe["value"]
             dt = dt4
+    if a.dump_outputs and rank == 0:  # (the region the headline timed)
+        write_dump(a.dump_outputs, dumps[headline_region or "serial_merge"])
 
     # ---- N > 1: the merged shard of a small sharded job against a single-rank fusion of ALL its frames ----
-    if world > 1 and a.check_frames > 0:
+    if world > 1 and a.full and a.check_frames > 0:
         pipe_fn = None
         if slab_pipe is not None:
             pipe_fn = lambda fz, fr, c: sdist.fuse_merge_pipelined(fz, fr, c, ws, n_slabs=slab_pipe["slabs"], comm_stream=comm_stream,
@@ -757,7 +784,7 @@ def main():
 
     # ---- N = 1: the job fused slab by slab (what the slab-pipelined merge of N > 1 does between its collectives) ----
     slabwise = None
-    if rank == 0 and world == 1 and windowed_headline(st) and not a.no_side:
+    if rank == 0 and world == 1 and a.full and windowed_headline(st) and not a.no_side:
         n_slabs = 8
         bounds = sdist.slab_bounds(int(grid.nvox[0]), n_slabs, ramp=True)
         x0s = (C.c_int32 * len(bounds))(*[b[0] for b in bounds])
@@ -795,14 +822,14 @@ def main():
 
     # ---- the other configurations and the copy rate of this box, measured in this run (rank 0, N = 1) ----
     side, copy_rate = None, None
-    if rank == 0 and world == 1 and not a.no_side and isinstance(a.grid, int) and a.grid == 256 and a.depth_kind == "A" and a.pose_kind == "look_at" and not a.labels \
+    if rank == 0 and world == 1 and a.full and not a.no_side and isinstance(a.grid, int) and a.grid == 256 and a.depth_kind == "A" and a.pose_kind == "look_at" and not a.labels \
             and a.feat_dtype == "f32" and a.width == 640 and a.height == 480:
         copy_rate = hbm_copy_rate(device)
         side = side_workloads(a, device, L, (depth, rgb, poses, ks, feat), npy, npx)
     if roofline is not None and copy_rate is not None:
         roofline["hbm_copy_GBps"] = copy_rate
         roofline["frac_of_copy_rate"] = round(roofline["achieved"] / copy_rate, 4)
-    # ---- roofline.traffic measured in THIS run (rank 0, N = 1, the default command): PMC counters cannot be read in-process, so
+    # ---- roofline.traffic measured in THIS run (rank 0, N = 1, --full): PMC counters cannot be read in-process, so
     #      one job is run twice more as a child under rocprofv3 --pmc (FETCH_SIZE, then WRITE_SIZE: separate passes)
     if roofline is not None and side is not None and not a.no_pmc and roofline.get("kernel") == "fuse_window_kernel":
         m = measure_traffic(a)
@@ -811,9 +838,9 @@ def main():
             roofline["traffic_source"] = m["source"]
             roofline["traffic_read_bytes"], roofline["traffic_write_bytes"] = m["read"], m["write"]
 
-    # ---- CPU baseline: the oracle on a bounded sample of the same frames (rank 0, N=1 only) ----
+    # ---- CPU baseline: the oracle on a bounded sample of the same frames (rank 0, N=1 only; --full, or --cpu-frames n > 0) ----
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_frames != 0:
+    if rank == 0 and world == 1 and (a.cpu_frames > 0 or (a.full and a.cpu_frames < 0)):
         cpu = cpu_baseline(a, grid, depth, rgb, poses, ks, feat, npy, npx)
 
     if rank == 0:
@@ -845,6 +872,7 @@ def main():
                                         "threshold": merge_state["last_merge"]["threshold"], "probe": merge_state["sparse_note"]}
                                        if merge_state["last_merge"] else None),
                 "rccl_world": dist.get_world_size() if world > 1 else 1, "backend": a.backend if world > 1 else None,
+                "full": a.full,
             },
             "headline_region": headline_region,
             "serial_merge": serial_merge,
@@ -862,7 +890,7 @@ def main():
         }
         if api_b1 is not None:
             out["api_b1"] = api_b1
-            if side is not None:  # (the driver's default line: the reference's own call pattern beside the other workloads)
+            if side is not None:  # (the --full line: the reference's own call pattern beside the other workloads)
                 side["api_b1"] = api_b1
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -873,6 +901,52 @@ def main():
 
 def windowed_headline(st):
     return st.get("window_rows", 0) > 0
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of samples in all (the files with their headers stay under 64 MB)
+DUMP_BUFFERS = ("tsdf", "rgb", "weight", "tsdf_weight", "clip_feat", "labels_one_hot")
+
+
+def sample_volume(fz, n_vox, world, rank, dist):
+    """--dump-outputs: the volume's buffers -- what a caller of the fused path reads -- at a fixed, seeded sample of voxels (the
+    same voxels in every run with the same arguments), as host arrays: float32 for the float buffers, float64 (exact) for the
+    counters.  N > 1: every rank contributes the sampled rows it holds merged (its stripes after a reduce-scatter; rank 0 alone
+    when every rank holds the whole volume) and the pieces are summed, so the arrays are those of the merged volume."""
+    import numpy as np
+
+    names = [k for k in DUMP_BUFFERS if k in fz._buffers]
+    per_voxel = 8 + sum((4 if fz._buffers[k].is_floating_point() else 8) * fz._buffers[k][0].numel() for k in names)
+    k = min(n_vox, DUMP_BYTES // per_voxel)
+    idx = torch.randperm(n_vox, generator=torch.Generator().manual_seed(5150))[:k].sort().values
+    dev = fz._buffers["tsdf"].device
+    idx_d = idx.to(dev)
+    mine = None
+    if world > 1:
+        stripes = fz._shard_stripes
+        if stripes is None:
+            mine = torch.full((k,), rank == 0, dtype=torch.bool, device=dev)
+        else:
+            first = torch.tensor(sorted(f for f, _ in stripes), dtype=torch.int64, device=dev)
+            end = first + torch.tensor([c for _, c in sorted(stripes)], dtype=torch.int64, device=dev)
+            pos = torch.searchsorted(first, idx_d, right=True) - 1
+            mine = (pos >= 0) & (idx_d < end[pos.clamp_min(0)])
+    out = {"sample_voxel_index": idx.double().numpy()}
+    for name in names:
+        t = getattr(fz, name)[idx_d]  # (through the module: pending frames and the deferred clear are resolved first)
+        t = t.float() if t.is_floating_point() else t.double()
+        if mine is not None:
+            t = torch.where(mine.view(-1, *([1] * (t.dim() - 1))), t, torch.zeros_like(t))
+            dist.all_reduce(t)
+        out[name] = np.ascontiguousarray(t.cpu().numpy())
+    return out
+
+
+def write_dump(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def measure_traffic(a, timeout_s=150, overrides=None):
@@ -936,7 +1010,7 @@ SIDE_TRAFFIC_CASES = {  # side workload -> the main-path flags of the same job (
 
 def side_traffic(a, path):
     """`bench.py --side-traffic`: the counter traffic (HBM bytes per window of the row kernel) of every side workload's job, two
-    profiler passes each, written to `path` (committed as profiles/r06/side_traffic.json: the default run, which must stay
+    profiler passes each, written to `path` (committed as profiles/r06/side_traffic.json: the --full run, which must stay
     within minutes, quotes it instead of running eight more child processes)."""
     out = {}
     for name, ov in SIDE_TRAFFIC_CASES.items():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # development A/B of the order-free row kernel's compile-time options on one box:
 #   bash tools/of_ab.sh "<-D flags>[;ENV=..]" ...       (first line: the build as it is)
-run() { for k in ${KINDS:-A B}; do env SAF_WIN_FORM=sums $2 timeout -k 10 200 python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1 --depth-kind $k 2>/dev/null | python3 -c "
+run() { for k in ${KINDS:-A B}; do env SAF_WIN_FORM=sums $2 timeout -k 10 200 python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1 --depth-kind $k 2>/dev/null | python3 -c "
 import sys,json
 t=sys.stdin.read().strip().splitlines()
 try:

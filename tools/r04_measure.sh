@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-4 measurement set (run on a GPU box): the forms of the row kernel, the widths only the brick form takes.
 OUT=gpurun_out/r04m; mkdir -p $OUT
-B="timeout -k 10 300 python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1"
+B="timeout -k 10 300 python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1"
 line() { python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$1', d['value'], 'frames/s', d['ms_per_step'], 'ms/step  row kernel per window', r['avg_launch_us'], 'us frac', r['frac'], ' isolated', (r.get('isolated') or {}).get('avg_launch_us'), (r.get('isolated') or {}).get('frac'), ' classify', d['kernel_breakdown']['sweep_us'], 'us')"; }
 {
 for form in sums rows bricks; do for kind in A B; do SAF_WIN_FORM=$form $B --depth-kind $kind 2>/dev/null | line "form=$form depth=$kind 256^3x512 f32:"; done; done

@@ -4,7 +4,7 @@
 # SAF_CLEAR_WGS = workgroups per CU of the clear kernel (default 4 beside a row kernel, 16 alone).
 OUT=${1:-gpurun_out/r05clear}
 mkdir -p $OUT
-B="python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --no-pmc --steps 10 --warmup 3"
+B="python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --no-pmc --steps 10 --warmup 3"
 for k in ${KINDS:-B A}; do
   for v in ${VARS:-0 1:2 1:4 1:8 1:16 0 1:4}; do
     b=${v%%:*}; w=${v##*:}; [ "$w" = "$v" ] && w=""

@@ -10,7 +10,7 @@ mkdir -p $OUT
 C=spatially_aware_ai_amd/csrc
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Wno-unused-function"
 OTHERS=$(ls $C/*.o | grep -v saf_window.o | tr "\n" " ")
-B="python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --no-pmc"
+B="python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --no-pmc"
 line() { python3 -c "
 import sys,json
 t=sys.stdin.read().strip().splitlines()

@@ -8,7 +8,7 @@ FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Wno-unused-
 OTHERS=$(ls $C/*.o | grep -v saf_window.o | tr "\n" " ")
 /opt/rocm/bin/hipcc $FLAGS -DSAF_WIN_TIMING -c $C/saf_window.hip -o /tmp/win_timing.o && \
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libsaf_timing.so /tmp/win_timing.o $OTHERS || exit 1
-B="python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --no-pmc --steps 1 --warmup 0"
+B="python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --no-pmc --steps 1 --warmup 0"
 for cfg in "" "--feat-dtype bf16" "--feat-dtype bf16 --labels" "--feat-dtype bf16 --labels --label-kind world"; do
   for ov in 0 1; do
     SAF_LIB_PATH=/tmp/libsaf_timing.so SAF_WIN_OVERLAP=$ov timeout -k 10 200 $B $cfg 2>&1 >/dev/null | grep "win timing" | tail -2 | sed "s/^/[${cfg:-f32}] overlap=$ov: /"

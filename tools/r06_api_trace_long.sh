@@ -3,7 +3,7 @@
 # rocprofv3 --kernel-trace: per window the row kernel's start / end, the wait before it, and the classification launches beside it.
 OUT=${1:-gpurun_out/r06apil}; N=${2:-2048}
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --cpu-frames 0 --no-pmc --no-side --end-to-end 0 --steps 2 --warmup 1 --api-b1 $N > $OUT/api.json 2> $OUT/api.err
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --full --cpu-frames 0 --no-pmc --no-side --end-to-end 0 --steps 2 --warmup 1 --api-b1 $N > $OUT/api.json 2> $OUT/api.err
 python3 - <<PY
 import csv, glob, json
 f = sorted(glob.glob("$OUT/trace/*/*_kernel_trace.csv"))[-1]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs bench.py over the shapes the windowed and the per-frame path must both survive (each run checks the
 # fused frame count and the weight sum against the kernel counters).  Usage on a GPU box: bash tools/soak.sh
-run() { echo "## $*"; timeout -k 10 300 python bench.py --cpu-frames 0 "$@" 2>&1 | grep -o "\"value\": [0-9.]*\|Error.*\|Assertion.*" | tr '\n' ' '; echo; }
+run() { echo "## $*"; timeout -k 10 300 python bench.py --full --cpu-frames 0 "$@" 2>&1 | grep -o "\"value\": [0-9.]*\|Error.*\|Assertion.*" | tr '\n' ' '; echo; }
 run --steps 10 --warmup 1
 run --steps 4 --warmup 1 --labels
 run --steps 4 --warmup 1 --labels --depth-kind B

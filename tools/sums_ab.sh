@@ -9,5 +9,5 @@ try:
 except Exception as e:
     print('$1 FAILED', e, t[-3:])"; }
 for form in ${FORMS:-rows sums}; do for k in A B; do
-  SAF_WIN_FORM=$form timeout -k 10 200 python3 bench.py --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1 --depth-kind $k "$@" 2>gpurun_out/sums_ab_$form$k.err | line "form=$form depth=$k"
+  SAF_WIN_FORM=$form timeout -k 10 200 python3 bench.py --full --cpu-frames 0 --no-side --end-to-end 0 --steps 3 --warmup 1 --depth-kind $k "$@" 2>"${TMPDIR:-/tmp}/sums_ab_$form$k.err" | line "form=$form depth=$k"
 done; done

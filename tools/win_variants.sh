@@ -13,7 +13,7 @@ for v in ${VARIANTS:-base P2=3 P2=2}; do
   /opt/rocm/bin/hipcc $FLAGS $def -c $C/saf_window.hip -o /tmp/win_$tag.o && \
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libsaf_$tag.so /tmp/win_$tag.o $OTHERS || { echo "$tag BUILD FAILED"; continue; }
   for ov in 1 0; do
-    SAF_WIN_OVERLAP=$ov SAF_LIB_PATH=/tmp/libsaf_$tag.so python3 bench.py --steps 5 --warmup 2 --cpu-frames 0 ${BENCH_ARGS} > $OUT/${tag}_ov$ov.json 2> $OUT/${tag}_ov$ov.err
+    SAF_WIN_OVERLAP=$ov SAF_LIB_PATH=/tmp/libsaf_$tag.so python3 bench.py --full --steps 5 --warmup 2 --cpu-frames 0 ${BENCH_ARGS} > $OUT/${tag}_ov$ov.json 2> $OUT/${tag}_ov$ov.err
     python3 - <<PY
 import json
 try:

@@ -15,7 +15,7 @@ for v in ${VARIANTS:-base EMU=2}; do
   /opt/rocm/bin/hipcc $FLAGS $def -c $C/saf_window.hip -o /tmp/win_$tag.o && \
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/libsaf_$tag.so /tmp/win_$tag.o $OTHERS || { echo "$tag BUILD FAILED"; continue; }
   for x in ${XS:-0 1}; do for ov in ${OVS:-0 1}; do
-    SAF_WIN_XCD=$x SAF_WIN_OVERLAP=$ov SAF_LIB_PATH=/tmp/libsaf_$tag.so python3 bench.py --steps 4 --warmup 1 --cpu-frames 0 ${BENCH_ARGS} > $OUT/${tag}_x${x}_ov$ov.json 2> $OUT/${tag}_x${x}_ov$ov.err
+    SAF_WIN_XCD=$x SAF_WIN_OVERLAP=$ov SAF_LIB_PATH=/tmp/libsaf_$tag.so python3 bench.py --full --steps 4 --warmup 1 --cpu-frames 0 ${BENCH_ARGS} > $OUT/${tag}_x${x}_ov$ov.json 2> $OUT/${tag}_x${x}_ov$ov.err
     python3 - <<PY
 import json
 try:
