@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SAF_ABI_VERSION 3
+#define SAF_ABI_VERSION 4
 
 enum saf_status {
   SAF_OK = 0,
@@ -341,6 +341,52 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
 
 /* Device scratch saf_query_scan needs (the surgery weights w[n_text]); 0 for other epilogues. */
 size_t saf_query_workspace_bytes(int32_t n_text, int32_t epilogue);
+
+/*
+ * Top-k labels per row (ABI 4; eval_scannet_segmentation.py:546-561 -- `segment`, of whose argsort the eval reads columns [:, :5]
+ * and [:, 0]): per row the k labels of largest scale * <f^, t_l>, best first, f^ the row under `normalize` (the eval: SAF_NORM_L2_CLAMP,
+ * scale 100).  Of equal scores the smaller label comes first.
+ *   feats / text / normalize as saf_query_scan; n_text >= 1
+ *   k          1 <= k <= 8 and k <= n_text (SAF_E_INVALID otherwise)
+ *   out_index  [n_rows, k] i32
+ *   out_prob   [n_rows, k] f32 or NULL: the labels' softmax probabilities over ALL n_text labels (the reference's `relevance`)
+ *   workspace  saf_query_topk_workspace_bytes(n_rows, n_text, k) bytes, 256-byte aligned (0 for n_text <= 32): the rows' running
+ *              top-k and softmax maximum / denominator between blocks of 64 (32 at feat_dim > 512) labels
+ * Numerics as saf_query_scan: the split scan for feat_dim % 16 == 0 (SAF_Q_SPLIT=0: exact fp32), exact fp32 matrix instructions for
+ * feat_dim % 8 == 0; other widths (or rows not on 16-byte boundaries) one wave per row, fp32.
+ */
+size_t saf_query_topk_workspace_bytes(int64_t n_rows, int32_t n_text, int32_t k);
+int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride, int32_t feat_dim, const float* text,
+                   int32_t n_text, int64_t text_stride, float scale, int32_t normalize, int32_t k, int32_t* out_index,
+                   float* out_prob, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Exact nearest neighbour (ABI 4; eval_scannet_segmentation.py:585-586, scipy.spatial.KDTree(pred).query(gt)): for every query
+ * point the reference point of smallest squared distance, computed in fp64 from the fp32 coordinates ((qx-rx)^2 + (qy-ry)^2 +
+ * (qz-rz)^2 in that order); of equal distances the smaller reference index.
+ *   ref        [n_ref, 3] f32, n_ref >= 1;  query [n_query, 3] f32 (n_query = 0: nothing to do)
+ *   out_index  [n_query] i32;  out_dist2 [n_query] f64 or NULL
+ *   workspace  saf_nearest_workspace_bytes(n_ref, n_query) bytes, 256-byte aligned
+ * Method: a uniform grid over the reference points' bounding box (at most n_ref cells, sized on the device: no host
+ * synchronisation), the points counting-sorted into cells, each query searching rings of cells outward until no unsearched cell
+ * can hold a point as near.  Coordinates must be finite (the Python layer checks); any input stays in bounds.
+ */
+size_t saf_nearest_workspace_bytes(int64_t n_ref, int64_t n_query);
+int saf_nearest_points(const float* ref, int64_t n_ref, const float* query, int64_t n_query, int32_t* out_index, double* out_dist2,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Segmentation scoring counts (ABI 4; eval_scannet_segmentation.py:589-601 and sklearn's confusion_matrix(labels=range(L))):
+ *   gt         [n] i32 ground-truth class per vertex; a vertex with gt outside [0, n_classes) (-1: unlabelled) is skipped
+ *   pred       [n, pred_stride] i32 predicted labels, best first; topk <= pred_stride
+ *   cmat       [n_classes, n_classes] i64: cmat[g, p0] += 1 (p0 = pred[i, 0]; a p0 outside [0, n_classes) is left out of cmat only)
+ *   ncorrect_top1 / ncorrect_topk / ntotal  [n_classes] i64: p0 == g / g among the first topk / every counted vertex
+ *   accumulate 0: the outputs are zeroed first; otherwise the counts are added to them (a confusion matrix over many scenes)
+ * Exact integer counts, independent of scheduling.
+ */
+int saf_segmentation_counts(const int32_t* gt, const int32_t* pred, int64_t n, int32_t pred_stride, int32_t topk, int32_t n_classes,
+                            int64_t* cmat, int64_t* ncorrect_top1, int64_t* ncorrect_topk, int64_t* ntotal, int32_t accumulate,
+                            void* stream);
 
 /*
  * Wide scan (BASELINE config 5: hundreds to thousands of text queries over a 16-bit feature

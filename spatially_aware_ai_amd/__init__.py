@@ -17,6 +17,7 @@ __all__ = [
     "scene_bounds",
     "label_components",
     "discover_objects",
+    "evaluation",
 ]
 
 
@@ -29,4 +30,8 @@ def __getattr__(name):
         from . import clip_seem_fusion as _m
 
         return getattr(_m, name)
+    if name == "evaluation":
+        import importlib
+
+        return importlib.import_module(".evaluation", __name__)
     raise AttributeError(name)

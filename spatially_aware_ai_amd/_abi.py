@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 SAF_OK = 0
 SAF_E_INVALID = -1
@@ -139,6 +139,21 @@ PROTOTYPES = {
             C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int64, _fp, _fp, _fp, C.c_int64,
             _fp, C.c_size_t, _fp,
         ],
+    ),
+    "saf_query_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "saf_query_topk": (
+        C.c_int,
+        [
+            _fp, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+            _fp, C.c_int32, C.c_int64, C.c_float, C.c_int32,
+            C.c_int32, _fp, _fp, _fp, C.c_size_t, _fp,
+        ],
+    ),
+    "saf_nearest_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "saf_nearest_points": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "saf_segmentation_counts": (
+        C.c_int,
+        [_fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, _fp],
     ),
     "saf_merge_finalize": (C.c_int, [C.POINTER(SafVolume), C.c_int64, C.c_int64, _fp]),
     "saf_mean_to_sum": (C.c_int, [C.POINTER(SafVolume), C.c_int64, C.c_int64, _fp]),

@@ -253,6 +253,118 @@ __device__ __forceinline__ T row_of_half(T v, int src, int h) {
 // ---- epilogue on the MFMA accumulator layout: this lane holds column n = m (+32 t) of 16 rows.  `inv`: the factor of row m
 // (1 / norm); CS (the split scan): the row's and the columns' power-of-two scales 2^rexp, 2^cexp undone by one v_ldexp_f32,
 // which cannot leave fp32's range half-way the way two multiplications can.
+// ---- top-k labels per row (saf_query_topk; eval_scannet_segmentation.py:546-561): the scan's epilogue keeps, per row, the k best
+// (score, label) pairs and the softmax's running maximum and denominator.  Over more than one block of labels the state travels
+// between the blocks' launches through the workspace (k pairs + 2 floats per row).  In the epilogue a row's list lies ACROSS the
+// lanes of its half -- lane j < k holds entry j -- so nothing is a per-lane array: each round takes the best candidate of the block
+// not yet taken (two reductions over the half) and, if it beats the carried k-th, shifts it into the list by one DPP row shift.
+// A block's labels all come after the carried ones, so the rounds stop at the first candidate that does not beat the k-th.
+enum { EPI_TOPK = 4 };  // internal
+constexpr int kTopkMax = 8;
+constexpr int kNoLabel = 0x7fffffff;
+struct TopkArgs {
+  float* st_val = nullptr;  // [n_rows, k] carried scaled scores, best first (more than one label block)
+  int* st_idx = nullptr;    // [n_rows, k] their labels
+  float* st_max = nullptr;  // [n_rows] running maximum of the scaled scores
+  float* st_sum = nullptr;  // [n_rows] running sum of exp(score - maximum)
+  int* out_index = nullptr; // [n_rows, k]
+  float* out_prob = nullptr;
+  int k = 0, col0 = 0, first = 1, last = 1;
+};
+
+// (score a, label ia) ranks before (b, ib): the larger score, of equal scores the smaller label
+__device__ __forceinline__ bool topk_before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_lane_i(int x) {
+  return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
+}
+__device__ __forceinline__ int half_min_i(int x) {  // over the 32 lanes of this half (as half_max)
+  x = min(x, dpp_lane_i<0xB1>(x));
+  x = min(x, dpp_lane_i<0x4E>(x));
+  x = min(x, dpp_lane_i<0x141>(x));
+  x = min(x, dpp_lane_i<0x140>(x));
+  const auto r = __builtin_amdgcn_permlane16_swap((uint32_t)x, (uint32_t)x, false, false);
+  return min((int)r[0], (int)r[1]);
+}
+// lane `j` of this half (j wave-uniform)
+template <typename T>
+__device__ __forceinline__ T lane_of_half(T v, int j, int h) {
+  const int lo = __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j), hi = __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j + 32);
+  return __builtin_bit_cast(T, h ? hi : lo);
+}
+
+// One row's block of scores: sc[t] = the scaled score of label col0 + m + 32 t of the block (ok[t]: the label exists).
+template <int TILES>
+__device__ __forceinline__ void topk_row(const float (&sc)[TILES], const bool (&ok)[TILES], int m, int h, int64_t r, int64_t n_rows,
+                                         const TopkArgs& tk) {
+  const bool live = r < n_rows;
+  const int k = tk.k;
+  auto label = [&](int t) { return ok[t] ? tk.col0 + m + 32 * t : kNoLabel; };
+  float cs = -INFINITY, rm = -INFINITY, rs = 0.0f;  // this lane's entry of the list; the row's running max and denominator
+  int ci = kNoLabel;
+  if (!tk.first && live) {
+    if (m < k) {
+      cs = tk.st_val[r * k + m];
+      ci = tk.st_idx[r * k + m];
+    }
+    rm = tk.st_max[r];
+    rs = tk.st_sum[r];
+  }
+  // softmax over all labels, a block at a time: relevance = (100 * dotprod).softmax(dim=-1)   eval_scannet_segmentation.py:558
+  float bm = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) bm = fmaxf(bm, ok[t] ? sc[t] : -INFINITY);
+  const float nm = fmaxf(rm, half_max(bm));
+  float e = 0.0f;
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) e += ok[t] && sc[t] > -INFINITY ? expf(sc[t] - nm) : 0.0f;
+  rs = (rm > -INFINITY ? rs * expf(rm - nm) : 0.0f) + half_sum(e);
+  rm = nm;
+  // the block's candidates in rank order, each shifted into the list while it beats the list's k-th
+  float ps = INFINITY;
+  int pi = -1;
+#pragma nounroll
+  for (int j = 0; j < k; ++j) {
+    float bs = -INFINITY;
+    int bi = kNoLabel;
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+      const int l = label(t);
+      if (ok[t] && topk_before(ps, pi, sc[t], l) && topk_before(sc[t], l, bs, bi)) {
+        bs = sc[t];
+        bi = l;
+      }
+    }
+    const float xs = half_max(bs);
+    const int xi = half_min_i(bs == xs ? bi : kNoLabel);
+    const bool take = live && xi != kNoLabel && topk_before(xs, xi, lane_of_half(cs, k - 1, h), lane_of_half(ci, k - 1, h));
+    if (!__builtin_amdgcn_ballot_w64(take)) break;
+    // entry m - 1 (row_shr:1; lane m = 0 is the list's head and does not read it)
+    const float us = __builtin_bit_cast(float, dpp_lane_i<0x111>(__builtin_bit_cast(int, cs)));
+    const int ui = dpp_lane_i<0x111>(ci);
+    if (take && !topk_before(cs, ci, xs, xi)) {
+      const bool here = m == 0 || topk_before(us, ui, xs, xi);
+      cs = here ? xs : us;
+      ci = here ? xi : ui;
+    }
+    ps = xs;
+    pi = xi;
+  }
+  if (!live || m >= k) return;
+  if (tk.last) {
+    tk.out_index[r * k + m] = ci == kNoLabel ? -1 : ci;
+    if (tk.out_prob) tk.out_prob[r * k + m] = ci == kNoLabel ? 0.0f : expf(cs - rm) / rs;
+  } else {
+    tk.st_val[r * k + m] = cs;
+    tk.st_idx[r * k + m] = ci;
+    if (m == 0) {
+      tk.st_max[r] = rm;
+      tk.st_sum[r] = rs;
+    }
+  }
+}
+
 __device__ __forceinline__ float row_inverse(float ss, int normalize) {
   // clip_feat /= norm ; nan_to_num: an all-zero row gives zeros       clip_seem_fusion.py:508-511
   // SAF_NORM_L2_CLAMP: norm.clamp_min(0.1)                            eval_scannet_segmentation.py:549-551
@@ -263,7 +375,7 @@ template <int EPI, int TILES, bool CS>
 __device__ __forceinline__ void scan_epilogue(const f32x16 (&acc)[TILES], float inv, int rexp, const int (&cexp)[TILES], int64_t tile,
                                               int64_t n_rows, int L, float scale, const float (&wl)[TILES],
                                               float* __restrict__ out, float* __restrict__ out_last, int64_t out_stride,
-                                              int out_col0, float* __restrict__ stage = nullptr) {
+                                              int out_col0, float* __restrict__ stage = nullptr, const TopkArgs& tk = TopkArgs{}) {
   const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
   // `stage` (this wave's 8 x L floats of LDS, or null): the [N, L] matrix leaves as whole 16-byte pieces of 8 rows at a time --
   // registers 4j .. 4j + 3 hold rows 8j .. 8j + 7 of the tile, 32 L contiguous bytes of the output -- instead of a row's 32
@@ -283,6 +395,12 @@ __device__ __forceinline__ void scan_epilogue(const f32x16 (&acc)[TILES], float 
       ok[t] = (m + 32 * t) < L;
       val[t] = acc[t][i] * inv_i;  // cosine score S[r][n]
       if (CS) val[t] = ldexpf(val[t], -(rexp_i + cexp[t]));
+    }
+    if constexpr (EPI == EPI_TOPK) {
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) val[t] *= scale;
+      topk_row<TILES>(val, ok, m, h, r, n_rows, tk);
+      continue;
     }
     if (EPI == SAF_Q_SOFTMAX) {
       // relevance = (100 * img_feats @ text.T).softmax(-1)            clipfusion.py:902-903
@@ -346,7 +464,7 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
                                                                 int L, int64_t tstride, float scale, int normalize,
                                                                 const float* __restrict__ wts, float* __restrict__ out,
                                                                 float* __restrict__ out_last, int64_t out_stride, int out_col0,
-                                                                int /*stage_on: the split scan's*/) {
+                                                                int /*stage_on: the split scan's*/, TopkArgs tk) {
   // (out_stride / out_col0: where this launch's L columns lie in the output row -- L and 0, or one 64-label block of a wider row)
   extern __shared__ __attribute__((aligned(16))) float s_text[];  // [TILES*32][D + 4], rows >= L are zero
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -432,7 +550,8 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
     }
     ss += __shfl_xor(ss, 32);  // both halves of row m
     const int none[TILES] = {};
-    scan_epilogue<EPI, TILES, false>(acc, row_inverse(ss, normalize), 0, none, tile, n_rows, L, scale, wl, out, out_last, out_stride, out_col0);
+    scan_epilogue<EPI, TILES, false>(acc, row_inverse(ss, normalize), 0, none, tile, n_rows, L, scale, wl, out, out_last, out_stride, out_col0,
+                                     nullptr, tk);
   }
 }
 
@@ -485,7 +604,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
                                                          const float* __restrict__ text, int L, int64_t tstride, float scale,
                                                          int normalize, const float* __restrict__ wts, float* __restrict__ out,
                                                          float* __restrict__ out_last, int64_t out_stride, int out_col0,
-                                                         int stage_on) {
+                                                         int stage_on, TopkArgs tk) {
   // [TILES*32] label rows of D/16 k-steps x {half 0, half 1} x {hi, lo} x 8 halfs (+16 bytes: the rows' reads fall on different
   // banks), then the labels' scale exponents
   extern __shared__ __attribute__((aligned(16))) unsigned char s_split[];
@@ -657,7 +776,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
     }
     ss = other_half_sum(ss);  // both halves of row m
     scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), re, ce, tile, n_rows, L, scale, wl, out, out_last,
-                                    out_stride, out_col0, stage);
+                                    out_stride, out_col0, stage, tk);
   }
 }
 
@@ -679,7 +798,7 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
                                                            const float* __restrict__ text, int L, int64_t tstride, float scale,
                                                            int normalize, const float* __restrict__ wts, float* __restrict__ out,
                                                            float* __restrict__ out_last, int64_t out_stride, int out_col0,
-                                                           int stage_on) {
+                                                           int stage_on, TopkArgs tk) {
   static_assert(FT == SAF_F16 || FT == SAF_BF16, "16-bit volumes");
   extern __shared__ __attribute__((aligned(16))) unsigned char s_split[];  // as query_split_kernel's, the pieces in plain k order
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -860,14 +979,14 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
     }
     ss = other_half_sum(ss);  // both halves of row m
     scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), re, ce, tile, n_rows, L, scale, wl, out, out_last,
-                                    out_stride, out_col0, stage);
+                                    out_stride, out_col0, stage, tk);
   }
 }
 
 template <int EPI, int FT, int TILES, int TH, int SPLIT>  // SPLIT: 0 the exact-fp32 scan, 1 the split scan, 2 its 16-bit-volume form
 int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
                    float scale, int normalize, const float* wts, float* out, float* out_last, int per_cu, size_t shmem, hipStream_t s,
-                   int64_t out_stride, int out_col0) {
+                   int64_t out_stride, int out_col0, const TopkArgs& tk) {
   auto fn = SPLIT == 2 ? query_split16_kernel<EPI, (FT == SAF_F32 ? SAF_F16 : FT), TILES, TH>
             : SPLIT ? query_split_kernel<EPI, FT, TILES, TH> : query_mfma_kernel<EPI, FT, TILES, TH>;
   constexpr int kWavesTh = TH / 64;
@@ -886,7 +1005,7 @@ int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, co
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(TH), shmem, s, feats, n_rows, fstride, D, text, L,
-                     tstride, scale, normalize, wts, out, out_last, out_stride > 0 ? out_stride : (int64_t)L, out_col0, stage ? 1 : 0);
+                     tstride, scale, normalize, wts, out, out_last, out_stride > 0 ? out_stride : (int64_t)L, out_col0, stage ? 1 : 0, tk);
   return check_launch(SPLIT == 2 ? "query_split16_kernel" : SPLIT ? "query_split_kernel" : "query_mfma_kernel");
 }
 
@@ -898,7 +1017,8 @@ inline bool split_wanted(int D) {
 
 template <int EPI, int FT, int TILES>
 int launch_mfma_t(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0) {
+                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0,
+                  const TopkArgs& tk) {
   const bool split = split_wanted(D);
   // (the split scan's label rows take the bytes of the fp32 rows -- two fp16 pieces per value -- plus a scale per label)
   const size_t shmem = (size_t)TILES * 32 * (D + 4) * sizeof(float) + (split ? (size_t)TILES * 32 * sizeof(float) : 0);
@@ -906,7 +1026,7 @@ int launch_mfma_t(const void* feats, int64_t n_rows, int64_t fstride, int D, con
   // SAF_Q_THREADS (read per call; development): 256 or 512 threads per workgroup whatever the tiles leave room for
   const char* th_env = getenv("SAF_Q_THREADS");
   const bool wide = th_env ? atoi(th_env) == 512 : per_cu <= 1;
-#define SAF_Q_GO(TH, SP) launch_mfma_th<EPI, FT, TILES, TH, SP>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, per_cu, shmem, s, out_stride, out_col0)
+#define SAF_Q_GO(TH, SP) launch_mfma_th<EPI, FT, TILES, TH, SP>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, per_cu, shmem, s, out_stride, out_col0, tk)
   // a 16-bit volume whose rows lie on 16-byte boundaries: one load per k-step in the matrix instruction's layout, one piece per feature
   const char* e16 = getenv("SAF_Q_SPLIT16");  // (0: through the fp32 form, development / A-B)
   if (split && FT != SAF_F32 && fstride % 8 == 0 && !(e16 && atoi(e16) == 0)) return wide ? SAF_Q_GO(512, 2) : SAF_Q_GO(256, 2);
@@ -926,24 +1046,25 @@ inline bool mfma_ok(int ft, int64_t fstride, int D, int L, const void* feats) {
 
 template <int EPI, int FT>
 int launch_mfma_f(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0) {
+                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0,
+                  const TopkArgs& tk) {
   return L > 32 ? launch_mfma_t<EPI, FT, 2>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, out_stride, out_col0)
+                                            out_last, s, out_stride, out_col0, tk)
                 : launch_mfma_t<EPI, FT, 1>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, out_stride, out_col0);
+                                            out_last, s, out_stride, out_col0, tk);
 }
 
 template <int EPI>
 int launch_mfma(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L,
                 int64_t tstride, float scale, int normalize, const float* wts, float* out, float* out_last,
-                hipStream_t s, int64_t out_stride = 0, int out_col0 = 0) {
+                hipStream_t s, int64_t out_stride = 0, int out_col0 = 0, const TopkArgs& tk = TopkArgs{}) {
   switch (ft) {
     case SAF_BF16:
-      return launch_mfma_f<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0);
+      return launch_mfma_f<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
     case SAF_F16:
-      return launch_mfma_f<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0);
+      return launch_mfma_f<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
     default:
-      return launch_mfma_f<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0);
+      return launch_mfma_f<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
   }
 }
 
@@ -1017,6 +1138,109 @@ int launch(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, co
   }
 }
 
+// Top-k for shapes the matrix scans do not take (feat_dim % 8 != 0, unaligned rows): one wave per row as query_kernel, the row's
+// scaled scores in LDS, then k rounds of a wave-wide arg-max over the labels ranked after the previous round's pick.
+template <int FT>
+__global__ __launch_bounds__(kQThreads) void topk_rows_kernel(const void* __restrict__ feats, int64_t n_rows, int64_t fstride, int D,
+                                                              const float* __restrict__ text, int L, int64_t tstride, float scale,
+                                                              int normalize, int k, int* __restrict__ out_index,
+                                                              float* __restrict__ out_prob) {
+  extern __shared__ float s_mem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Dp = (D + 3) & ~3, Lp = (L + 3) & ~3;
+  float* row = s_mem + (size_t)wave * (Dp + Lp);
+  float* sc = row + Dp;
+  for (int64_t r0 = (int64_t)blockIdx.x * kQWaves; r0 < n_rows; r0 += (int64_t)gridDim.x * kQWaves) {
+    const int64_t r = r0 + wave;
+    const bool active = r < n_rows;
+    if (active) {
+      float ss = 0.f;
+      for (int c = lane; c < D; c += 64) {
+        const float x = load_feat<FT>(feats, r * fstride + c);
+        row[c] = x;
+        ss += x * x;
+      }
+      if (normalize) {
+        float norm = sqrtf(wave_sum(ss));
+        if (normalize == SAF_NORM_L2_CLAMP) norm = norm < 0.1f ? 0.1f : norm;
+        for (int c = lane; c < D; c += 64) {
+          float q = row[c] / norm;
+          if (normalize == SAF_NORM_L2) {
+            if (q != q) q = 0.f;
+            if (__builtin_isinf(q)) q = q > 0.f ? 3.4028234663852886e38f : -3.4028234663852886e38f;
+          }
+          row[c] = q;
+        }
+      }
+      for (int l = 0; l < L; ++l) {
+        const float* t = text + (int64_t)l * tstride;
+        float acc = 0.f;
+        for (int c = lane; c < D; c += 64) acc = __builtin_fmaf(row[c], t[c], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) sc[l] = scale * acc;
+      }
+    }
+    __syncthreads();  // sc[] written by lane 0, read by all lanes below
+    if (active) {
+      float mx = -INFINITY;
+      for (int l = lane; l < L; l += 64) mx = fmaxf(mx, sc[l]);
+      mx = wave_max(mx);
+      float sum = 0.f;
+      for (int l = lane; l < L; l += 64) sum += sc[l] > -INFINITY ? expf(sc[l] - mx) : 0.0f;
+      sum = wave_sum(sum);
+      float ps = INFINITY;
+      int pi = -1;
+      for (int j = 0; j < k; ++j) {
+        float bs = -INFINITY;
+        int bi = kNoLabel;
+        for (int l = lane; l < L; l += 64) {
+          const float v = sc[l];
+          if (topk_before(ps, pi, v, l) && topk_before(v, l, bs, bi)) {
+            bs = v;
+            bi = l;
+          }
+        }
+        const float xs = wave_max(bs);
+        int xi = bs == xs ? bi : kNoLabel;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) xi = min(xi, __shfl_xor(xi, o));
+        if (lane == 0) {
+          out_index[r * k + j] = xi == kNoLabel ? -1 : xi;
+          if (out_prob) out_prob[r * k + j] = xi == kNoLabel ? 0.0f : expf(xs - mx) / sum;
+        }
+        ps = xs;
+        pi = xi;
+      }
+    }
+    __syncthreads();  // sc[]/row[] are reused by the next iteration
+  }
+}
+
+int launch_topk_rows(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
+                     float scale, int normalize, int k, int* out_index, float* out_prob, hipStream_t s) {
+  const size_t shmem = (size_t)kQWaves * (((D + 3) & ~3) + ((L + 3) & ~3)) * sizeof(float);
+  if (shmem > 150 * 1024) return fail(SAF_E_UNSUPPORTED, "query top-k: feat_dim + n_text too large (%zu B LDS)", shmem);
+  auto fn = ft == SAF_BF16 ? topk_rows_kernel<SAF_BF16> : ft == SAF_F16 ? topk_rows_kernel<SAF_F16> : topk_rows_kernel<SAF_F32>;
+  if (shmem > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
+  int64_t blocks = (n_rows + kQWaves - 1) / kQWaves;
+  const int64_t cap = (int64_t)device_cus() * 8;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kQThreads), shmem, s, feats, n_rows, fstride, D, text, L, tstride, scale,
+                     normalize, k, out_index, out_prob);
+  return check_launch("topk_rows_kernel");
+}
+
+// labels per launch of the matrix scans' top-k (0: the one-wave-per-row kernel)
+inline int topk_block(int ft, int64_t fstride, int D, const void* feats) {
+  return mfma_ok(ft, fstride, D, 64, feats) ? 64 : mfma_ok(ft, fstride, D, 32, feats) ? 32 : 0;
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 }  // namespace
 }  // namespace saf
 
@@ -1089,6 +1313,56 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
     default:
       return fail(SAF_E_INVALID, "query scan: unknown epilogue %d", epilogue);
   }
+}
+
+size_t saf_query_topk_workspace_bytes(int64_t n_rows, int32_t n_text, int32_t k) {
+  // the state carried between label blocks: only where there is more than one (blocks are 32 labels or more)
+  if (n_rows <= 0 || n_text <= 32 || k < 1 || k > kTopkMax) return 0;
+  return 2 * align256((size_t)n_rows * k * sizeof(float)) + 2 * align256((size_t)n_rows * sizeof(float));
+}
+
+int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride, int32_t feat_dim, const float* text,
+                   int32_t n_text, int64_t text_stride, float scale, int32_t normalize, int32_t k, int32_t* out_index,
+                   float* out_prob, void* workspace, size_t workspace_bytes, void* stream) {
+  if (feat_dtype != SAF_F32 && feat_dtype != SAF_BF16 && feat_dtype != SAF_F16)
+    return fail(SAF_E_INVALID, "query top-k: unknown feature dtype %d", feat_dtype);
+  if (!feats || !text || !out_index || n_rows < 0 || feat_dim <= 0 || n_text <= 0 || feat_stride < feat_dim ||
+      text_stride < feat_dim || normalize < SAF_NORM_NONE || normalize > SAF_NORM_L2_CLAMP)
+    return fail(SAF_E_INVALID, "query top-k: bad arguments");
+  if (k < 1 || k > kTopkMax || k > n_text) return fail(SAF_E_INVALID, "query top-k: k = %d (1 <= k <= min(8, n_text = %d))", k, n_text);
+  if (n_rows == 0) return SAF_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int bw = topk_block(feat_dtype, feat_stride, feat_dim, feats);
+  if (bw == 0)
+    return launch_topk_rows(feat_dtype, feats, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize, k,
+                            out_index, out_prob, s);
+  TopkArgs tk;
+  tk.k = k;
+  tk.out_index = out_index;
+  tk.out_prob = out_prob;
+  if (n_text > bw) {
+    const size_t need = saf_query_topk_workspace_bytes(n_rows, n_text, k);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
+      return fail(SAF_E_WORKSPACE, "query top-k: %d labels need %zu bytes of 256-byte aligned workspace", n_text, need);
+    char* w = static_cast<char*>(workspace);
+    tk.st_val = reinterpret_cast<float*>(w);
+    w += align256((size_t)n_rows * k * sizeof(float));
+    tk.st_idx = reinterpret_cast<int*>(w);
+    w += align256((size_t)n_rows * k * sizeof(float));
+    tk.st_max = reinterpret_cast<float*>(w);
+    w += align256((size_t)n_rows * sizeof(float));
+    tk.st_sum = reinterpret_cast<float*>(w);
+  }
+  for (int c0 = 0; c0 < n_text; c0 += bw) {
+    const int lb = n_text - c0 < bw ? n_text - c0 : bw;
+    tk.col0 = c0;
+    tk.first = c0 == 0;
+    tk.last = c0 + lb >= n_text;
+    const int rc = launch_mfma<EPI_TOPK>(feat_dtype, feats, n_rows, feat_stride, feat_dim, text + (int64_t)c0 * text_stride, lb,
+                                         text_stride, scale, normalize, nullptr, nullptr, nullptr, s, 0, 0, tk);
+    if (rc) return rc;
+  }
+  return SAF_OK;
 }
 
 }  // extern "C"

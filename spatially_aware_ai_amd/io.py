@@ -179,6 +179,80 @@ def save_ply(path, verts, faces, vertex_colors=None):
     return path
 
 
+_PLY_TYPES = {
+    "char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+    "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8",
+}
+
+
+def load_ply_vertices(path) -> np.ndarray:
+    """The ``x y z`` of a PLY file's ``vertex`` element as float32 [V, 3] -- what the eval reads of a mesh through
+    ``open3d.io.read_triangle_mesh(...).vertices`` (eval_scannet_segmentation.py:579-587).  Binary little- and big-endian
+    and ASCII files; other vertex properties (of any scalar type: ScanNet's ``_vh_clean_2.ply`` has uchar red green blue
+    alpha, ``save_ply`` the same) and other elements (faces) are skipped."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []  # elements: [name, count, [(property, type or None for a list, list types)]]
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                elements[-1][2].append((w[4], None, (w[2], w[3])))
+            else:
+                elements[-1][2].append((w[2], w[1], None))
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+    names = [e[0] for e in elements]
+    if "vertex" not in names:
+        raise ValueError(f"{path}: no vertex element")
+    vi = names.index("vertex")
+    _, n, props = elements[vi]
+    pnames = [p[0] for p in props]
+    if not all(c in pnames for c in "xyz"):
+        raise ValueError(f"{path}: the vertex element has no x y z")
+    if fmt == "ascii":
+        lines = data[body:].decode("ascii").splitlines()
+        lines = [l for l in lines if l.strip()]
+        first = sum(e[1] for e in elements[:vi])  # one line per item of the elements before
+        if any(p[1] is None for p in props):
+            rows = [l.split() for l in lines[first:first + n]]
+            cols = [pnames.index(c) for c in "xyz"]  # (a list before x y z would shift them: not supported below)
+            if any(p[1] is None for p in props[: max(cols) + 1]):
+                raise ValueError(f"{path}: list properties before x y z in the vertex element")
+            return np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float32).reshape(n, 3)
+        table = np.array(" ".join(lines[first:first + n]).split(), dtype=np.float64).reshape(n, len(props))
+        return np.ascontiguousarray(table[:, [pnames.index(c) for c in "xyz"]]).astype(np.float32)
+    end_ch = "<" if fmt == "binary_little_endian" else ">"
+    off = body
+    for e in elements[:vi]:  # skip the elements before the vertices
+        if all(p[1] is not None for p in e[2]):
+            off += e[1] * sum(int(_PLY_TYPES[p[1]][1]) for p in e[2])
+            continue
+        for _ in range(e[1]):
+            for p in e[2]:
+                if p[1] is not None:
+                    off += int(_PLY_TYPES[p[1]][1])
+                else:
+                    ct = np.dtype(end_ch + _PLY_TYPES[p[2][0]])
+                    cnt = int(np.frombuffer(data, ct, 1, off)[0])
+                    off += ct.itemsize + cnt * int(_PLY_TYPES[p[2][1]][1])
+    if any(p[1] is None for p in props):
+        raise ValueError(f"{path}: list properties in a binary vertex element")
+    dt = np.dtype([(p[0], end_ch + _PLY_TYPES[p[1]]) for p in props])
+    v = np.frombuffer(data, dt, n, off)
+    return np.stack([v["x"], v["y"], v["z"]], axis=-1).astype(np.float32)
+
+
 def save_scene_arrays(out_dir, fusion, vert_clip_feat=None, vertex_obj_idx=None):
     """The numpy artefacts of save_files_and_broadcast (clip_seem_fusion.py:566-581) straight from the device:
     voxel_rgb.npy [nx,ny,nz,3], voxel_clip_feats.npy [nx,ny,nz,D] (clip_seem_fusion.py:335-338 reshapes the flat buffers
