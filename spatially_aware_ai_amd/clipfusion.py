@@ -259,6 +259,12 @@ class _FusionVolumeMixin:
         one backbone batch (the reference feeds its ViT 35 tiles per call; a flush feeds it 128 x 35)."""
         bsz = int(depth_imgs.shape[0])
         f32 = torch.float32
+        if getattr(self, "_shard_stripes", None) is not None:
+            # refused HERE, not when the queue is flushed: a queued frame would make every later read of the volume raise
+            raise SafError(
+                "this volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
+                "(distributed.gather_shards, or merge_volumes(..., gather=True)) before fusing more frames"
+            )
         if clip_feat_img is None:
             fn, fshape = lazy_feat
             lazy_ok = self._defer_ok(bsz, fshape[1], fshape[2]) and all(
@@ -710,6 +716,7 @@ class _FusionVolumeMixin:
         super().__setattr__("accum_mode", accum_mode)
         self._shard_stripes = None
         self.__dict__["_shard_plans"] = None
+        self.__dict__["_shard16"] = None  # (distributed.shard_features_16's copy of the rows that were just discarded)
         self.__dict__["_feat_stale"] = lazy
 
 

@@ -193,8 +193,9 @@ def sparse_wish(sparse, device, group=None):
 class _Touched:
     """What one merge knows about the rows any rank touched (from the all-reduced weight of the rows the plan covers):
     ``offs[j][k]`` = position, among the touched rows in ascending order, of the first touched row of part k of piece j
-    (k = world: the end of the piece's world equal parts; a tail of fewer than world rows is reduced on its own), after ONE
-    host synchronisation.  Device tensors: a scan kernel and the boundaries' positions copied to pinned memory
+    (k = world: the end of the piece's world equal parts; a tail of fewer than world rows is reduced on its own; k = world + 1:
+    the end of the piece, tail included -- ``last_merge["touched_rows"]`` counts the tail's rows too), after ONE host
+    synchronisation.  Device tensors: a scan kernel and the boundaries' positions copied to pinned memory
     (``saf_merge_scan_touched``; no index list -- pack / add read the positions).  CPU tensors (the gloo tests): torch."""
 
     def __init__(self, weight_total, plan, world):
@@ -204,7 +205,7 @@ class _Touched:
         self.world = world
         bounds = []
         for first, rows, c in plan:
-            bounds += [first - self.first0 + k * c for k in range(world + 1)]
+            bounds += [first - self.first0 + k * c for k in range(world + 1)] + [first - self.first0 + rows]
         self.hip = self.w.is_cuda
         self._idx = None
         if self.hip:
@@ -225,7 +226,7 @@ class _Touched:
             cs = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(touched, 0, dtype=torch.int64)])
             pre = cs[torch.tensor(bounds, dtype=torch.int64)].tolist()
             self._touched = touched
-        self.offs = [pre[j * (world + 1) : (j + 1) * (world + 1)] for j in range(len(plan))]
+        self.offs = [pre[j * (world + 2) : (j + 1) * (world + 2)] for j in range(len(plan))]
 
     def idx(self):  # (CPU route only: the touched rows' indices, relative to first0)
         if self._idx is None:
@@ -307,7 +308,7 @@ def _merge_rows(tensors, plan, group, rank, world, wish):
                         dist.reduce(t[first + world * c : first + rows], dst=_global_rank(group, world - 1), op=dist.ReduceOp.SUM, group=group)
                 else:
                     _reduce_scatter_striped(t, [(first, rows, c)], group, rank, world)
-        last_merge.update(packed=packed, touched_rows=int(sum(o[world] - o[0] for o in touched.offs)))
+        last_merge.update(packed=packed, touched_rows=int(sum(o[world + 1] - o[0] for o in touched.offs)))
         return packed
     for t in rest.values():
         _reduce_scatter_striped(t, plan, group, rank, world)
@@ -541,6 +542,13 @@ def merge_slab_sums(tensors: dict, first_row: int, n_rows: int, group=None, mode
     return stripes_of_rank(plan, rank, world)
 
 
+def _rows_rewritten(fusion):
+    """A merge step (sums <-> means, a collective) is about to rewrite the volume's rows: 16-bit shard copies made before it
+    (``shard_features_16``) are stale."""
+    fusion.__dict__["_merge_epoch"] = fusion.__dict__.get("_merge_epoch", 0) + 1
+    fusion.__dict__["_shard16"] = None
+
+
 def _require_f32_sums(fusion, what):
     if fusion._buffers["clip_feat"].dtype != torch.float32:
         raise SafError(
@@ -571,6 +579,7 @@ def fuse_merge_pipelined(fusion, frame_arr, n_frames, workspace, n_slabs=8, grou
     if fusion.accum_mode != _abi.SAF_SUM:
         raise SafError("fuse_merge_pipelined fuses sums: set accum_mode = SAF_SUM (reset(accum_mode=SAF_SUM))")
     L = lib()
+    _rows_rewritten(fusion)
     dev = fusion._buffers["tsdf"].device
     main = torch.cuda.current_stream(dev)
     comm = comm_stream if comm_stream is not None else main
@@ -663,6 +672,7 @@ def finalize_sums(fusion, first: int = 0, count: int | None = None):
     the whole volume is covered the module returns to running-mean mode."""
     n = fusion.tsdf.numel()
     count = n - first if count is None else count
+    _rows_rewritten(fusion)
     vol = fusion._c_volume()
     with torch.cuda.device(fusion.tsdf.device):
         check(lib().saf_merge_finalize(C.byref(vol), first, count, current_stream_ptr()), "saf_merge_finalize")
@@ -672,6 +682,7 @@ def finalize_sums(fusion, first: int = 0, count: int | None = None):
 
 def means_to_sums(fusion):
     """Turn a running-mean volume into sums (x * w) so it can enter the reduction."""
+    _rows_rewritten(fusion)
     vol = fusion._c_volume()
     with torch.cuda.device(fusion.tsdf.device):
         check(lib().saf_mean_to_sum(C.byref(vol), 0, fusion.tsdf.numel(), current_stream_ptr()), "saf_mean_to_sum")
@@ -692,6 +703,7 @@ def merge_volumes(fusion, group=None, mode: str = "reduce_scatter", gather: bool
     if fusion.accum_mode != _abi.SAF_SUM:
         means_to_sums(fusion)
     tensors = _volume_tensors(fusion)
+    _rows_rewritten(fusion)
     n = fusion.tsdf.numel()
     plans = []
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -731,6 +743,7 @@ def gather_shards(fusion, group=None):
         return [(0, n)]
     world = dist.get_world_size(group)
     tensors = _volume_tensors(fusion)
+    _rows_rewritten(fusion)
     plans = getattr(fusion, "_shard_plans", None)
     if plans:
         rank = dist.get_rank(group)
@@ -757,8 +770,9 @@ def gather_shards(fusion, group=None):
 
 def shard_features_16(fusion, first, count, dtype=torch.float16):
     """The 16-bit copy of a volume's voxel shard that the wide scan reads (cached on the module until the volume
-    is fused into or reset again).  One pass over count * D * 4 bytes."""
-    key = (first, count, dtype, fusion.clip_feat.data_ptr(), int(fusion.fuse_stats[2]))
+    is fused into, merged or reset again: a merge changes every row but neither the shard range of a one-piece plan, nor the
+    address, nor the frame count -- ``_merge_epoch`` counts the merges).  One pass over count * D * 4 bytes."""
+    key = (first, count, dtype, fusion.clip_feat.data_ptr(), int(fusion.fuse_stats[2]), fusion.__dict__.get("_merge_epoch", 0))
     cached = fusion.__dict__.get("_shard16")
     if cached is not None and cached[0] == key:
         return cached[1]

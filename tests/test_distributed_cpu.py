@@ -407,3 +407,65 @@ def test_gather_shards_makes_a_striped_volume_whole(world, with_plan):
     out = mgr.dict()
     mp.spawn(_gather_shards_worker, args=(world, _free_port(), out, with_plan), nprocs=world, join=True)
     assert all(out.get(r) for r in range(world)), dict(out)
+
+
+# ---- the CPU companion of tests/test_distributed_gpu.py: the reference alone on the GPU test's workloads ------------------
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("name", ["W1", "W1B", "W1a", "W2", "W3"])
+def test_sharded_oracle_sums_stay_inside_the_bar_of_the_gpu_workloads(oracle, name, world):
+    """tests/dist_workloads.py at world 2 and 4 with NO device code: every rank's shard fused into an oracle SUM volume, the
+    shards added in rank order in numpy, divided, against the oracle's single-process running mean.  The reference alone must
+    stay inside the elementwise bar (clip_feat, rgb: rtol 1e-4, atol 1e-6; tsdf: atol 2e-6) that the GPU cases then apply -- so
+    a failure there is the HIP path's.  Measured worst |error| / (atol + rtol |want|) over W1, W1B, W1a, W2, W3 at both world
+    sizes: 0.17 (clip_feat, W1a at world 2), 0.008 (rgb, W1), 0.02 (tsdf, W1B) -- every workload keeps the elementwise bar; none of them
+    fuses more than 96 frames, so the row-magnitude bar of tests/test_sums_form.py is not needed.
+    Also the properties the GPU cases rely on: W1 / W3 voxel counts divide by neither the world size nor 64; W2 has pieces no
+    rank touched and a (piece, rank) part without touched rows beside a part with some; W3 leaves a rank without frames; the
+    two jobs of the two-jobs case touch voxel sets that differ in both directions."""
+    import dist_workloads as wl
+
+    s = wl.spec(name, world)
+    frames = wl.frames_of(s)
+    ref = wl.reference(oracle, s, frames)
+    n = ref["weight"].shape[0]
+    shards = []
+    for r in range(world):
+        mine = sdist.shard_frames(len(frames), r, world)
+        shards.append(wl.tensors_of(wl.oracle_fuse(wl.oracle_volume(oracle, s, _abi.SAF_SUM), [frames[i] for i in mine], s["seem"])))
+    total = {k: shards[0][k].copy() for k in shards[0]}
+    for sh in shards[1:]:
+        for k in total:
+            total[k] += sh[k]
+    for k in wl.INT_TENSORS:
+        if k in ref:
+            assert np.array_equal(total[k], ref[k]), k
+    w = np.maximum(total["weight"], 1).astype(np.float32)
+    tw = np.maximum(total["tsdf_weight"], 1).astype(np.float32)
+    worst = {"clip_feat": wl.elementwise_excess(total["clip_feat"] / w[:, None], ref["clip_feat"], "clip_feat"),
+             "rgb": wl.elementwise_excess(total["rgb"] / w[:, None], ref["rgb"], "rgb"),
+             "tsdf": wl.elementwise_excess(total["tsdf"] / tw, ref["tsdf"], "tsdf")}
+    print(f"{name} world {world}: worst error over the elementwise bar {worst}, touched {int((ref['weight'] > 0).sum())} of {n}, "
+          f"largest weight {int(ref['weight'].max())}")
+    assert max(worst.values()) <= 1.0, worst
+    assert int((ref["weight"] > 0).sum()) > 100
+    if name in ("W1", "W1B", "W3"):
+        assert n % world != 0 and n % 64 != 0
+        assert len(wl.plan_of(s, world)) >= 3
+    if name != "W3":
+        assert min(len(sdist.shard_frames(len(frames), r, world)) for r in range(world)) >= (16 if s["dim"] == 512 else 1)
+    else:
+        assert len(sdist.shard_frames(len(frames), world - 1, world)) == 0 and len(frames) >= 1
+    if name == "W2":
+        plan = wl.plan_of(s, world)
+        touched = ref["weight"] > 0
+        assert len(plan) >= 3 and plan[-1][1] < plan[0][1] and 0 < plan[-1][1] - world * plan[-1][2] < world
+        counts = np.array([[int(touched[f + k * c:f + (k + 1) * c].sum()) for k in range(world)] for f, _, c in plan])
+        assert (counts.sum(1) == 0).any(), "W2 needs a piece no rank touched"
+        assert ((counts == 0).any(1) & (counts > 0).any(1)).any(), "W2 needs a part without touched rows beside one with some"
+        frac = counts.sum(1) / np.array([world * c for _, _, c in plan])
+        assert (frac > 0.3).any() and (frac <= 0.3).any(), "sparse = 0.3 must pack some pieces and not others"
+        assert 0 < touched.sum() < 0.5 * n
+    if name == "W1B":
+        a = wl.reference(oracle, wl.spec("W1", world), wl.frames_of(wl.spec("W1", world)))["weight"] > 0
+        b = ref["weight"] > 0
+        assert int((a & ~b).sum()) > 100 and int((b & ~a).sum()) > 100, "job A and job B must each touch voxels the other does not"
