@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SAF_ABI_VERSION 4
+#define SAF_ABI_VERSION 5
 
 enum saf_status {
   SAF_OK = 0,
@@ -487,6 +487,45 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
 int saf_clip_tiles(const float* rgb, int32_t batch, int32_t height, int32_t width, int64_t stride_b, int64_t stride_c,
                    int64_t stride_y, int64_t stride_x, int32_t patch, int32_t stride, int32_t out_size,
                    const float* mean3, const float* std3, void* out, int32_t out_dtype, void* stream);
+
+/*
+ * Ray cast of the fused volume from a camera pose (ABI 5; new capability, nothing to mirror in the reference: its AR client --
+ * app_unity.py, magicleap2_camera_match.py -- asks what a headset camera sees of the volume).  One ray per pixel (u, v),
+ * u = 0 .. width - 1, v = 0 .. height - 1; fp32 throughout, one IEEE operation at a time in the order written here
+ * (tests/raycast_reference.py restates it in NumPy):
+ *   grid     voxel centre i of an axis lies at axis[i]; origin = (axis_x[0], axis_y[0], axis_z[0]),
+ *            voxel_size = (axis_x[nx - 1] - axis_x[0]) / (nx - 1).  Grid coordinates g = (p - origin) / voxel_size: centre i at g = i.
+ *   ray      d_cam = ((u - K[0][2]) / K[0][0], (v - K[1][2]) / K[1][1], 1); d = R d_cam per row as (r0 dcx + r1 dcy) + r2;
+ *            o = pose[:3, 3]; p(t) = o + t d, so t is camera z -- the convention of saf_frame.depth.  In grid coordinates
+ *            g(t) = og + t gd with og = (o - origin) / voxel_size and gd = d / voxel_size, per axis.
+ *            pose [4,4] camera->world and K [3,3] are DEVICE pointers as in saf_frame (no host synchronisation).  K must have no
+ *            skew and a third row of (0, 0, 1); the call cannot read device memory, so it is the kernel that refuses any other K:
+ *            every pixel is then a miss.
+ *   range    t in [z_near, z_far] clipped by the slab method to 0 <= g <= n - 1 per axis (t1 = (0 - og) / gd, t2 = (n - 1 - og) / gd;
+ *            an axis with gd = 0 keeps the range iff 0 <= og <= n - 1).  An empty range is a miss.
+ *   samples  t_k = t_enter + k s, k = 0, 1, ... while t_k <= t_exit (at most 65536), s = (step_vox voxel_size) / max(|dx|, |dy|, |dz|).
+ *   value    f_k = trilinear interpolation of tsdf at g(t_k): cell i = floor(g) clamped to [0, n - 2], offset g - i, per axis;
+ *            a + f (b - a) along z, then y, then x.  The sample is OBSERVED iff all 8 corners have tsdf_weight > 0.
+ *   hit      the first k with samples k and k + 1 both observed, f_k > 0 and f_{k+1} <= 0 (front faces only);
+ *            t* = t_k + s (f_k / (f_k - f_{k+1})).
+ *   out_depth [H,W] f32   t*, 0 for a miss (missing depth is 0, as in saf_frame.depth)
+ *   out_voxel [H,W] i32   flat index (x ny + y) nz + z of the voxel nearest to g(t*) (round half to even per axis, clamped to the
+ *                         grid), -1 for a miss
+ *   out_rgb   [H,W,3] f32 (may be NULL) vol->rgb of that voxel; 0 for a miss or where the voxel's `weight` is 0
+ * The volume needs at least 2 voxels per axis and fewer than 2^31 in all.  SAF_E_INVALID (on the host, nothing is launched) for a
+ * NULL vol / pose / K / out_depth / out_voxel, non-positive sizes, step_vox <= 0 or z_far <= z_near.
+ * One wave casts an 8 x 8-pixel tile; the corner taps are read as pairs along z (8-byte requests).
+ */
+int saf_raycast(const saf_volume* vol, const float* pose, const float* K, int32_t height, int32_t width, float step_vox,
+                float z_near, float z_far, float* out_depth, int32_t* out_voxel, float* out_rgb, void* stream);
+
+/*
+ * dst[p, :] = src[index[p], :] for p = 0 .. n_index - 1, rows of zeros where index[p] < 0 (or >= n_src_rows): the rows of the
+ * voxels a ray cast hit, for saf_query_scan (ABI 5).  Bytes are copied, whatever the dtype: row_bytes must be a multiple of 16
+ * and src / dst 16-byte aligned (SAF_E_INVALID otherwise, as for NULL pointers and non-positive sizes; nothing is launched).
+ */
+int saf_gather_rows(const void* src, int64_t n_src_rows, int64_t row_bytes, const int32_t* index, int64_t n_index, void* dst,
+                    void* stream);
 
 /*
  * Marching cubes on the TSDF, on the device: the mesh half of extract_mesh (clipfusion.py:723-739,

@@ -79,6 +79,17 @@ class ClipSeemFusion(_FusionVolumeMixin, torch.nn.Module):
         colors, feats, obj, seg = self.sample_mesh_vertices(verts, self.voxel_obj_idx, self.objects_segmentation_color)
         return self._verts_world(verts), faces, colors, feats, obj, seg
 
+    def render(self, pose, K, height, width, **kw):
+        """``_FusionVolumeMixin.render`` plus ``label`` [H,W] i32: the panoptic class of the voxel each pixel sees --
+        ``label_index()`` at ``voxel`` -- or -1 for a miss."""
+        out = super().render(pose, K, height, width, **kw)
+        # the histogram rows of the hit voxels only (143 counters: not a multiple of 16 bytes, so torch moves them), decoded by
+        # the kernel behind label_index()
+        rows = self.labels_one_hot.index_select(0, out.voxel.reshape(-1).clamp_min(0).long())
+        lab = argmax_with_check(rows).to(torch.int32).view_as(out.voxel)
+        out.label = torch.where(out.hit, lab, torch.full_like(lab, -1))
+        return out
+
     def label_index(self):
         """Per-voxel class id, -1 where nothing was fused: the manager's
         ``argmax_with_check_2d_efficient(labels_one_hot)`` (clip_seem_fusion.py:315-325)."""

@@ -16,7 +16,9 @@ fallback: tensors that are not on the HIP device raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -796,6 +798,92 @@ class _FusionVolumeMixin:
         verts, faces = self._marching_cubes_vertices(marching_cubes)
         colors, feats = self.sample_mesh_vertices(verts)[:2]
         return self._verts_world(verts), faces, colors, feats
+
+    # -- viewing the volume from a pose (not in the reference: its AR client needs it, app_unity.py) --------------
+    def render(self, pose, K, height, width, step_vox=0.5, z_near=0.0, z_far=None, rgb=True):
+        """What a camera at ``pose`` (cam->world [4,4]) with intrinsics ``K`` [3,3] sees of the volume (saf_raycast, include/saf.h):
+        a ``RenderResult`` of device tensors -- ``depth`` [H,W] f32 (camera z of the first front-face zero crossing of the TSDF,
+        0 = miss), ``voxel`` [H,W] i32 (flat index of the voxel nearest to the hit, -1 = miss), ``rgb`` [H,W,3] f32 (that voxel's
+        colour; None with ``rgb=False``) and ``hit`` (``voxel >= 0``).  ``step_vox``: sample spacing in voxels along the ray's
+        dominant axis; ``z_far=None``: the grid's diagonal.  Frames still queued behind ``integrate()`` are fused first.
+
+        Two things a caller should know.  A ``K`` with skew or a third row other than (0, 0, 1) is not supported: ``K`` lives on
+        the device and is not read back, so no error is raised -- every pixel comes back as a miss.  And the answer is that of
+        the fused FIELD: a camera outside the scanned room looks at the back of the walls' truncation bands, whose outer edge
+        (carved to free space by oblique frames, left negative by head-on ones) can read as a surface -- tens of pixels of a
+        view may report a depth just outside a wall.  A camera inside the scanned space never sees a band from behind."""
+        pose = self._f32c(torch.as_tensor(pose), "pose")
+        K = self._f32c(torch.as_tensor(K), "K")
+        if tuple(pose.shape) != (4, 4) or tuple(K.shape) != (3, 3):
+            raise ValueError("pose must be [4,4] and K [3,3]")
+        if getattr(self, "_shard_stripes", None) is not None or self.x_planes is not None:
+            raise SafError("render() needs the whole grid: this module holds a slab / the stripes of a voxel-sharded volume")
+        vol = self._c_volume()  # (joins the queue: the volume holds every frame handed to integrate())
+        dev = self._buffers["tsdf"].device
+        height, width = int(height), int(width)
+        if z_far is None:
+            z_far = _grid_diagonal(self.voxel_size, self.nvox)
+        shape = (max(height, 0), max(width, 0))
+        depth = torch.empty(shape, dtype=torch.float32, device=dev)
+        voxel = torch.empty(shape, dtype=torch.int32, device=dev)
+        color = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if rgb else None
+        p = _abi.ptr
+        with torch.cuda.device(dev):
+            rc = lib().saf_raycast(C.byref(vol), p(pose.to(dev)), p(K.to(dev)), height, width, float(step_vox), float(z_near),
+                                   float(z_far), p(depth), p(voxel), p(color), current_stream_ptr())
+        check(rc, "saf_raycast")
+        return RenderResult(depth=depth, voxel=voxel, rgb=color, hit=voxel >= 0)
+
+    def render_query(self, text_features, pose, K, height, width, epilogue="softmax", scale=100.0, normalize=True, **render_kw):
+        """``render`` plus ``relevance`` [H,W,L] f32: the text query of ``Clip.run_query`` (epilogue "softmax", or the raw
+        "scores") over the feature rows of the voxels the pixels see -- saf_gather_rows on ``clip_feat``, then the scan every
+        other query uses (fp32 and bf16 volumes).  Miss pixels get 0 in every column.  (Feature surgery weighs the labels over
+        the whole row set: not offered per view.)"""
+        epi = {"scores": _abi.SAF_Q_SCORES, "softmax": _abi.SAF_Q_SOFTMAX}.get(epilogue)
+        if epi is None:
+            raise ValueError(f"render_query takes the epilogues 'scores' and 'softmax', not {epilogue!r}")
+        out = self.render(pose, K, height, width, **render_kw)
+        rows = gather_rows(self.clip_feat, out.voxel.reshape(-1))
+        text_features = torch.as_tensor(text_features)
+        rel = _query_scan(rows, text_features, epi, scale=scale, normalize=normalize)
+        rel = rel.masked_fill_(~out.hit.reshape(-1, 1), 0.0)
+        out.relevance = rel.view(out.voxel.shape[0], out.voxel.shape[1], -1)
+        return out
+
+
+def _grid_diagonal(voxel_size, nvox):
+    return float(voxel_size) * math.sqrt(sum(float(n) ** 2 for n in nvox))
+
+
+@dataclass
+class RenderResult:
+    """What ``render`` / ``render_query`` return: per-pixel device tensors ([H,W,...]); fields a call does not produce are None."""
+
+    depth: torch.Tensor
+    voxel: torch.Tensor
+    rgb: torch.Tensor | None
+    hit: torch.Tensor
+    label: torch.Tensor | None = None      # ClipSeemFusion.render: panoptic class of the voxel, -1 = miss
+    relevance: torch.Tensor | None = None  # render_query: [H,W,L]
+
+
+def gather_rows(src, index):
+    """``out[p] = src[index[p]]``, rows of zeros where ``index[p] < 0`` (saf_gather_rows): ``src`` [N, ...] contiguous on the HIP
+    device with rows of a multiple of 16 bytes, ``index`` [P] int32."""
+    require_cuda(src, "the rows to gather")
+    require_cuda(index, "the row index")
+    if not src.is_contiguous():
+        raise SafError("gather_rows needs contiguous rows")
+    idx = index.to(device=src.device, dtype=torch.int32).contiguous().reshape(-1)
+    n = int(src.shape[0])
+    row_bytes = (src.numel() // max(n, 1)) * src.element_size()
+    out = torch.empty((idx.numel(),) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if idx.numel() == 0:
+        return out
+    with torch.cuda.device(src.device):
+        rc = lib().saf_gather_rows(src.data_ptr(), n, row_bytes, idx.data_ptr(), idx.numel(), out.data_ptr(), current_stream_ptr())
+    check(rc, "saf_gather_rows")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

@@ -57,6 +57,23 @@ class SceneResult:
         self.seconds["text_query"] = self.seconds.get("text_query", 0.0) + time.perf_counter() - t0
         return out
 
+    def render_query(self, clip_model, text, pose, K, height, width):
+        """The text query seen from a camera (what the reference's AR client overlays on its view, app_unity.py): an RGBA image
+        [H,W,4] (numpy f32) -- ``text`` against the scene's object classes as in ``text_query``, softmax relevance of ``text``
+        (the last column) per pixel through ``relevance_to_rgba``; alpha 0 where the pixel sees nothing of the volume."""
+        from .clip_seem_fusion import relevance_to_rgba
+
+        t0 = time.perf_counter()
+        uo = self.scene_knowledge.get("unique_objects", {})
+        names = sorted(set(uo[k]["class_label"] for k in uo) - {text}) + [text]
+        feats = clip_model.encode_text_with_prompt_ensemble(names, "cpu", prompt_templates=["a photo of {}"])
+        out = self.fusion.render_query(feats, pose, K, height, width, epilogue="softmax", rgb=False)
+        rel = out.relevance[..., -1].reshape(-1).cpu().numpy()
+        rgba = relevance_to_rgba(rel).astype(np.float32).reshape(int(height), int(width), 4)
+        rgba[~out.hit.cpu().numpy()] = 0.0
+        self.seconds["render_query"] = self.seconds.get("render_query", 0.0) + time.perf_counter() - t0
+        return rgba
+
 
 class FrameStager:
     """Host -> device staging of the loader's frames through a few reusable pinned buffers.
