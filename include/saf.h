@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SAF_ABI_VERSION 5
+#define SAF_ABI_VERSION 6
 
 enum saf_status {
   SAF_OK = 0,
@@ -526,6 +526,41 @@ int saf_raycast(const saf_volume* vol, const float* pose, const float* K, int32_
  */
 int saf_gather_rows(const void* src, int64_t n_src_rows, int64_t row_bytes, const int32_t* index, int64_t n_index, void* dst,
                     void* stream);
+
+/*
+ * Per-object descriptors of a segmented volume (ABI 6; flood_fill_3d hands each object's {"clip_feats", "rgb", "voxels"} to the
+ * in-situ classifier, handy_utils.py:400-404, and app_unity.py's /merge_objects, /rename_object and /memorize_objects work on
+ * objects as wholes: this is the reduction of a voxel labelling to one row per object, on the device).
+ *   slot       [N] i32: voxel n (flat index (x ny + y) nz + z) is a member of object k = slot[n] iff 0 <= k < n_objects; any other
+ *              value means no object
+ *   count      [K] i64 members of object k (K = n_objects);  bbox [K,6] i32 (xmin, ymin, zmin, xmax, ymax, zmax) and
+ *              coord_sum [K,3] i64 over all members, in voxel indices.  An object without a member gets count 0, the box
+ *              (nx, ny, nz, -1, -1, -1) and zeros elsewhere
+ *   n_fused    [K] i64 and weight_sum [K] i64: the FUSED members (vol->weight > 0) and the sum of their weights
+ *   rgb_mean   [K,3] f32 mean over the fused members of vol->rgb clamped to [0, 1] (the clamp of saf_sample_vertices)
+ *   feat_mean  [K,D] f32 mean over the fused members of the normalised feature row (volume dtype f32 or bf16, any feat_dim >= 1;
+ *              rows on 16-byte boundaries are read 16 bytes per lane, others element by element); 0 where n_fused is 0
+ *   normalize  SAF_NORM_L2 (f / |f|, NaN -> 0: a zero row contributes zeros and still counts in n_fused) or SAF_NORM_L2_CLAMP
+ *              (f / max(|f|, 0.1)).  SAF_NORM_NONE returns SAF_E_UNSUPPORTED: raw rows have no bounded range, and the sums below
+ *              are exact only for bounded terms
+ *   workspace  saf_object_stats_workspace_bytes(n_voxels, n_objects, feat_dim) bytes, 256-byte aligned (0 for a bad size)
+ * rgb_mean, feat_mean, weight_sum, n_fused and coord_sum may each be NULL; with feat_mean == NULL no feature row is read.  Every
+ * output is written in full: the caller zeroes nothing.
+ * Determinism: integer outputs are exact, and two calls on the same inputs return the same bytes in every output whatever the grid
+ * or the scheduling.  The means are sums of rint(v 2^30) over terms v in [-1, 1] (a normalised element, a clamped colour; NaN
+ * counts as 0, anything outside the range as its nearer end) held as 64-bit integers -- integer adds commute, and 2^31 members
+ * times 2^30 stay below 2^63 --, finished as (double)S / (2^30 n_fused) and rounded once to f32.  The norm is the fp32 sum of
+ * squares in a fixed order, sqrtf, and one IEEE division per element.
+ * SAF_E_INVALID (on the host, nothing is launched) for a NULL vol / slot / count / bbox, n_objects < 1, a grid of 2^31 voxels or
+ * more, a workspace that is too small or misaligned.
+ * A wave walks fixed chunks of 512 voxels in raster order (objects are runs along z), accumulates consecutive members of one
+ * object in registers and flushes them with 64-bit integer atomics when the slot changes or the chunk ends; `slot` and `weight`
+ * are read once per voxel, feature rows only for fused members: 8 N + M (D s + 16) bytes for M fused members of s-byte elements.
+ */
+size_t saf_object_stats_workspace_bytes(int64_t n_voxels, int32_t n_objects, int32_t feat_dim);
+int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objects, int32_t normalize, int64_t* count,
+                     int64_t* n_fused, int64_t* weight_sum, int32_t* bbox /*[K,6]*/, int64_t* coord_sum /*[K,3]*/,
+                     float* rgb_mean /*[K,3]*/, float* feat_mean /*[K,D]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Marching cubes on the TSDF, on the device: the mesh half of extract_mesh (clipfusion.py:723-739,

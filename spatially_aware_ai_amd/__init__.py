@@ -18,6 +18,12 @@ __all__ = [
     "label_components",
     "discover_objects",
     "evaluation",
+    "objects",
+    "describe_objects",
+    "ObjectDescriptors",
+    "object_slots",
+    "merge_objects",
+    "mark_object_of_interest",
 ]
 
 
@@ -30,8 +36,12 @@ def __getattr__(name):
         from . import clip_seem_fusion as _m
 
         return getattr(_m, name)
-    if name == "evaluation":
+    if name in ("evaluation", "objects"):
         import importlib
 
-        return importlib.import_module(".evaluation", __name__)
+        return importlib.import_module("." + name, __name__)
+    if name in ("describe_objects", "object_slots", "merge_objects", "mark_object_of_interest", "ObjectDescriptors"):
+        from . import objects as _m
+
+        return getattr(_m, name)
     raise AttributeError(name)

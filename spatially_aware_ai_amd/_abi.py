@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 SAF_OK = 0
 SAF_E_INVALID = -1
@@ -183,6 +183,11 @@ PROTOTYPES = {
         [C.POINTER(SafVolume), _fp, _fp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, _fp],
     ),
     "saf_gather_rows": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, _fp]),
+    "saf_object_stats_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "saf_object_stats": (
+        C.c_int,
+        [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp],
+    ),
     "saf_label_components_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "saf_label_components": (
         C.c_int,

@@ -45,6 +45,7 @@ class SceneResult:
     paths: dict = field(default_factory=dict)
     seconds: dict = field(default_factory=dict)
     engine: TextQueryEngine | None = None
+    objects: object | None = None  # objects.ObjectDescriptors, computed by the first object_query
 
     def text_query(self, clip_model, text):
         """``clip_text_query`` (clip_seem_fusion.py:482-561): RGBA heat map over the scene mesh, or None."""
@@ -73,6 +74,26 @@ class SceneResult:
         rgba[~out.hit.cpu().numpy()] = 0.0
         self.seconds["render_query"] = self.seconds.get("render_query", 0.0) + time.perf_counter() - t0
         return rgba
+
+    def object_query(self, clip_model, text):
+        """The text query answered per OBJECT (objects.ObjectQueryResult): ``text`` against the scene's object classes, labels
+        chosen exactly as ``render_query`` chooses them; ``best(n)`` names the most relevant objects with their centroid and
+        box.  The descriptors (one reduction over the volume, ``objects.describe_objects``) are computed by the first call.
+        They are kept in ``self.objects`` and NOT recomputed when the scene knowledge changes: after ``merge_objects(...,
+        voxel_obj_idx=...)`` or a change of an object's ``removed`` flag assign ``self.objects = self.objects.merged(...)`` or
+        set ``self.objects = None`` (the next call describes the objects again)."""
+        from .objects import describe_objects
+
+        t0 = time.perf_counter()
+        if self.objects is None:
+            self.objects = describe_objects(self.fusion, self.voxel_obj_idx, self.scene_knowledge)
+        uo = self.scene_knowledge.get("unique_objects", {})
+        names = sorted(set(uo[k]["class_label"] for k in uo) - {text}) + [text]
+        feats = clip_model.encode_text_with_prompt_ensemble(names, "cpu", prompt_templates=["a photo of {}"])
+        out = self.objects.query(feats, epilogue="softmax")
+        torch.cuda.synchronize()
+        self.seconds["object_query"] = self.seconds.get("object_query", 0.0) + time.perf_counter() - t0
+        return out
 
 
 class FrameStager:
