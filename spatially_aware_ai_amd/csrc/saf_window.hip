@@ -1647,7 +1647,6 @@ WinFn pick_win(bool sum, bool bf16, bool of, size_t* lds) {
   return of ? pick_win<CPL, true>(sum, bf16) : pick_win<CPL, false>(sum, bf16);
 }
 
-// Shapes the windowed path takes; everything else runs the per-frame pipeline.
 }  // namespace
 
 size_t window_workspace_bytes(int64_t n_vox, int D, int P, bool bricks, int H, int W, bool labels) {
@@ -1669,30 +1668,276 @@ int window_frames() {
   return e && atoi(e) == 64 ? 64 : kWin;
 }
 
-bool window_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
+namespace {
+// What a call and a session derive alike from one (volume, frame shape, workspace): the workspace layout, the row kernel, the
+// depth-tile geometry and the knobs that are read per call.  Both drivers launch through it (win_view, launch_*, win_geom).
+struct WinPlan {
+  WinLayout wl;
+  int H, W, npy, npx, rgb_bilinear;  // the frames' shape
+  int P, img_vecs, prep_blocks, split;
+  int ts_log2, tiles_x, n_tiles;  // depth tiles of the classification's occlusion cull
+  int wlen;                       // frames per window
+  int wgs_env;                    // SAF_WIN_WGS (0: unset)
+  bool tiled, tiled_first, sum, of, maps16, rgbl_on, brick_form, xcd, verify;
+  size_t dpx, img_bytes16, win_lds, aux_bytes;
+  WinFn fn;  // the row kernel (nullptr: the brick form)
+};
+int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, WinPlan* pl) {
+  pl->H = kf0.H; pl->W = kf0.W; pl->npy = kf0.npy; pl->npx = kf0.npx; pl->rgb_bilinear = kf0.rgb_bilinear;
+  const int P = pl->P = kf0.npy * kf0.npx;
+  // Two layouts of the workspace: with room for the window's depth images re-laid-out in tiles (a workspace sized by
+  // saf_fuse_workspace_bytes_for_frames) or without (the classification then reads the frames' own row-major images).
+  // SAF_CLS_TILED=0 (read per call): never tiled; 2: the first unit of a call reads the tiled copies too (tests: a single-window call).
+  const size_t dpx = pl->dpx = depth_px_padded(kf0.H, kf0.W);
+  // (a volume that counts labels: the frames-sized layout also holds one window of packed {r, g, b, label} images)
+  const size_t rpx = kv.labels ? rgbl_px_padded(kf0.H, kf0.W) : 0;
+  const WinLayout wl_lin = win_layout(kv.N, kv.D, P), wl_til = win_layout(kv.N, kv.D, P, false, dpx, rpx);
+  const char* til_env = getenv("SAF_CLS_TILED");
+  pl->tiled = !(til_env && til_env[0] == '0') && dpx * sizeof(float) < (size_t)1 << 31 && workspace_bytes >= wl_til.cmax_off;
+  pl->tiled_first = til_env && til_env[0] == '2';
+  if (pl->tiled && brick_form_ok(kv)) {  // the brick form's pools follow the tile region: both must fit, or neither moves
+    const size_t a_lin = workspace_bytes > wl_lin.cmax_off ? workspace_bytes - wl_lin.cmax_off : 0;
+    const size_t a_til = workspace_bytes - wl_til.cmax_off;
+    if (a_lin > 0 && brick_aux_fits(kv, a_lin) && !(a_til > 0 && brick_aux_fits(kv, a_til))) pl->tiled = false;
+  }
+  const WinLayout& wl = pl->wl = pl->tiled ? wl_til : wl_lin;
+  if (workspace_bytes < wl.cmax_off) return fail(SAF_E_WORKSPACE, "windowed path: workspace too small");
+  pl->sum = kv.accum == SAF_SUM;
+  pl->img_vecs = (int)(wl.img_bytes / sizeof(float4));
+  pl->prep_blocks = (kv.D * (P + 1) + 255) / 256;
+  pl->aux_bytes = workspace_bytes - wl.cmax_off;
+  pl->brick_form = brick_form_ok(kv) && pl->aux_bytes > 0 && brick_aux_fits(kv, pl->aux_bytes);
+  pl->split = pl->brick_form && brick_split() ? 1 : 0;
+  // ClipSeemFusion's image side from packed images (SAF_WIN_RGBL=0, read per call: from the frames' own images -- the A/B)
+  pl->rgbl_on = !pl->brick_form && wl.cmax_off > wl.rgbl_off && kf0.rgb_bilinear && kf0.label_map &&
+                !(getenv("SAF_WIN_RGBL") && getenv("SAF_WIN_RGBL")[0] == '0');
+  // SAF_WIN_MAPS16=0 (read per call): a bf16 volume keeps fp32 map images -- it takes the frame-ordered kernel, bit-identical
+  // to the per-frame bf16 pipeline -- instead of the order-free form's bf16 images (one rounding of every tap to the volume's
+  // precision, exact when the backbone emitted bf16: BASELINE config 3).  fp32 volumes are not affected.
+  const char* m16 = getenv("SAF_WIN_MAPS16");
+  pl->of = window_form_sums() && !(kv.bf16 != 0 && m16 && m16[0] == '0');
+  pl->fn = nullptr;
+  pl->win_lds = 0;
+  if (!pl->brick_form) {
+    switch (kv.D / 256) {
+      case 1: pl->fn = pick_win<1>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
+      case 2: pl->fn = pick_win<2>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
+      case 3: pl->fn = pick_win<3>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
+      default: pl->fn = pick_win<4>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
+    }
+    if (!pl->fn) return fail(SAF_E_UNSUPPORTED, "windowed path: no row kernel for this width");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)pl->win_lds);
+    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
+  }
+  // bf16 volume in the order-free form: the window's map images are kept in bf16 (what the kernel's BF16 && OF instantiations read)
+  pl->maps16 = !pl->brick_form && pl->of && kv.bf16 != 0 && SAF_WIN_MAPS16_BUILD;
+  pl->img_bytes16 = ((size_t)kv.D * (P + 1) * 2 + 255) & ~(size_t)255;
+  if (pl->maps16) pl->img_vecs = (int)(pl->img_bytes16 / sizeof(float4));
+  // the depth tiles of the classification's occlusion cull: 16 x 16 pixels, doubled until a frame has at most kMaxDepthTiles
+  int ts_log2 = 4;
+  while (((kf0.W + (1 << ts_log2) - 1) >> ts_log2) * ((kf0.H + (1 << ts_log2) - 1) >> ts_log2) > kMaxDepthTiles) ++ts_log2;
+  pl->ts_log2 = ts_log2;
+  pl->tiles_x = (kf0.W + (1 << ts_log2) - 1) >> ts_log2;
+  pl->n_tiles = pl->tiles_x * ((kf0.H + (1 << ts_log2) - 1) >> ts_log2);
+  pl->wlen = window_frames();
+  pl->wgs_env = getenv("SAF_WIN_WGS") ? atoi(getenv("SAF_WIN_WGS")) : 0;
+  pl->xcd = !(getenv("SAF_WIN_XCD") && getenv("SAF_WIN_XCD")[0] == '0');
+  // SAF_CLS_VERIFY=1 (read per call): the self-checking classification -- every voxel slot computes the reference's pixel chain
+  // as well and counts disagreements with the guarded path in stats[7] (tests; tools/cls_guard_verify.py)
+  pl->verify = getenv("SAF_CLS_VERIFY") && getenv("SAF_CLS_VERIFY")[0] == '1';
+  return SAF_OK;
+}
+
+// Where things lie in the workspace.  Header (unit counters, the classification launches' counter shards, the frame table) and
+// mask planes are double-buffered by unit parity; the depth tiles of a window lie in one of kTileWindows slots.
+struct WinView {
+  int par;
+  unsigned char* hdr;  // starts with the row kernel's piece counter
+  unsigned long long* cls_acc;
+  WinTable* tab;
+  uint32_t* masks;
+  float* maps;          // the window's map images (fp32, or bf16: WinPlan::maps16)
+  const float4* rgbl;   // the window's packed {r, g, b, label} images, or nullptr (WinPlan::rgbl_on)
+  unsigned char* aux;   // the brick form's channel maxima, camera table and segment pools
+};
+WinView win_view(unsigned char* ws, const WinPlan& pl, int par) {
+  static_assert(kClsAccOff + kClsShards * 2 * sizeof(unsigned long long) <= kTableOff && kClsAccOff >= 256,
+                "workspace header layout");
+  WinView v;
+  v.par = par;
+  v.hdr = ws + (size_t)par * kHdrBytes;
+  v.cls_acc = reinterpret_cast<unsigned long long*>(v.hdr + kClsAccOff);
+  v.tab = reinterpret_cast<WinTable*>(v.hdr + kTableOff);
+  v.maps = reinterpret_cast<float*>(ws + kHdrTotal);
+  v.masks = reinterpret_cast<uint32_t*>(ws + kHdrTotal + pl.wl.maps_bytes + (size_t)par * pl.wl.mask_bytes);
+  v.rgbl = pl.rgbl_on ? reinterpret_cast<const float4*>(ws + pl.wl.rgbl_off) : nullptr;
+  v.aux = ws + pl.wl.cmax_off;
+  return v;
+}
+struct TileView {
+  float* dmax_w;    // [kWin] largest, [kWin] smallest tile maximum of the window's frames
+  float* tmax_w;    // [kWin][kMaxDepthTiles]
+  float* tdepth_w;  // (tiled layout only) the window's depth images in tiles
+};
+TileView tile_view(unsigned char* ws, const WinPlan& pl, int tslot) {
+  TileView t;
+  t.dmax_w = reinterpret_cast<float*>(ws + pl.wl.tile_off + (size_t)tslot * pl.wl.tile_win);
+  t.tmax_w = t.dmax_w + 1024;
+  t.tdepth_w = t.tmax_w + (size_t)kWin * kMaxDepthTiles;
+  return t;
+}
+
+// The one rule for the launch sizes of a unit (a volume or a slab of it).
+struct WinGeom {
+  uint32_t cls_wgs, grid;  // workgroups of a classification launch (4 bricks each), of the row kernel
+  int xcd_order;
+};
+WinGeom win_geom(const WinPlan& pl, const KVol& u) {
+  WinGeom g;
+  const uint32_t n_pieces = (uint32_t)(((int64_t)u.N + kPiece - 1) / kPiece);
+  const uint32_t row_wgs = (n_pieces + kWinWaves - 1) / kWinWaves;
+  // (the frame-ordered form keeps its rows in LDS: with 512-hit chunks 115 KB per workgroup at D = 512 -- ONE fits a CU, and a grid
+  //  of two per CU would leave half of the persistent workgroups waiting for the others to finish)
+  const int fit = pl.win_lds > 0 ? (int)((160 * 1024) / pl.win_lds) : 2;
+  g.grid = (uint32_t)device_cus() * (pl.wgs_env > 0 ? pl.wgs_env : (pl.of ? SAF_WIN_OF_WPE : (fit < 1 ? 1 : (fit > 2 ? 2 : fit))));
+  if (g.grid > row_wgs) g.grid = row_wgs;
+  // the classification's bricks: the brick grid padded to whole 8 x 8 tiles of brick columns
+  const uint32_t tx = ((uint32_t)u.nx + 8 * kBrickX - 1) / (8 * kBrickX), ty = ((uint32_t)u.ny + 8 * kBrickY - 1) / (8 * kBrickY);
+  const uint32_t nbz = ((uint32_t)u.nz + kBrickZ - 1) / kBrickZ;
+  g.cls_wgs = (tx * ty * 64u * nbz + 3u) / 4u;
+  // units of the row kernel in XCD-compact order (see the kernel); SAF_WIN_XCD=0: linear order
+  g.xcd_order = pl.xcd && u.nx % 16 == 0 && u.ny % 16 == 0 && u.nz % kUnitVox == 0 && u.N % kPiece == 0 ? 1 : 0;
+  return g;
+}
+
+// One classification launch's frames: frames[first .. first + n), n <= kClsFrames, at offset fb (a multiple of kClsFrames) of
+// their window.
+struct FrameGroup {
+  const saf_frame* frames;
+  int first, n, fb;
+};
+
+// The group's depth tile maxima (and, in the tiled layout, tiled copies) from the frames' own images, on stream `st`.
+void launch_depth_tiles(const WinPlan& pl, const TileView& tv, const FrameGroup& g, hipStream_t st) {
+  ClsArgs ca;
+  ca.n = g.n;
+  ca.H = pl.H; ca.W = pl.W;
+  for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = g.frames[g.first + (k < g.n ? k : 0)].depth;
+  float* tmax = tv.tmax_w + (size_t)g.fb * kMaxDepthTiles;
+  hipLaunchKernelGGL(depth_max_kernel, dim3((pl.n_tiles + 3) / 4, g.n), dim3(256), 0, st, ca, pl.ts_log2, pl.tiles_x, pl.n_tiles, tmax,
+                     pl.tiled ? tv.tdepth_w + (size_t)g.fb * pl.dpx : nullptr, (pl.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2,
+                     (int)pl.dpx);
+  hipLaunchKernelGGL(depth_reduce_kernel, dim3(g.n), dim3(256), 0, st, tmax, pl.n_tiles, tv.dmax_w + g.fb);
+}
+
+// The group's classification launch (one mask plane) over the unit `kv`, on stream `cs`.  count: the launch counts its frames in
+// stats[2]; use_tiled: it reads the tiled depth copies that launch_depth_tiles wrote.
+int launch_classify(const WinPlan& pl, const WinView& v, const TileView& tv, const KVol& kv, const FrameGroup& g, int count,
+                    bool use_tiled, uint64_t* stats, saf_profiler* prof, hipStream_t cs) {
+  ClsArgs ca;
+  ca.n = g.n;
+  ca.H = pl.H; ca.W = pl.W; ca.slot = g.fb; ca.count = count;
+  ca.guard_x = pl.W <= 8192 ? (float)pl.W * SAF_CLS_GUARD_EPS : 2.0f;
+  ca.guard_y = pl.H <= 8192 ? (float)pl.H * SAF_CLS_GUARD_EPS : 2.0f;
+  ca.mid_x = (float)(pl.W - 1) * 0.5f; ca.mid_y = (float)(pl.H - 1) * 0.5f;
+  ca.verify = stats ? reinterpret_cast<unsigned long long*>(stats) + 7 : nullptr;
+  ca.tiles_x8 = (pl.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2;  // tiles per image row
+  ca.depth_bytes = use_tiled ? (int)(pl.dpx * sizeof(float)) : pl.H * pl.W * 4;
+  for (int k = 0; k < kClsFrames; ++k) {
+    const saf_frame& fr = g.frames[g.first + (k < g.n ? k : 0)];
+    ca.depth[k] = fr.depth; ca.rgb[k] = fr.rgb; ca.pose[k] = fr.pose; ca.K[k] = fr.K; ca.label_map[k] = fr.label_map;
+    ca.feat_map[k] = fr.feat_map;
+  }
+  if (use_tiled) {
+    const float* tdepth = tv.tdepth_w + (size_t)g.fb * pl.dpx;
+    for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = tdepth + (size_t)(k < g.n ? k : 0) * pl.dpx;
+  }
+  uint32_t* plane = v.masks + (size_t)(g.fb / kClsFrames) * pl.wl.mask_plane;
+  ScopedPair t(prof, 1, g.first, cs);
+  const bool verify = pl.verify && stats;
+  const bool sum = pl.sum;
+  auto kfn = use_tiled ? (verify ? (sum ? classify_bricks_kernel<true, true, true> : classify_bricks_kernel<false, true, true>)
+                                 : (sum ? classify_bricks_kernel<true, false, true> : classify_bricks_kernel<false, false, true>))
+                       : (verify ? (sum ? classify_bricks_kernel<true, true, false> : classify_bricks_kernel<false, true, false>)
+                                 : (sum ? classify_bricks_kernel<true, false, false> : classify_bricks_kernel<false, false, false>));
+  // (the frames' largest depths, dmax, feed the bricks' frame cull)
+  hipLaunchKernelGGL(kfn, dim3(win_geom(pl, kv).cls_wgs), dim3(256), 0, cs, kv, ca, tv.dmax_w + g.fb,
+                     tv.tmax_w + (size_t)g.fb * kMaxDepthTiles, pl.ts_log2, pl.tiles_x, plane,
+                     reinterpret_cast<unsigned long long*>(stats), v.cls_acc, v.tab);
+  return check_launch("classify_bricks_kernel");
+}
+
+// A unit starts on stream `cs`: its header (counters, frame table) and mask planes were those of the unit two back, whose row
+// kernel must be over (two_back: there is such a unit); then the header is cleared.
+int open_unit_header(const WinView& v, const WinOverlap* ov, bool two_back, hipStream_t cs) {
+  if (ov && two_back && hipStreamWaitEvent(cs, ov->fuse_done[v.par], 0) != hipSuccess) return fail(SAF_E_HIP, "hipStreamWaitEvent");
+  if (hipMemsetAsync(v.hdr, 0, kHdrBytes, cs) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(workspace header)");
+  return SAF_OK;
+}
+
+// The row step of a unit whose F frames are classified, on stream `s`: the window's map images (prep: unless the workspace holds
+// them already -- the slabs of one window share them), then the row kernel or the brick form.  f0: the profiler's frame number.
+int launch_rows(const WinPlan& pl, const WinView& v, const KVol& kv, int F, bool prep, uint64_t* stats, saf_profiler* prof, int f0,
+                hipStream_t s) {
+  int rc = SAF_OK;
+  WinArgs wa;
+  wa.F = F; wa.H = pl.H; wa.W = pl.W; wa.npy = pl.npy; wa.npx = pl.npx; wa.rgb_bilinear = pl.rgb_bilinear;
+  wa.rgbl = v.rgbl;
+  wa.rgbl_px = (int)rgbl_px_padded(pl.H, pl.W); wa.rgbl_tiles_x = (pl.W + 3) >> 2;
+  if (prep) {
+    ScopedPair t(prof, 0, f0, s);
+    hipLaunchKernelGGL(prep_rows_kernel, dim3(pl.prep_blocks, F), dim3(256), 0, s, v.tab, static_cast<void*>(v.maps),
+                       pl.maps16 ? (int)(pl.img_bytes16 / 2) : (int)(pl.wl.img_bytes / sizeof(float)), kv.D, pl.P, pl.maps16 ? 1 : 0);
+    if ((rc = check_launch("prep_rows_kernel"))) return rc;
+    if (wa.rgbl) {
+      hipLaunchKernelGGL(prep_rgbl_kernel, dim3((pl.H * pl.W + 255) / 256, F), dim3(256), 0, s, v.tab, const_cast<float4*>(wa.rgbl), pl.H,
+                         pl.W, wa.rgbl_tiles_x, wa.rgbl_px);
+      if ((rc = check_launch("prep_rgbl_kernel"))) return rc;
+    }
+  }
+  ScopedPair t(prof, 2, f0, s);
+  if (pl.brick_form)
+    return launch_fuse_bricks(kv, wa, v.tab, v.maps, pl.wl.img_bytes, reinterpret_cast<unsigned long long*>(stats),
+                              reinterpret_cast<unsigned int*>(v.hdr), v.masks, pl.wl.mask_plane, v.cls_acc, v.aux, pl.aux_bytes, v.par,
+                              pl.split, s);
+  const WinGeom g = win_geom(pl, kv);
+  hipLaunchKernelGGL(pl.fn, dim3(g.grid), dim3(kWinThreads), pl.win_lds, s, kv, wa, v.tab, v.maps, pl.img_vecs,
+                     reinterpret_cast<unsigned long long*>(stats), reinterpret_cast<unsigned int*>(v.hdr), v.masks, pl.wl.mask_plane,
+                     v.cls_acc, g.xcd_order);
+  return check_launch("fuse_window_kernel");
+}
+
+// Shapes the windowed path takes; everything else runs the per-frame pipeline.  A call needs kWinMinFrames frames and may take
+// the brick form; a session's push may be short, and a session takes the row forms only.
+bool win_shape_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, int min_frames, bool bricks_allowed) {
   const bool enabled = !(getenv("SAF_WINDOW") && getenv("SAF_WINDOW")[0] == '0');
-  if (!enabled || n_frames < kWinMinFrames) return false;
+  if (!enabled || n_frames < min_frames) return false;
   // SAF_WINDOW_BF16=0 keeps bf16 volumes on the per-frame pipeline
   const bool bf16_on = !(getenv("SAF_WINDOW_BF16") && getenv("SAF_WINDOW_BF16")[0] == '0');
   if (kv.bf16 && !bf16_on) return false;
-  const saf_frame& fr0 = frames[0];
-  const WinLayout wl0 = win_layout(kv.N, kv.D, fr0.npy * fr0.npx);
-  const bool bricks = brick_form_ok(kv) && workspace_bytes > wl0.cmax_off && brick_aux_fits(kv, workspace_bytes - wl0.cmax_off);
+  const saf_frame& f0 = frames[0];
+  const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
+  if (brick_form_ok(kv) && !bricks_allowed) return false;
+  const bool bricks = brick_form_ok(kv) && workspace_bytes > wl.cmax_off && brick_aux_fits(kv, workspace_bytes - wl.cmax_off);
   if (!bricks) {  // the frame-ordered row kernel: whole 1 KiB pieces of a row per wave instruction
     if (kv.D % 256 != 0 || kv.D > 1024) return false;
     if (kv.bf16 && kv.D % 512 != 0) return false;  // a lane moves 8 bf16 channels: 512 per wave
   }
-  const saf_frame& f0 = frames[0];
-  for (int32_t i = 0; i < n_frames; ++i) {
+  for (int32_t i = 1; i < n_frames; ++i) {
     const saf_frame& f = frames[i];
     if (f.height != f0.height || f.width != f0.width || f.npy != f0.npy || f.npx != f0.npx ||
         f.rgb_bilinear != f0.rgb_bilinear || (f.label_map == nullptr) != (f0.label_map == nullptr))
       return false;
   }
   if (f0.npx + 3 > 255 || f0.npy + 3 > 255) return false;  // a hit's map cell travels as two bytes
-  const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
   if (wl.maps_bytes >= (size_t)kTapOutside) return false;  // the taps are buffer loads with 31-bit byte offsets
   return workspace_bytes >= wl.cmax_off;  // (the brick form's own region was checked above: brick_aux_fits)
+}
+}  // namespace
+
+bool window_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
+  return win_shape_ok(kv, frames, n_frames, workspace_bytes, kWinMinFrames, true);
 }
 
 // x-planes [x0, x0 + nx) of a volume as a volume of their own: the same buffers, offset (a slab of x-planes is a contiguous
@@ -1738,64 +1983,11 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     KFrame t;
     if ((rc = make_kframe(&frames[i], &t))) return rc;
   }
-  const int P = kf0.npy * kf0.npx;
-  // Two layouts of the workspace: with room for the window's depth images re-laid-out in tiles (a workspace sized by
-  // saf_fuse_workspace_bytes_for_frames) or without (the classification then reads the frames' own row-major images).
-  // SAF_CLS_TILED=0 (read per call): never tiled; 2: the first unit of a call reads the tiled copies too (tests: a single-window call).
-  const size_t dpx = depth_px_padded(kf0.H, kf0.W);
-  // (a volume that counts labels: the frames-sized layout also holds one window of packed {r, g, b, label} images)
-  const size_t rpx = kv.labels ? rgbl_px_padded(kf0.H, kf0.W) : 0;
-  const WinLayout wl_lin = win_layout(kv.N, kv.D, P), wl_til = win_layout(kv.N, kv.D, P, false, dpx, rpx);
-  const char* til_env = getenv("SAF_CLS_TILED");
-  bool tiled = !(til_env && til_env[0] == '0') && dpx * sizeof(float) < (size_t)1 << 31 && workspace_bytes >= wl_til.cmax_off;
-  if (tiled && brick_form_ok(kv)) {  // the brick form's pools follow the tile region: both must fit, or neither moves
-    const size_t a_lin = workspace_bytes > wl_lin.cmax_off ? workspace_bytes - wl_lin.cmax_off : 0;
-    const size_t a_til = workspace_bytes - wl_til.cmax_off;
-    if (a_lin > 0 && brick_aux_fits(kv, a_lin) && !(a_til > 0 && brick_aux_fits(kv, a_til))) tiled = false;
-  }
-  const WinLayout wl = tiled ? wl_til : wl_lin;
-  // ClipSeemFusion's image side from packed images (SAF_WIN_RGBL=0, read per call: from the frames' own images -- the A/B)
-  const bool rgbl_on = wl.cmax_off > wl.rgbl_off && kf0.rgb_bilinear && kf0.label_map && !(getenv("SAF_WIN_RGBL") && getenv("SAF_WIN_RGBL")[0] == '0');
-  const bool sum = kv.accum == SAF_SUM;
-  int img_vecs = (int)(wl.img_bytes / sizeof(float4));
-  const int prep_blocks = (kv.D * (P + 1) + 255) / 256;
-  const size_t aux_bytes = workspace_bytes > wl.cmax_off ? workspace_bytes - wl.cmax_off : 0;
-  const bool brick_form = brick_form_ok(kv) && aux_bytes > 0 && brick_aux_fits(kv, aux_bytes);
-  const int split = brick_form && brick_split() ? 1 : 0;
-  WinFn fn = nullptr;
-  size_t win_lds = 0;
-  // SAF_WIN_MAPS16=0 (read per call): a bf16 volume keeps fp32 map images -- it takes the frame-ordered kernel, bit-identical
-  // to the per-frame bf16 pipeline -- instead of the order-free form's bf16 images (one rounding of every tap to the volume's
-  // precision, exact when the backbone emitted bf16: BASELINE config 3).  fp32 volumes are not affected.
-  const char* m16 = getenv("SAF_WIN_MAPS16");
-  const bool of = window_form_sums() && !(kv.bf16 != 0 && m16 && m16[0] == '0');
-  if (!brick_form) switch (kv.D / 256) {
-    case 1: fn = pick_win<1>(sum, kv.bf16 != 0, of, &win_lds); break;
-    case 2: fn = pick_win<2>(sum, kv.bf16 != 0, of, &win_lds); break;
-    case 3: fn = pick_win<3>(sum, kv.bf16 != 0, of, &win_lds); break;
-    default: fn = pick_win<4>(sum, kv.bf16 != 0, of, &win_lds); break;
-  }
-  // bf16 volume in the order-free form: the window's map images are kept in bf16 (what the kernel's BF16 && OF instantiations read)
-  const bool maps16 = !brick_form && of && kv.bf16 != 0 && SAF_WIN_MAPS16_BUILD;
-  const size_t img_bytes16 = ((size_t)kv.D * (P + 1) * 2 + 255) & ~(size_t)255;
-  if (maps16) img_vecs = (int)(img_bytes16 / sizeof(float4));
-  if (!brick_form) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)win_lds);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", win_lds, hipGetErrorString(e));
-  }
-  float* maps = reinterpret_cast<float*>(ws + kHdrTotal);
-  const int wgs_env = getenv("SAF_WIN_WGS") ? atoi(getenv("SAF_WIN_WGS")) : 0;
-  const char* xcd_env = getenv("SAF_WIN_XCD");
-  static_assert(kClsAccOff + kClsShards * 2 * sizeof(unsigned long long) <= kTableOff && kClsAccOff >= 256,
-                "workspace header layout");
-  // the depth tiles of the classification's occlusion cull: 16 x 16 pixels, doubled until a frame has at most kMaxDepthTiles
-  int ts_log2 = 4;
-  while (((kf0.W + (1 << ts_log2) - 1) >> ts_log2) * ((kf0.H + (1 << ts_log2) - 1) >> ts_log2) > kMaxDepthTiles) ++ts_log2;
-  const int tiles_x = (kf0.W + (1 << ts_log2) - 1) >> ts_log2, n_tiles = tiles_x * ((kf0.H + (1 << ts_log2) - 1) >> ts_log2);
+  WinPlan pl;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
   int tile_window[kTileWindows];  // which window's tile maxima a slot of the tile region holds (-1: none)
   for (int k = 0; k < kTileWindows; ++k) tile_window[k] = -1;
-  const int wlen = window_frames();
+  const int wlen = pl.wlen;
   const int n_win = (n_frames + wlen - 1) / wlen;
   auto win_frames = [&](int w) { return n_frames - w * wlen < wlen ? n_frames - w * wlen : wlen; };
 
@@ -1815,7 +2007,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     const char* e0 = getenv("SAF_WIN_W0_SLABS");
     const char* e1 = getenv("SAF_WIN_SLABS");
     auto fit = [&](int n) {
-      if (!ov || brick_form || n < 2 || kv.nx % 16 != 0) return 1;
+      if (!ov || pl.brick_form || n < 2 || kv.nx % 16 != 0) return 1;
       while (n > 1 && (kv.nx / 16) % n != 0) --n;
       return n;
     };
@@ -1827,28 +2019,6 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     }
   }
   const int n_units = (int)units.size();
-
-  struct Geom {
-    uint32_t cls_wgs, grid;  // workgroups of a classification launch (4 bricks each), of the row kernel
-    int xcd_order;
-  };
-  auto geom = [&](const KVol& u) {
-    Geom g;
-    const uint32_t n_pieces = (uint32_t)(((int64_t)u.N + kPiece - 1) / kPiece);
-    const uint32_t row_wgs = (n_pieces + kWinWaves - 1) / kWinWaves;
-    // (the frame-ordered form keeps its rows in LDS: with 512-hit chunks 115 KB per workgroup at D = 512 -- ONE fits a CU, and a grid
-    //  of two per CU would leave half of the persistent workgroups waiting for the others to finish)
-    const int fit = win_lds > 0 ? (int)((160 * 1024) / win_lds) : 2;
-    g.grid = (uint32_t)device_cus() * (wgs_env > 0 ? wgs_env : (of ? SAF_WIN_OF_WPE : (fit < 1 ? 1 : (fit > 2 ? 2 : fit))));
-    if (g.grid > row_wgs) g.grid = row_wgs;
-    // the classification's bricks: the brick grid padded to whole 8 x 8 tiles of brick columns
-    const uint32_t tx = ((uint32_t)u.nx + 8 * kBrickX - 1) / (8 * kBrickX), ty = ((uint32_t)u.ny + 8 * kBrickY - 1) / (8 * kBrickY);
-    const uint32_t nbz = ((uint32_t)u.nz + kBrickZ - 1) / kBrickZ;
-    g.cls_wgs = (tx * ty * 64u * nbz + 3u) / 4u;
-    // units of the row kernel in XCD-compact order (see the kernel); SAF_WIN_XCD=0: linear order
-    g.xcd_order = !(xcd_env && xcd_env[0] == '0') && u.nx % 16 == 0 && u.ny % 16 == 0 && u.nz % kUnitVox == 0 && u.N % kPiece == 0 ? 1 : 0;
-    return g;
-  };
 
   // Two streams.  The classification (VALU-bound; TSDF, depth images, one mask plane per 32 frames) of unit u + 1 runs
   // on `cs` while the row kernel (memory-bound) of unit u runs on the caller's stream: the row kernel leaves LDS and
@@ -1869,21 +2039,11 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
       fprintf(stderr, "[win trace] %8.3f ms  %s %d\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), what, w);
   };
-  // The depth tile maxima (and tiled copies) of one window: depth_max_kernel + depth_reduce_kernel per 32 frames, on stream `st`.
+  // The depth tile maxima (and tiled copies) of one window: one launch_depth_tiles per 32 frames, on stream `st`.
   auto depth_tiles = [&](int widx, int f0, int F, hipStream_t st) {
-    float* dmax_w = reinterpret_cast<float*>(ws + wl.tile_off + (size_t)(widx % kTileWindows) * wl.tile_win);
-    float* tmax_w = dmax_w + 1024;
-    float* tdepth_w = tmax_w + (size_t)kWin * kMaxDepthTiles;
-    for (int fb = 0; fb < F; fb += kClsFrames) {
-      ClsArgs ca;
-      ca.n = fb + kClsFrames < F ? kClsFrames : F - fb;
-      ca.H = kf0.H; ca.W = kf0.W;
-      for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = frames[f0 + fb + (k < ca.n ? k : 0)].depth;
-      float* tmax = tmax_w + (size_t)fb * kMaxDepthTiles;
-      hipLaunchKernelGGL(depth_max_kernel, dim3((n_tiles + 3) / 4, ca.n), dim3(256), 0, st, ca, ts_log2, tiles_x, n_tiles, tmax,
-                         tiled ? tdepth_w + (size_t)fb * dpx : nullptr, (kf0.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2, (int)dpx);
-      hipLaunchKernelGGL(depth_reduce_kernel, dim3(ca.n), dim3(256), 0, st, tmax, n_tiles, dmax_w + fb);
-    }
+    const TileView tv = tile_view(ws, pl, widx % kTileWindows);
+    for (int fb = 0; fb < F; fb += kClsFrames)
+      launch_depth_tiles(pl, tv, FrameGroup{frames, f0 + fb, fb + kClsFrames < F ? kClsFrames : F - fb, fb}, st);
   };
   // The later windows' tiles AHEAD of time, on the caller's stream: it is idle until the first window has been classified, and
   // every such pair of small launches inside the classification chain (16 per 512-frame job, ~70 us each beside a row kernel)
@@ -1899,76 +2059,38 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   }
   auto classify = [&](int ui) -> int {
     const WinUnit& u = units[ui];
-    const Geom g = geom(u.kv);
-    const int F = u.F, f0 = u.f0, par = ui & 1;
-    unsigned char* hdr = ws + (size_t)par * kHdrBytes;
-    uint32_t* masks = reinterpret_cast<uint32_t*>(ws + kHdrTotal + wl.maps_bytes + (size_t)par * wl.mask_bytes);
+    const int F = u.F, f0 = u.f0;
+    const WinView v = win_view(ws, pl, ui & 1);
     // the window's depth tile maxima: computed when a unit of the window first needs them
     const int widx = f0 / wlen, tslot = widx % kTileWindows;
-    float* dmax_w = reinterpret_cast<float*>(ws + wl.tile_off + (size_t)tslot * wl.tile_win);  // [kWin] largest, [kWin] smallest
-    float* tmax_w = dmax_w + 1024;
-    float* tdepth_w = tmax_w + (size_t)kWin * kMaxDepthTiles;  // (tiled layout only) the window's depth images in tiles
+    const TileView tv = tile_view(ws, pl, tslot);
     const bool tiles_cached = tile_window[tslot] == widx;
     tile_window[tslot] = widx;
-    unsigned long long* cls_acc = reinterpret_cast<unsigned long long*>(hdr + kClsAccOff);
-    WinTable* tab = reinterpret_cast<WinTable*>(hdr + kTableOff);
+    int r;
     mark("classify: begin", ui);
-    if (ov && ui >= 2 && hipStreamWaitEvent(cs, ov->fuse_done[par], 0) != hipSuccess) return fail(SAF_E_HIP, "hipStreamWaitEvent");
     if (pre_tiles && ui == 1 && hipStreamWaitEvent(cs, ov->tiles, 0) != hipSuccess) return fail(SAF_E_HIP, "hipStreamWaitEvent(tiles)");
-    // header: unit counters, dmax, the classification launches' counter shards, the frame table
-    if (hipMemsetAsync(hdr, 0, kHdrBytes, cs) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(workspace header)");
+    if ((r = open_unit_header(v, ov, ui >= 2, cs))) return r;
     mark("classify: header memset queued", ui);
+    if (!tiles_cached) depth_tiles(widx, f0, F, cs);  // (reads the frames' own images; writes the tile maxima and, in the tiled layout, the copies)
+    // (unit 0 has the chip to itself -- everything the caller queued before is done, nothing of this call runs yet --, where the
+    //  classification is bound by its vector instructions and the tile offset costs 5 % (0.92 vs 0.97 ms per launch): it reads the
+    //  frames' own images; the tiled copies pay where the address path is shared, i.e. for every later unit)
+    const bool use_tiled = pl.tiled && (ui > 0 || pl.tiled_first);
     for (int fb = 0; fb < F; fb += kClsFrames) {
-      ClsArgs ca;
-      ca.n = fb + kClsFrames < F ? kClsFrames : F - fb;
-      ca.H = kf0.H; ca.W = kf0.W; ca.slot = fb; ca.count = u.count;
-      ca.guard_x = kf0.W <= 8192 ? (float)kf0.W * SAF_CLS_GUARD_EPS : 2.0f;
-      ca.guard_y = kf0.H <= 8192 ? (float)kf0.H * SAF_CLS_GUARD_EPS : 2.0f;
-      ca.mid_x = (float)(kf0.W - 1) * 0.5f; ca.mid_y = (float)(kf0.H - 1) * 0.5f;
-      ca.verify = stats ? reinterpret_cast<unsigned long long*>(stats) + 7 : nullptr;
-      ca.tiles_x8 = (kf0.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2;  // tiles per image row
-      // (unit 0 has the chip to itself -- everything the caller queued before is done, nothing of this call runs yet --, where the
-      //  classification is bound by its vector instructions and the tile offset costs 5 % (0.92 vs 0.97 ms per launch): it reads the
-      //  frames' own images; the tiled copies pay where the address path is shared, i.e. for every later unit)
-      const bool use_tiled = tiled && (ui > 0 || (til_env && til_env[0] == '2'));
-      ca.depth_bytes = use_tiled ? (int)(dpx * sizeof(float)) : kf0.H * kf0.W * 4;
-      for (int k = 0; k < kClsFrames; ++k) {
-        const saf_frame& fr = frames[f0 + fb + (k < ca.n ? k : 0)];
-        ca.depth[k] = fr.depth; ca.rgb[k] = fr.rgb; ca.pose[k] = fr.pose; ca.K[k] = fr.K; ca.label_map[k] = fr.label_map;
-        ca.feat_map[k] = fr.feat_map;
-      }
-      uint32_t* plane = masks + (size_t)(fb / kClsFrames) * wl.mask_plane;
-      // the frames' largest depths feed the bricks' frame cull
-      float* dmax = dmax_w + fb;
-      float* tmax = tmax_w + (size_t)fb * kMaxDepthTiles;
-      float* tdepth = tdepth_w + (size_t)fb * dpx;
-      if (!tiles_cached && fb == 0) depth_tiles(widx, f0, F, cs);  // (reads the frames' own images; writes the tile maxima and, in the tiled layout, the copies)
-      if (use_tiled)
-        for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = tdepth + (size_t)(k < ca.n ? k : 0) * dpx;
-      ScopedPair t(prof, 1, f0 + fb, cs);
-      // SAF_CLS_VERIFY=1 (read per call): the self-checking classification -- every voxel slot computes the reference's pixel chain
-      // as well and counts disagreements with the guarded path in stats[7] (tests; tools/cls_guard_verify.py)
-      const bool verify = getenv("SAF_CLS_VERIFY") && getenv("SAF_CLS_VERIFY")[0] == '1' && stats;
-      auto kfn = use_tiled ? (verify ? (sum ? classify_bricks_kernel<true, true, true> : classify_bricks_kernel<false, true, true>)
-                                 : (sum ? classify_bricks_kernel<true, false, true> : classify_bricks_kernel<false, false, true>))
-                       : (verify ? (sum ? classify_bricks_kernel<true, true, false> : classify_bricks_kernel<false, true, false>)
-                                 : (sum ? classify_bricks_kernel<true, false, false> : classify_bricks_kernel<false, false, false>));
-      hipLaunchKernelGGL(kfn, dim3(g.cls_wgs), dim3(256), 0, cs, u.kv, ca, dmax, tmax, ts_log2, tiles_x, plane,
-                         reinterpret_cast<unsigned long long*>(stats), cls_acc, tab);
+      const FrameGroup g{frames, f0 + fb, fb + kClsFrames < F ? kClsFrames : F - fb, fb};
+      if ((r = launch_classify(pl, v, tv, u.kv, g, u.count, use_tiled, stats, prof, cs))) return r;
     }
-    int r = check_launch("classify_bricks_kernel");
-    if (r) return r;
-    if (split) {  // the brick form's build kernel: the window's hit records, sorted groups and scalar side, into the segment pool
+    if (pl.split) {  // the brick form's build kernel: the window's hit records, sorted groups and scalar side, into the segment pool
       WinArgs wa;
       wa.F = F; wa.H = kf0.H; wa.W = kf0.W; wa.npy = kf0.npy; wa.npx = kf0.npx; wa.rgb_bilinear = kf0.rgb_bilinear;
       wa.rgbl = nullptr; wa.rgbl_px = 0; wa.rgbl_tiles_x = 0;
       ScopedPair t(prof, 3, f0, cs);
-      if ((r = launch_brick_build(u.kv, wa, tab, wl.img_bytes, reinterpret_cast<unsigned long long*>(stats), masks, wl.mask_plane,
-                                  ws + wl.cmax_off, aux_bytes, par, cs)))
+      if ((r = launch_brick_build(u.kv, wa, v.tab, pl.wl.img_bytes, reinterpret_cast<unsigned long long*>(stats), v.masks, pl.wl.mask_plane,
+                                  v.aux, pl.aux_bytes, v.par, cs)))
         return r;
     }
     mark("classify: launches queued", ui);
-    if (ov && hipEventRecord(ov->cls_done[par], cs) != hipSuccess) return fail(SAF_E_HIP, "hipEventRecord");
+    if (ov && hipEventRecord(ov->cls_done[v.par], cs) != hipSuccess) return fail(SAF_E_HIP, "hipEventRecord");
     return SAF_OK;
   };
   if ((rc = classify(0))) return rc;
@@ -1979,53 +2101,23 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   // say which rows its row kernel writes -- the two kernels' rows are disjoint.  What it buys is small (the row kernel slows down
   // by nearly what the clear takes: saf_misc.hip, clear_rows).  SAF_WIN_CLEAR_BESIDE=0 (read per call): behind the last row
   // kernel, on the caller's stream.
-  const bool clear_beside = recycled && ov && !brick_form && !(slabs && slabs->n > 0) && n_units == n_win &&
+  const bool clear_beside = recycled && ov && !pl.brick_form && !(slabs && slabs->n > 0) && n_units == n_win &&
                             !(getenv("SAF_WIN_CLEAR_BESIDE") && getenv("SAF_WIN_CLEAR_BESIDE")[0] == '0');
   int maps_of = -1;  // the window whose map images the workspace holds
   for (int ui = 0; ui < n_units && rc == SAF_OK; ++ui) {
     const WinUnit& u = units[ui];
-    const Geom g = geom(u.kv);
-    const int F = u.F, f0 = u.f0, par = ui & 1;
-    WinArgs wa;
-    wa.F = F; wa.H = kf0.H; wa.W = kf0.W; wa.npy = kf0.npy; wa.npx = kf0.npx; wa.rgb_bilinear = kf0.rgb_bilinear;
-    wa.rgbl = rgbl_on && !brick_form ? reinterpret_cast<const float4*>(ws + wl.rgbl_off) : nullptr;
-    wa.rgbl_px = (int)rgbl_px_padded(kf0.H, kf0.W); wa.rgbl_tiles_x = (kf0.W + 3) >> 2;
-    unsigned char* hdr = ws + (size_t)par * kHdrBytes;
-    const WinTable* tab = reinterpret_cast<const WinTable*>(hdr + kTableOff);
-    uint32_t* masks = reinterpret_cast<uint32_t*>(ws + kHdrTotal + wl.maps_bytes + (size_t)par * wl.mask_bytes);
+    const int par = ui & 1;
+    const WinView v = win_view(ws, pl, par);
     if (ov && ui + 1 < n_units && (rc = classify(ui + 1))) break;  // queued now: it runs beside this unit's row kernel
     if (ov && hipStreamWaitEvent(s, ov->cls_done[par], 0) != hipSuccess) { rc = fail(SAF_E_HIP, "hipStreamWaitEvent"); break; }
     if (clear_beside && ui + 1 == n_units) {
       // (queued behind this unit's classification; the row kernel of the unit before must have stored its weights)
       if (ui >= 1 && hipStreamWaitEvent(cs, ov->fuse_done[par ^ 1], 0) != hipSuccess) { rc = fail(SAF_E_HIP, "hipStreamWaitEvent"); break; }
-      if ((rc = launch_clear_unwritten(u.kv, masks, wl.mask_plane, (F + kClsFrames - 1) / kClsFrames, cs))) break;
+      if ((rc = launch_clear_unwritten(u.kv, v.masks, pl.wl.mask_plane, (u.F + kClsFrames - 1) / kClsFrames, cs))) break;
     }
-    if (maps_of != u.window) {  // (the slabs of one window share its map images)
-      ScopedPair t(prof, 0, f0, s);
-      hipLaunchKernelGGL(prep_rows_kernel, dim3(prep_blocks, F), dim3(256), 0, s, tab, static_cast<void*>(maps),
-                         maps16 ? (int)(img_bytes16 / 2) : (int)(wl.img_bytes / sizeof(float)), kv.D, P, maps16 ? 1 : 0);
-      if ((rc = check_launch("prep_rows_kernel"))) break;
-      if (wa.rgbl) {
-        hipLaunchKernelGGL(prep_rgbl_kernel, dim3((kf0.H * kf0.W + 255) / 256, F), dim3(256), 0, s, tab, const_cast<float4*>(wa.rgbl), kf0.H, kf0.W,
-                           wa.rgbl_tiles_x, wa.rgbl_px);
-        if ((rc = check_launch("prep_rgbl_kernel"))) break;
-      }
-      maps_of = u.window;
-    }
-    if (brick_form) {
-      ScopedPair t(prof, 2, f0, s);
-      rc = launch_fuse_bricks(u.kv, wa, tab, maps, wl.img_bytes, reinterpret_cast<unsigned long long*>(stats),
-                              reinterpret_cast<unsigned int*>(hdr), masks, wl.mask_plane,
-                              reinterpret_cast<const unsigned long long*>(hdr + kClsAccOff),
-                              ws + wl.cmax_off, aux_bytes, par, split, s);
-    } else {
-      ScopedPair t(prof, 2, f0, s);
-      hipLaunchKernelGGL(fn, dim3(g.grid), dim3(kWinThreads), win_lds, s, u.kv, wa, tab, maps, img_vecs,
-                         reinterpret_cast<unsigned long long*>(stats), reinterpret_cast<unsigned int*>(hdr), masks, wl.mask_plane,
-                         reinterpret_cast<const unsigned long long*>(hdr + kClsAccOff), g.xcd_order);
-      rc = check_launch("fuse_window_kernel");
-    }
-    if (rc) break;
+    // (the slabs of one window share its map images)
+    if ((rc = launch_rows(pl, v, u.kv, u.F, maps_of != u.window, stats, prof, u.f0, s))) break;
+    maps_of = u.window;
     mark("rows: queued", ui);
     // a finished slab of a recycled volume: its rows that are still unwritten are zeroed before anyone is told it is finished
     if (u.done >= 0 && recycled && (rc = launch_clear_unwritten(u.kv, nullptr, 0, 0, s))) break;
@@ -2066,112 +2158,23 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
 // session keeps ONE pipeline over its calls and classifies as the frames arrive: every push of 32 frames is one classification
 // launch (one mask plane) on the classification stream; when a window's last plane is queued its row kernel follows on the
 // caller's stream, and the next window's launches -- pushed while it runs -- run beside it, as units u and u + 1 of one
-// fuse_many_windowed call do.  Same kernels, same arguments per launch, same window cuts: results are bit for bit those of one
+// fuse_many_windowed call do.  A session calls the launchers that fuse_many_windowed calls (win_plan, launch_depth_tiles,
+// launch_classify, open_unit_header, launch_rows) with the same window cuts: results are bit for bit those of one
 // saf_fuse_frames call over the same frames.  (The row forms only: the brick form builds its segments per window.)
 // ---------------------------------------------------------------------------------------------
-namespace {
-struct StreamPlan {  // what fuse_many_windowed derives at its top, for one (volume, frame shape, workspace)
-  WinLayout wl;
-  bool tiled, sum, maps16;
-  size_t dpx, img_bytes16, win_lds;
-  int P, img_vecs, prep_blocks, ts_log2, tiles_x, n_tiles, wlen;
-  WinFn fn;
-};
-int stream_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, StreamPlan* pl) {
-  pl->P = kf0.npy * kf0.npx;
-  pl->dpx = depth_px_padded(kf0.H, kf0.W);
-  const WinLayout wl_lin = win_layout(kv.N, kv.D, pl->P),
-                  wl_til = win_layout(kv.N, kv.D, pl->P, false, pl->dpx, kv.labels ? rgbl_px_padded(kf0.H, kf0.W) : 0);
-  const char* til_env = getenv("SAF_CLS_TILED");
-  pl->tiled = !(til_env && til_env[0] == '0') && pl->dpx * sizeof(float) < (size_t)1 << 31 && workspace_bytes >= wl_til.cmax_off;
-  pl->wl = pl->tiled ? wl_til : wl_lin;
-  if (workspace_bytes < pl->wl.cmax_off) return fail(SAF_E_WORKSPACE, "session: workspace too small");
-  pl->sum = kv.accum == SAF_SUM;
-  pl->img_vecs = (int)(pl->wl.img_bytes / sizeof(float4));
-  pl->prep_blocks = (kv.D * (pl->P + 1) + 255) / 256;
-  const char* m16 = getenv("SAF_WIN_MAPS16");
-  const bool of = window_form_sums() && !(kv.bf16 != 0 && m16 && m16[0] == '0');
-  switch (kv.D / 256) {
-    case 1: pl->fn = pick_win<1>(pl->sum, kv.bf16 != 0, of, &pl->win_lds); break;
-    case 2: pl->fn = pick_win<2>(pl->sum, kv.bf16 != 0, of, &pl->win_lds); break;
-    case 3: pl->fn = pick_win<3>(pl->sum, kv.bf16 != 0, of, &pl->win_lds); break;
-    default: pl->fn = pick_win<4>(pl->sum, kv.bf16 != 0, of, &pl->win_lds); break;
-  }
-  if (!pl->fn) return fail(SAF_E_UNSUPPORTED, "session: no row kernel for this width");
-  pl->maps16 = of && kv.bf16 != 0 && SAF_WIN_MAPS16_BUILD;
-  pl->img_bytes16 = ((size_t)kv.D * (pl->P + 1) * 2 + 255) & ~(size_t)255;
-  if (pl->maps16) pl->img_vecs = (int)(pl->img_bytes16 / sizeof(float4));
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->win_lds);
-  if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
-  pl->ts_log2 = 4;
-  while (((kf0.W + (1 << pl->ts_log2) - 1) >> pl->ts_log2) * ((kf0.H + (1 << pl->ts_log2) - 1) >> pl->ts_log2) > kMaxDepthTiles) ++pl->ts_log2;
-  pl->tiles_x = (kf0.W + (1 << pl->ts_log2) - 1) >> pl->ts_log2;
-  pl->n_tiles = pl->tiles_x * ((kf0.H + (1 << pl->ts_log2) - 1) >> pl->ts_log2);
-  pl->wlen = window_frames();
-  return SAF_OK;
-}
-}  // namespace
-
 bool stream_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
-  // what the windowed ROW forms take (window_ok's shape rules without its minimum of 16 frames per call: a push may be short)
-  if (brick_form_ok(kv)) return false;
-  if (getenv("SAF_WINDOW") && getenv("SAF_WINDOW")[0] == '0') return false;
-  if (kv.bf16 && getenv("SAF_WINDOW_BF16") && getenv("SAF_WINDOW_BF16")[0] == '0') return false;
-  if (kv.D % 256 != 0 || kv.D > 1024 || (kv.bf16 && kv.D % 512 != 0) || n_frames < 1) return false;
-  const saf_frame& f0 = frames[0];
-  for (int32_t i = 1; i < n_frames; ++i) {
-    const saf_frame& f = frames[i];
-    if (f.height != f0.height || f.width != f0.width || f.npy != f0.npy || f.npx != f0.npx || f.rgb_bilinear != f0.rgb_bilinear ||
-        (f.label_map == nullptr) != (f0.label_map == nullptr))
-      return false;
-  }
-  if (f0.npx + 3 > 255 || f0.npy + 3 > 255) return false;
-  const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
-  return wl.maps_bytes < (size_t)kTapOutside && workspace_bytes >= wl.cmax_off;
+  return win_shape_ok(kv, frames, n_frames, workspace_bytes, 1, false);
 }
 
+namespace {
 // the open window's row kernel: behind its last classification launch
-int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen) {
-  if (!st->open || st->filled == 0) return SAF_OK;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  StreamPlan pl;
-  int rc = stream_plan(st->kv, st->kf0, workspace_bytes, &pl);
-  if (rc) return rc;
-  const KVol& kv = st->kv;
-  const int par = st->n_windows & 1, F = st->filled;
-  if (hipEventRecord(ov->cls_done[par], ov->aux) != hipSuccess || hipStreamWaitEvent(s, ov->cls_done[par], 0) != hipSuccess)
+int close_window(const WinPlan& pl, unsigned char* ws, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen) {
+  int rc = SAF_OK;
+  const WinView v = win_view(ws, pl, st->n_windows & 1);
+  if (hipEventRecord(ov->cls_done[v.par], ov->aux) != hipSuccess || hipStreamWaitEvent(s, ov->cls_done[v.par], 0) != hipSuccess)
     return fail(SAF_E_HIP, "session: could not order the row kernel behind its classification");
-  unsigned char* hdr = ws + (size_t)par * kHdrBytes;
-  const WinTable* tab = reinterpret_cast<const WinTable*>(hdr + kTableOff);
-  uint32_t* masks = reinterpret_cast<uint32_t*>(ws + kHdrTotal + pl.wl.maps_bytes + (size_t)par * pl.wl.mask_bytes);
-  float* maps = reinterpret_cast<float*>(ws + kHdrTotal);
-  WinArgs wa;
-  wa.F = F; wa.H = st->kf0.H; wa.W = st->kf0.W; wa.npy = st->kf0.npy; wa.npx = st->kf0.npx; wa.rgb_bilinear = st->kf0.rgb_bilinear;
-  const bool rgbl_on = pl.wl.cmax_off > pl.wl.rgbl_off && st->kf0.rgb_bilinear && st->kf0.label_map &&
-                       !(getenv("SAF_WIN_RGBL") && getenv("SAF_WIN_RGBL")[0] == '0');
-  wa.rgbl = rgbl_on ? reinterpret_cast<const float4*>(ws + pl.wl.rgbl_off) : nullptr;
-  wa.rgbl_px = (int)rgbl_px_padded(st->kf0.H, st->kf0.W); wa.rgbl_tiles_x = (st->kf0.W + 3) >> 2;
-  hipLaunchKernelGGL(prep_rows_kernel, dim3(pl.prep_blocks, F), dim3(256), 0, s, tab, static_cast<void*>(maps),
-                     pl.maps16 ? (int)(pl.img_bytes16 / 2) : (int)(pl.wl.img_bytes / sizeof(float)), kv.D, pl.P, pl.maps16 ? 1 : 0);
-  if ((rc = check_launch("prep_rows_kernel"))) return rc;
-  if (wa.rgbl) {
-    hipLaunchKernelGGL(prep_rgbl_kernel, dim3((wa.H * wa.W + 255) / 256, F), dim3(256), 0, s, tab, const_cast<float4*>(wa.rgbl), wa.H, wa.W,
-                       wa.rgbl_tiles_x, wa.rgbl_px);
-    if ((rc = check_launch("prep_rgbl_kernel"))) return rc;
-  }
-  // (the row kernel's grid and unit order: as fuse_many_windowed's geom())
-  const bool of = window_form_sums() && !(kv.bf16 != 0 && getenv("SAF_WIN_MAPS16") && getenv("SAF_WIN_MAPS16")[0] == '0');
-  const int wgs_env = getenv("SAF_WIN_WGS") ? atoi(getenv("SAF_WIN_WGS")) : 0;
-  const char* xcd_env = getenv("SAF_WIN_XCD");
-  const uint32_t n_pieces = (uint32_t)(((int64_t)kv.N + kPiece - 1) / kPiece), row_wgs = (n_pieces + kWinWaves - 1) / kWinWaves;
-  uint32_t grid = (uint32_t)device_cus() * (wgs_env > 0 ? wgs_env : (of ? SAF_WIN_OF_WPE : 2));
-  if (grid > row_wgs) grid = row_wgs;
-  const int xcd_order = !(xcd_env && xcd_env[0] == '0') && kv.nx % 16 == 0 && kv.ny % 16 == 0 && kv.nz % kUnitVox == 0 && kv.N % kPiece == 0 ? 1 : 0;
-  hipLaunchKernelGGL(pl.fn, dim3(grid), dim3(kWinThreads), pl.win_lds, s, kv, wa, tab, maps, pl.img_vecs,
-                     reinterpret_cast<unsigned long long*>(stats), reinterpret_cast<unsigned int*>(hdr), masks, pl.wl.mask_plane,
-                     reinterpret_cast<const unsigned long long*>(hdr + kClsAccOff), xcd_order);
-  if ((rc = check_launch("fuse_window_kernel"))) return rc;
-  if (hipEventRecord(ov->fuse_done[par], s) != hipSuccess) return fail(SAF_E_HIP, "hipEventRecord");
+  if ((rc = launch_rows(pl, v, st->kv, st->filled, true, stats, nullptr, 0, s))) return rc;
+  if (hipEventRecord(ov->fuse_done[v.par], s) != hipSuccess) return fail(SAF_E_HIP, "hipEventRecord");
   st->n_windows += 1;
   st->filled = 0;
   st->open = false;
@@ -2181,13 +2184,19 @@ int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipSt
     // classification launch of window w + 1 reaches the chip a few microseconds BEFORE the row kernel of window w (which still has a
     // cross-stream wait and prep_rows_kernel in front of it) -- as in one saf_fuse_frames call, where that launch runs at its
     // alone speed while the row kernel's workgroups find their places (profiles/r06/api_b1_timeline.txt: 1.05 ms against 8.4).
-    const int parn = st->n_windows & 1;
-    unsigned char* hdrn = ws + (size_t)parn * kHdrBytes;
-    if (st->n_windows >= 2 && hipStreamWaitEvent(ov->aux, ov->fuse_done[parn], 0) != hipSuccess) return fail(SAF_E_HIP, "hipStreamWaitEvent");
-    if (hipMemsetAsync(hdrn, 0, kHdrBytes, ov->aux) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(workspace header)");
+    if ((rc = open_unit_header(win_view(ws, pl, st->n_windows & 1), ov, st->n_windows >= 2, ov->aux))) return rc;
     st->open = true;
   }
   return SAF_OK;
+}
+}  // namespace
+
+int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen) {
+  if (!st->open || st->filled == 0) return SAF_OK;
+  WinPlan pl;
+  int rc = win_plan(st->kv, st->kf0, workspace_bytes, &pl);
+  if (rc) return rc;
+  return close_window(pl, static_cast<unsigned char*>(workspace), stats, s, ov, st, preopen);
 }
 
 // The depth tiles (maxima, tiled copies) of frames that WILL be pushed next, in order, computed on the stream they were staged on --
@@ -2200,29 +2209,20 @@ int stream_prepare(const KVol& kv, const saf_frame* frames, int32_t n_frames, vo
   int rc = SAF_OK;
   KFrame kf0;
   if ((rc = make_kframe(&frames[0], &kf0))) return rc;
-  StreamPlan pl;
-  if ((rc = stream_plan(kv, kf0, workspace_bytes, &pl))) return rc;
+  WinPlan pl;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
   if (st->prepared < st->pushed) st->prepared = st->pushed;
   int done = 0;
   while (done < n_frames) {
     // where frame number `prepared` of the session will lie: window = closed windows + what is still to be pushed ahead of it
     const long long ahead = st->prepared - st->pushed + (st->open ? st->filled : 0);
-    const int widx = st->n_windows + (int)(ahead / pl.wlen), fb = (int)(ahead % pl.wlen), tslot = widx % kTileWindows;
-    float* dmax_w = reinterpret_cast<float*>(ws + pl.wl.tile_off + (size_t)tslot * pl.wl.tile_win);
-    float* tmax_w = dmax_w + 1024;
-    float* tdepth_w = tmax_w + (size_t)kWin * kMaxDepthTiles;
-    ClsArgs ca;
-    ca.n = n_frames - done < kClsFrames ? n_frames - done : kClsFrames;
-    if (fb + ca.n > pl.wlen) ca.n = pl.wlen - fb;
-    ca.H = kf0.H; ca.W = kf0.W;
-    for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = frames[done + (k < ca.n ? k : 0)].depth;
-    float* tmax = tmax_w + (size_t)fb * kMaxDepthTiles;
-    hipLaunchKernelGGL(depth_max_kernel, dim3((pl.n_tiles + 3) / 4, ca.n), dim3(256), 0, ts, ca, pl.ts_log2, pl.tiles_x, pl.n_tiles, tmax,
-                       pl.tiled ? tdepth_w + (size_t)fb * pl.dpx : nullptr, (kf0.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2, (int)pl.dpx);
-    hipLaunchKernelGGL(depth_reduce_kernel, dim3(ca.n), dim3(256), 0, ts, tmax, pl.n_tiles, dmax_w + fb);
+    const int widx = st->n_windows + (int)(ahead / pl.wlen), fb = (int)(ahead % pl.wlen);
+    int n = n_frames - done < kClsFrames ? n_frames - done : kClsFrames;
+    if (fb + n > pl.wlen) n = pl.wlen - fb;
+    launch_depth_tiles(pl, tile_view(ws, pl, widx % kTileWindows), FrameGroup{frames, done, n, fb}, ts);
     if ((rc = check_launch("depth tiles"))) return rc;
-    st->prepared += ca.n;
-    done += ca.n;
+    st->prepared += n;
+    done += n;
   }
   return SAF_OK;
 }
@@ -2242,8 +2242,8 @@ int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void*
     return fail(SAF_E_INVALID, "the frames of a streaming session share their shapes: finish the session first");
   if (st->open && st->filled % kClsFrames != 0)
     return fail(SAF_E_INVALID, "the open window holds %d frames: only a window's LAST push may be short of a multiple of %d (finish the session)", st->filled, kClsFrames);
-  StreamPlan pl;
-  if ((rc = stream_plan(kv, kf0, workspace_bytes, &pl))) return rc;
+  WinPlan pl;  // built once per push: the window closes below use it too
+  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
   st->kv = kv; st->kf0 = kf0; st->have_shape = true;
   hipStream_t cs = ov->aux;
   // What the classification of these frames waits for: their staging.  With `ready` (an event the caller recorded behind it) ONLY
@@ -2265,72 +2265,34 @@ int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void*
   // computed THERE, behind the staging, and the classification waits for them -- two small launches per 32 frames (0.1 ms beside a
   // row kernel) that would otherwise sit in the classification chain, which a window's time follows
   hipStream_t ts = tile_stream ? tile_stream : cs;
-  const char* til_env = getenv("SAF_CLS_TILED");
-  const bool verify = getenv("SAF_CLS_VERIFY") && getenv("SAF_CLS_VERIFY")[0] == '1' && stats;
   int done = 0;
   while (done < n_frames) {
-    if (st->open && st->filled >= pl.wlen && (rc = stream_close(workspace, workspace_bytes, stats, s, ov, st, true))) return rc;
-    const int par = st->n_windows & 1, widx = st->n_windows, tslot = widx % kTileWindows;
-    unsigned char* hdr = ws + (size_t)par * kHdrBytes;
-    uint32_t* masks = reinterpret_cast<uint32_t*>(ws + kHdrTotal + pl.wl.maps_bytes + (size_t)par * pl.wl.mask_bytes);
-    float* dmax_w = reinterpret_cast<float*>(ws + pl.wl.tile_off + (size_t)tslot * pl.wl.tile_win);
-    float* tmax_w = dmax_w + 1024;
-    float* tdepth_w = tmax_w + (size_t)kWin * kMaxDepthTiles;
-    unsigned long long* cls_acc = reinterpret_cast<unsigned long long*>(hdr + kClsAccOff);
-    WinTable* tab = reinterpret_cast<WinTable*>(hdr + kTableOff);
-    if (!st->open) {  // a window starts: its header (counters, frame table) and mask planes were the window's two before
-      if (st->n_windows >= 2 && hipStreamWaitEvent(cs, ov->fuse_done[par], 0) != hipSuccess) return fail(SAF_E_HIP, "hipStreamWaitEvent");
-      if (hipMemsetAsync(hdr, 0, kHdrBytes, cs) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(workspace header)");
+    if (st->open && st->filled >= pl.wlen && (rc = close_window(pl, ws, stats, s, ov, st, true))) return rc;
+    const int widx = st->n_windows;
+    const WinView v = win_view(ws, pl, widx & 1);
+    const TileView tv = tile_view(ws, pl, widx % kTileWindows);
+    if (!st->open) {  // a window starts
+      if ((rc = open_unit_header(v, ov, st->n_windows >= 2, cs))) return rc;
       st->open = true;
       st->filled = 0;
     }
-    const int fb = st->filled;  // a multiple of 32 (checked above / by the loop)
-    ClsArgs ca;
-    ca.n = n_frames - done < kClsFrames ? n_frames - done : kClsFrames;
-    if (fb + ca.n > pl.wlen) ca.n = pl.wlen - fb;
-    ca.H = kf0.H; ca.W = kf0.W; ca.slot = fb; ca.count = 1;
-    ca.guard_x = kf0.W <= 8192 ? (float)kf0.W * SAF_CLS_GUARD_EPS : 2.0f;
-    ca.guard_y = kf0.H <= 8192 ? (float)kf0.H * SAF_CLS_GUARD_EPS : 2.0f;
-    ca.mid_x = (float)(kf0.W - 1) * 0.5f; ca.mid_y = (float)(kf0.H - 1) * 0.5f;
-    ca.verify = stats ? reinterpret_cast<unsigned long long*>(stats) + 7 : nullptr;
-    ca.tiles_x8 = (kf0.W + (1 << SAF_CLS_TILE_WL2) - 1) >> SAF_CLS_TILE_WL2;
-    // (the session's first window has the chip to itself: it reads the frames' own images, as a call's first unit does)
-    const bool use_tiled = pl.tiled && (widx > 0 || (til_env && til_env[0] == '2'));
-    ca.depth_bytes = use_tiled ? (int)(pl.dpx * sizeof(float)) : kf0.H * kf0.W * 4;
-    for (int k = 0; k < kClsFrames; ++k) {
-      const saf_frame& fr = frames[done + (k < ca.n ? k : 0)];
-      ca.depth[k] = fr.depth; ca.rgb[k] = fr.rgb; ca.pose[k] = fr.pose; ca.K[k] = fr.K; ca.label_map[k] = fr.label_map;
-      ca.feat_map[k] = fr.feat_map;
-    }
-    float* dmax = dmax_w + fb;
-    float* tmax = tmax_w + (size_t)fb * kMaxDepthTiles;
-    float* tdepth = tdepth_w + (size_t)fb * pl.dpx;
+    FrameGroup g{frames, done, n_frames - done < kClsFrames ? n_frames - done : kClsFrames, st->filled};  // (fb: a multiple of 32 -- checked above / by the loop)
+    if (g.fb + g.n > pl.wlen) g.n = pl.wlen - g.fb;
     // this launch's depth tile maxima (and tiled copies), from the frames' own images
     if (!prepared) {
-      hipLaunchKernelGGL(depth_max_kernel, dim3((pl.n_tiles + 3) / 4, ca.n), dim3(256), 0, ts, ca, pl.ts_log2, pl.tiles_x, pl.n_tiles, tmax,
-                         pl.tiled ? tdepth : nullptr, ca.tiles_x8, (int)pl.dpx);
-      hipLaunchKernelGGL(depth_reduce_kernel, dim3(ca.n), dim3(256), 0, ts, tmax, pl.n_tiles, dmax);
+      launch_depth_tiles(pl, tv, g, ts);
       if (tile_stream && (hipEventRecord(ov->tiles, ts) != hipSuccess || hipStreamWaitEvent(cs, ov->tiles, 0) != hipSuccess))
         return fail(SAF_E_HIP, "session: could not order the classification behind its depth tiles");
     }
-    if (use_tiled)
-      for (int k = 0; k < kClsFrames; ++k) ca.depth[k] = tdepth + (size_t)(k < ca.n ? k : 0) * pl.dpx;
-    uint32_t* plane = masks + (size_t)(fb / kClsFrames) * pl.wl.mask_plane;
-    const uint32_t tx = ((uint32_t)kv.nx + 8 * kBrickX - 1) / (8 * kBrickX), ty = ((uint32_t)kv.ny + 8 * kBrickY - 1) / (8 * kBrickY);
-    const uint32_t nbz = ((uint32_t)kv.nz + kBrickZ - 1) / kBrickZ, cls_wgs = (tx * ty * 64u * nbz + 3u) / 4u;
-    auto kfn = use_tiled ? (verify ? (pl.sum ? classify_bricks_kernel<true, true, true> : classify_bricks_kernel<false, true, true>)
-                                   : (pl.sum ? classify_bricks_kernel<true, false, true> : classify_bricks_kernel<false, false, true>))
-                         : (verify ? (pl.sum ? classify_bricks_kernel<true, true, false> : classify_bricks_kernel<false, true, false>)
-                                   : (pl.sum ? classify_bricks_kernel<true, false, false> : classify_bricks_kernel<false, false, false>));
-    hipLaunchKernelGGL(kfn, dim3(cls_wgs), dim3(256), 0, cs, kv, ca, dmax, tmax, pl.ts_log2, pl.tiles_x, plane,
-                       reinterpret_cast<unsigned long long*>(stats), cls_acc, tab);
-    if ((rc = check_launch("classify_bricks_kernel"))) return rc;
-    st->filled += ca.n;
-    st->pushed += ca.n;
-    done += ca.n;
+    // (the session's first window has the chip to itself: it reads the frames' own images, as a call's first unit does)
+    const bool use_tiled = pl.tiled && (widx > 0 || pl.tiled_first);
+    if ((rc = launch_classify(pl, v, tv, kv, g, 1, use_tiled, stats, nullptr, cs))) return rc;
+    st->filled += g.n;
+    st->pushed += g.n;
+    done += g.n;
   }
   // a full window's row kernel follows at once: the launches of the next pushes run beside it
-  if (st->open && st->filled >= pl.wlen) rc = stream_close(workspace, workspace_bytes, stats, s, ov, st, true);
+  if (st->open && st->filled >= pl.wlen) rc = close_window(pl, ws, stats, s, ov, st, true);
   return rc;
 }
 

@@ -1105,6 +1105,42 @@ def test_deferred_window_queue_is_invisible(oracle, seem, fdt):
     assert que.pending_frames == 0 and int(que.weight.sum()) == 0
 
 
+@pytest.mark.parametrize("seem,fdt,dim", [(False, torch.float32, 512), (False, torch.float32, 256), (True, torch.bfloat16, 512)])
+def test_session_equals_one_bulk_call_in_the_default_form(seem, fdt, dim):
+    """The streaming session behind one-frame calls and one bulk call launch the same kernels with the same arguments over
+    the same window cuts (128 / 128 / 44 of 300 frames), in the DEFAULT (order-free) form too: every buffer bit for bit."""
+    from spatially_aware_ai_amd import ClipFusion, ClipSeemFusion
+
+    w, h, nvox, n_frames = 64, 48, (33, 30, 41), 300
+    npy, npx = syn.feature_map_shape(w, h)
+    grid = syn.make_grid(nvox, side=2.56 * nvox[0] / max(nvox))
+    frames = syn.make_frames(5151, n_frames, width=w, height=h, feat_dim=dim, npy=npy, npx=npx, depth_kind="B",
+                             missing_depth_frac=0.05)
+
+    def build(defer):
+        clip, seg = FakeClip(dim), FakeSeg()
+        if seem:
+            return ClipSeemFusion(grid.origin, grid.voxel_size, grid.nvox, grid.trunc, False, 10, 10, clip, seg,
+                                  keep_xyz_world=False, feat_dtype=fdt, defer_frames=defer).cuda()
+        return ClipFusion(grid.origin, grid.voxel_size, grid.nvox, grid.trunc, False, clip, None, 10, 10,
+                          keep_xyz_world=False, feat_dtype=fdt, defer_frames=defer).cuda()
+
+    que, bulk = build(True), build(False)
+    for f in frames:  # queued: one frame per call, no look before the end
+        que.integrate_features(f["depth"].cuda(), f["rgb"].cuda(), f["pose"].cuda(), f["K"].cuda(), f["feat"].cuda(),
+                               [f["labels"].float().cuda()] if seem else None)
+    assert que.pending_frames > 0
+    cat = lambda k: torch.cat([f[k] for f in frames]).cuda()
+    bulk.integrate_features(cat("depth"), cat("rgb"), cat("pose"), cat("K"), cat("feat"),
+                            [f["labels"].float().cuda() for f in frames] if seem else None)
+    for n in ("weight", "tsdf_weight", "tsdf", "rgb", "clip_feat") + (("labels_one_hot",) if seem else ()):
+        assert torch.equal(getattr(que, n), getattr(bulk, n)), f"{n} differs between the session and the bulk call"
+    sq, sb = que.stats(), bulk.stats()
+    assert sq["window_rows"] > 0 and sb["window_rows"] > 0, "both sides must reach the windowed path"
+    for k in ("valid", "tsdf_valid", "frames"):
+        assert sq[k] == sb[k], k
+
+
 def test_failed_flush_never_stages_past_the_ring_and_never_fuses_twice():
     """a flush that fails BEFORE any launch keeps its frames queued -- and a full ring then refuses
     further frames instead of staging into slot 512 (a device write past the ring); a flush that fails AFTER
