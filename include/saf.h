@@ -563,6 +563,93 @@ int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objec
                      float* rgb_mean /*[K,3]*/, float* feat_mean /*[K,D]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Rig front-end (added under ABI 6: additive, the version number stays; magicleap2_camera_match.py states the problem and the
+ * metadata layout, not this arithmetic -- its per-pixel loop has no occlusion test, its relative pose is not mirrored, and cv2's
+ * fixed-point remap is not in the build image: parity with it is unpinned).  A headset frame has a depth and a colour image from
+ * two cameras: two resolutions, two sets of intrinsics, a 5-coefficient lens distortion each, one pose each.  These calls take
+ * such frames to the one pinhole K and one pose per frame that saf_frame assumes.  fp32 throughout, one IEEE operation at a time
+ * in the order written here (tests/registration_reference.py restates it in NumPy).  The batch index b runs in the grid: one
+ * launch covers a batch (batch <= 65535).
+ *
+ *   camera   a HOST struct, copied into the kernel arguments.  dist = (k1, k2, p1, p2, k3), OpenCV's order (the five entries of
+ *            the headset's "Distortion"); no skew.  A "pinhole" camera below is one whose dist is IGNORED (taken as zeros).
+ *            pixel -> ray: x = (u - cx) / fx;  ray -> pixel: u = fx x + cx (one product, one sum).
+ *   D(x, y)  ideal -> distorted normalised coordinates:
+ *              r2 = x x + y y;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3))                        (innermost product first)
+ *              tx = (2 p1) (x y) + p2 (r2 + 2 (x x));  ty = p1 (r2 + 2 (y y)) + (2 p2) (x y)
+ *              xd = x rad + tx;  yd = y rad + ty
+ *   D^-1     exactly 8 fixed-point steps from (x, y) = (xd, yd): x <- (xd - tx(x, y)) / rad(x, y), y <- (yd - ty(x, y)) / rad(x, y),
+ *            both from the same (x, y).  The count is fixed so that the restatement can follow it.  rad <= 0 at any step, or a
+ *            non-finite (x, y) after the last, makes the pixel MISSING.  With all-zero coefficients D and D^-1 are the identity,
+ *            bit for bit.
+ *   T_d2c    [B,4,4] f32 in DEVICE memory, row-major: depth-camera coordinates -> colour-camera coordinates of frame b
+ *            (inv(pose_color) pose_depth for camera->world poses).  Q = R P + t per row as ((r0 Px + r1 Py) + r2 Pz) + t.
+ *   depth    raw (distorted) images hold camera z, the convention of saf_frame.depth; a value is PRESENT iff it is finite and > 0
+ *            (0, negative, NaN, +-inf are missing).
+ *
+ * saf_undistort_images: src [B,Hs,Ws,C] f32 channel-last (C = 3: rgb as the loaders yield it; C = 1: depth or label maps;
+ *   1 <= C <= 4) seen by cam_src -> dst [B,Hd,Wd,C] as the pinhole cam_dst sees it.  Output pixel (u, v): (x, y) = its ray in
+ *   cam_dst, (xd, yd) = D_src(x, y), (us, vs) = its pixel in cam_src.
+ *     interp 0  nearest: (rint(us), rint(vs)), half to even; 0 outside the image
+ *     interp 1  bilinear: cell (floor(us), floor(vs)), offsets us - floor(us), a + f (b - a) along u then along v; taps outside
+ *               the image contribute 0
+ *   Non-finite us / vs write 0.  Use nearest for depth and label maps: bilinear invents surfaces across depth edges and classes
+ *   between labels (the Python layer does).
+ *
+ * saf_depth_to_color: depth [B,Hd,Wd] raw, seen by cam_depth -> out_depth [B,Hc,Wc] camera z in the pinhole cam_color, 0 where
+ *   nothing lands.  A SCATTER: every present raw pixel (u, v) with depth z
+ *     (x, y) = D_depth^-1 of its ray (missing: skipped);  P = (x z, y z, z);  Q = T_d2c[b] P; skipped unless Q.z is finite and > 0
+ *     uc = fx_c (Q.x / Q.z) + cx_c, vc likewise (skipped unless finite)
+ *     hx = min((0.5 (fx_c / fx_d)) (z / Q.z), max_footprint / 2) + 1/32, hy likewise with fy: half the depth pixel's size in
+ *          colour pixels.  It ignores the rig's rotation and both lenses (a depth pixel at the rim of a strongly distorted image
+ *          is larger than this says)
+ *     it covers the integer colour pixels ceil(uc - hx) .. floor(uc + hx) x ceil(vc - hy) .. floor(vc + hy) inside the image
+ *   and every covered pixel keeps the smallest Q.z.  The closed interval and the 1/32 make neighbouring footprints overlap rather
+ *   than leave a gap; for an identity rig each pixel covers exactly itself even when uc is an ulp off an integer.  The minimum is an
+ *   atomicMin on the bit pattern of Q.z as an unsigned integer (positive floats order as their bits: order-free, two calls return
+ *   the same bytes) between a fill to +inf and a pass that writes 0 for +inf; the z-buffer is out_depth itself, so
+ *   saf_depth_to_color_workspace_bytes returns 0 and workspace may be NULL (kept in the signature for a form that needs one).
+ *   max_footprint: 1 .. 16 colour pixels (SAF_E_INVALID otherwise).  Why a splat and not a mesh of the depth image: a mesh
+ *   bridges depth edges with triangles no camera saw, and needs an edge threshold to cut them; a footprint never spans two source
+ *   pixels.  What it costs: a foreground edge is fattened by up to hx, and a magnification above max_footprint leaves gaps.
+ *
+ * saf_color_to_depth: the other direction (the reference script's).  A GATHER: output pixel (u, v) of the pinhole cam_depth_out
+ *     z = the nearest sample of the raw depth through D_depth, exactly saf_undistort_images with interp = 0;
+ *         out_depth[b,v,u] = z, 0 if missing
+ *     P = (x z, y z, z) on the pinhole ray (x, y) of (u, v);  Q = T_d2c[b] P;  (xq, yq) = (Q.x / Q.z, Q.y / Q.z)
+ *     (uc, vc) = the pixel of D_color(xq, yq) in cam_color; the raw colour image [B,Hc,Wc,3] is sampled there bilinearly (as
+ *         interp 1): ONE interpolation of the raw image, not the reference's two
+ *   VALID iff z is present, Q.z is finite and > 0, the cell lies inside the colour image (0 <= floor(uc) <= Wc - 2 and
+ *   0 <= floor(vc) <= Hc - 2) and, with a zbuf, Q.z - zb <= occlusion_tol (metres), where zb = zbuf[b] at the nearest pixel
+ *   (rint) of the pinhole projection (fx_z xq + cx_z, fy_z yq + cy_z); zb = 0 or a projection outside zbuf does not occlude.
+ *   zbuf [B,Hz,Wz] is an out_depth of saf_depth_to_color for the pinhole cam_zbuf; zbuf == NULL disables the test (cam_zbuf is
+ *   then not read).  out_rgb [B,Hd',Wd',3] is 0 where invalid; out_valid [B,Hd',Wd'] u8.
+ *   D_color is a polynomial: far outside the colour camera's field of view it can fold a point back into the image.  The
+ *   coefficients are taken to be valid over the depth camera's field of view; nothing here tests that.
+ *
+ * SAF_E_INVALID (on the host, nothing is launched) for NULL required pointers, non-positive sizes, a batch above 65535, channels
+ * outside 1 .. 4, interp other than 0 / 1, or a camera whose fx / fy is not finite and positive.  Every index is tested on the
+ * float before it is converted: any input (NaN, inf, 1e30, any T) stays in bounds.  One thread per source pixel (scatter) or
+ * output pixel (gathers); a wave owns an 8 x 8-pixel tile, so that its taps share lines.
+ */
+typedef struct saf_camera {
+  int32_t width, height;
+  float fx, fy, cx, cy;
+  float dist[5]; /* k1, k2, p1, p2, k3 */
+} saf_camera;
+
+int saf_undistort_images(const float* src, int32_t batch, int32_t channels, const saf_camera* cam_src, const saf_camera* cam_dst,
+                         int32_t interp, float* dst, void* stream);
+size_t saf_depth_to_color_workspace_bytes(int32_t batch, const saf_camera* cam_color);
+int saf_depth_to_color(const float* depth, const saf_camera* cam_depth, const float* T_d2c /*[B,4,4]*/, int32_t batch,
+                       const saf_camera* cam_color, int32_t max_footprint, float* out_depth, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int saf_color_to_depth(const float* depth, const saf_camera* cam_depth, const saf_camera* cam_depth_out,
+                       const float* T_d2c /*[B,4,4]*/, int32_t batch, const float* color, const saf_camera* cam_color,
+                       const float* zbuf, const saf_camera* cam_zbuf, float occlusion_tol, float* out_depth, float* out_rgb,
+                       uint8_t* out_valid, void* stream);
+
+/*
  * Marching cubes on the TSDF, on the device: the mesh half of extract_mesh (clipfusion.py:723-739,
  * clip_seem_fusion.py:824-842) -- un-fused voxels (weight == 0) act as the reference's NaN mask, faces with a vertex on
  * an edge to an un-fused voxel are dropped, unused vertices never exist.  Two calls, because the sizes are results:

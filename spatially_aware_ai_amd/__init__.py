@@ -24,6 +24,12 @@ __all__ = [
     "object_slots",
     "merge_objects",
     "mark_object_of_interest",
+    "registration",
+    "CameraModel",
+    "RgbdRig",
+    "RegisteredFrames",
+    "camera_from_meta",
+    "pose_from_meta",
 ]
 
 
@@ -36,12 +42,16 @@ def __getattr__(name):
         from . import clip_seem_fusion as _m
 
         return getattr(_m, name)
-    if name in ("evaluation", "objects"):
+    if name in ("evaluation", "objects", "registration"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
     if name in ("describe_objects", "object_slots", "merge_objects", "mark_object_of_interest", "ObjectDescriptors"):
         from . import objects as _m
+
+        return getattr(_m, name)
+    if name in ("CameraModel", "RgbdRig", "RegisteredFrames", "camera_from_meta", "pose_from_meta"):
+        from . import registration as _m
 
         return getattr(_m, name)
     raise AttributeError(name)

@@ -63,6 +63,18 @@ class SafFrame(C.Structure):
     ]
 
 
+class SafCamera(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("fx", C.c_float),
+        ("fy", C.c_float),
+        ("cx", C.c_float),
+        ("cy", C.c_float),
+        ("dist", C.c_float * 5),  # k1, k2, p1, p2, k3
+    ]
+
+
 # name -> (restype, argtypes); the exported symbols of libsaf_hip.so (include/saf.h)
 PROTOTYPES = {
     "saf_last_error": (C.c_char_p, []),
@@ -187,6 +199,17 @@ PROTOTYPES = {
     "saf_object_stats": (
         C.c_int,
         [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp],
+    ),
+    "saf_undistort_images": (C.c_int, [_fp, C.c_int32, C.c_int32, C.POINTER(SafCamera), C.POINTER(SafCamera), C.c_int32, _fp, _fp]),
+    "saf_depth_to_color_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(SafCamera)]),
+    "saf_depth_to_color": (
+        C.c_int,
+        [_fp, C.POINTER(SafCamera), _fp, C.c_int32, C.POINTER(SafCamera), C.c_int32, _fp, _fp, C.c_size_t, _fp],
+    ),
+    "saf_color_to_depth": (
+        C.c_int,
+        [_fp, C.POINTER(SafCamera), C.POINTER(SafCamera), _fp, C.c_int32, _fp, C.POINTER(SafCamera), _fp, C.POINTER(SafCamera),
+         C.c_float, _fp, _fp, _fp, _fp],
     ),
     "saf_label_components_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "saf_label_components": (
