@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SAF_ABI_VERSION 6
+#define SAF_ABI_VERSION 7
 
 enum saf_status {
   SAF_OK = 0,
@@ -182,7 +182,8 @@ int saf_fuse_path(const saf_volume* vol, const saf_frame* frames, int32_t n_fram
  * 32 at a time.  A separate saf_fuse_frames call per window exposes the window's whole classification (nothing of the call runs
  * beside it: 3.7 ms at 256^3) and cannot start before the window's last frame has arrived; a session keeps ONE pipeline:
  *   saf_fuse_session_ok      1 if a session takes these frames for this volume and workspace (what the windowed ROW forms take, on
- *                            two streams: SAF_WIN_OVERLAP != 0), 0 if not (use saf_fuse_frames), -1 for bad arguments.
+ *                            two streams: SAF_WIN_OVERLAP != 0, in windows of SAF_WINDOW_FRAMES frames: SAF_WIN_FRAMES unset), 0 if
+ *                            not (use saf_fuse_frames), -1 for bad arguments.
  *   saf_fuse_session_push    classifies the frames at once -- one launch (one mask plane of the open window) per 32 frames, on the
  *                            session's classification stream -- and, when a window (SAF_WINDOW_FRAMES) is complete, launches its row
  *                            kernel on `stream`: the launches of the following pushes run beside it.  Every push but a window's last
@@ -195,14 +196,19 @@ int saf_fuse_path(const saf_volume* vol, const saf_frame* frames, int32_t n_fram
  *                            `tile_stream` (a hipStream_t, may be NULL): the stream the frames were staged on (the one `ready_event`
  *                            was recorded on: with it the event itself is not waited for); the launches' depth tile maxima (two
  *                            small kernels per 32 frames) run there, behind the staging, instead of in the classification chain.  That stream must be ordered behind the row kernel of the window four windows back (the
- *                            tile region holds four windows: the host queue's staging ring has the same period).
+ *                            tile region holds four windows; with windows of SAF_WINDOW_FRAMES frames the host queue's staging
+ *                            ring of 4 x SAF_WINDOW_FRAMES slots has the same period.  With SAF_WIN_FRAMES=64 it has not -- the
+ *                            region turns over twice per turn of the ring -- and a session refuses: saf_fuse_session_ok is 0,
+ *                            push and prepare return SAF_E_UNSUPPORTED, and saf_fuse_frames cuts the shorter windows itself).
  *   saf_fuse_session_prepare (optional) the depth tile maxima of frames that will be pushed NEXT, in order, computed on `stream` (the one
  *                            they were staged on) a call ahead of their push: a `ready_event` recorded behind it has completed by the
  *                            time the frames are pushed, and the push then queues its launch with no cross-stream wait in front.
  *   saf_fuse_session_finish  launches the row kernel of the window that is still open; behind it (in stream order) the volume
  *                            holds every pushed frame, bit for bit as one saf_fuse_frames call over them leaves it.
  *   saf_fuse_session_abandon drops the open window without fusing its rows (the volume is being reset: its classification has
- *                            already updated the TSDF).  Launches nothing.
+ *                            updated the TSDF, or is still doing so).  Launches no kernel; `stream` (ABI version 7; any stream)
+ *                            waits for the session's classification stream, so that what the caller queues behind `stream` --
+ *                            zeroing the volume -- comes after the last store of the abandoned frames.
  *   saf_fuse_session_pending frames of the open window (0: none).
  * `stream`: the same stream for every call of a session (one of the host queue's own, so that the caller's stream can stage
  * later frames meanwhile).  Not thread-safe per session; sessions are independent of each other.
@@ -216,7 +222,7 @@ int saf_fuse_session_push(saf_fuse_session* session, const saf_volume* vol, cons
 int saf_fuse_session_prepare(saf_fuse_session* session, const saf_volume* vol, const saf_frame* frames, int32_t n_frames,
                              void* workspace, size_t workspace_bytes, void* stream);
 int saf_fuse_session_finish(saf_fuse_session* session, void* stream);
-int saf_fuse_session_abandon(saf_fuse_session* session);
+int saf_fuse_session_abandon(saf_fuse_session* session, void* stream);
 int saf_fuse_session_pending(const saf_fuse_session* session);
 void saf_fuse_session_destroy(saf_fuse_session* session);
 

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 SAF_OK = 0
 SAF_E_INVALID = -1
@@ -103,7 +103,7 @@ PROTOTYPES = {
     "saf_fuse_session_push": (C.c_int, [C.c_void_p, C.POINTER(SafVolume), C.POINTER(SafFrame), C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp, _fp]),
     "saf_fuse_session_prepare": (C.c_int, [C.c_void_p, C.POINTER(SafVolume), C.POINTER(SafFrame), C.c_int32, _fp, C.c_size_t, _fp]),
     "saf_fuse_session_finish": (C.c_int, [C.c_void_p, _fp]),
-    "saf_fuse_session_abandon": (C.c_int, [C.c_void_p]),
+    "saf_fuse_session_abandon": (C.c_int, [C.c_void_p, C.c_void_p]),
     "saf_fuse_session_pending": (C.c_int, [C.c_void_p]),
     "saf_fuse_session_destroy": (None, [C.c_void_p]),
     "saf_clear_unwritten_rows": (C.c_int, [C.POINTER(SafVolume), C.c_int64, C.c_int64, _fp]),

@@ -552,6 +552,12 @@ class _FusionVolumeMixin:
         if self._queue_busy() or self.__dict__.get("_feat_stale"):
             self._sync_volume()
         self._wait_for_queue()
+        # the session's classification stream and events belong to the device the module leaves (the flush above has joined them)
+        h = self.__dict__.get("_session")
+        if h:
+            lib().saf_fuse_session_destroy(h)
+        self.__dict__["_session"] = None
+        self.__dict__["_session_open"] = False
         self.__dict__["_stage"] = None
         self.__dict__["_fs"] = None  # (a stream of the old device)
         self.__dict__["_fs_event"] = None
@@ -688,7 +694,8 @@ class _FusionVolumeMixin:
     # -- extensions (not in the reference) ---------------------------------------------------
     def reset(self, accum_mode=_abi.SAF_RUNNING_MEAN, lazy=True):
         """Back to the freshly constructed state: every volume buffer zero (the reference builds a new module per
-        scan, clip_seem_fusion.py:291-302).  ``lazy``: the 4*D*N bytes of ``clip_feat`` are not cleared here -- a voxel
+        scan, clip_seem_fusion.py:291-302).  The counters of ``stats()`` go on counting over the scans of a module: a
+        caller who wants them per scan zeroes ``fuse_stats``.  ``lazy``: the 4*D*N bytes of ``clip_feat`` are not cleared here -- a voxel
         with weight 0 has a zero row by contract and the windowed fuse path never reads such rows; the rows still
         unwritten are zeroed when something first looks (any buffer access, state_dict, the merge, flush())."""
         self.__dict__["_pending_n"] = 0  # frames still queued would be fused into a volume that is being discarded
@@ -697,10 +704,12 @@ class _FusionVolumeMixin:
         b = self._buffers
         fs = self.__dict__.get("_fs")
         if fs is not None:
-            # a pushed window whose row kernel is still owed is dropped with the volume; what the queue's stream (and the
-            # library's classification stream behind it) already runs must finish before the buffers are zeroed here
+            # a pushed window whose row kernel is still owed is dropped with the volume; what the queue's stream and the
+            # library's classification stream already run must finish before the buffers are zeroed here: the abandon lets
+            # the queue's stream wait for the classification stream, the event recorded behind that wait covers both
             if self.__dict__.get("_session") is not None:
-                check(lib().saf_fuse_session_abandon(self.__dict__["_session"]), "saf_fuse_session_abandon")
+                with torch.cuda.device(b["tsdf"].device):
+                    check(lib().saf_fuse_session_abandon(self.__dict__["_session"], fs.cuda_stream), "saf_fuse_session_abandon")
             self.__dict__["_session_open"] = False
             ev = fs.record_event()
             self.__dict__["_fs_event"] = ev

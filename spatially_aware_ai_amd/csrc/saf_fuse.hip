@@ -1134,6 +1134,14 @@ struct saf_fuse_session {
 
 saf_fuse_session* saf_fuse_session_create(void) { return new saf_fuse_session; }
 
+// The settings a session runs under: two streams (SAF_WIN_OVERLAP != 0) and windows of SAF_WINDOW_FRAMES frames -- what the
+// caller's ring of frames is cut by (include/saf.h).  Under SAF_WIN_FRAMES=64 the tile region's four slots turn over every 256
+// frames, twice per turn of a 512-frame ring: saf_fuse_frames cuts its own windows there.
+static bool session_setting_ok() {
+  const char* ov = getenv("SAF_WIN_OVERLAP");
+  return !(ov && ov[0] == '0') && window_frames() == SAF_WINDOW_FRAMES;
+}
+
 static bool session_overlap(saf_fuse_session* ss, WinOverlap* ov) {
   if (!ss->pr && !(ss->pr = pipe_acquire())) return false;
   PipeRes* pr = ss->pr;
@@ -1146,7 +1154,7 @@ static bool session_overlap(saf_fuse_session* ss, WinOverlap* ov) {
 int saf_fuse_session_ok(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
   KVol kv;
   if (make_kvol(vol, &kv) || n_frames <= 0 || !frames) return -1;
-  if (getenv("SAF_WIN_OVERLAP") && getenv("SAF_WIN_OVERLAP")[0] == '0') return 0;
+  if (!session_setting_ok()) return 0;
   return stream_ok(kv, frames, n_frames, workspace_bytes) ? 1 : 0;
 }
 
@@ -1158,8 +1166,8 @@ int saf_fuse_session_push(saf_fuse_session* ss, const saf_volume* vol, const saf
   if (rc) return rc;
   if (n_frames <= 0 || !frames) return fail(SAF_E_INVALID, "bad frame array");
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  if (!stream_ok(kv, frames, n_frames, workspace_bytes) || (getenv("SAF_WIN_OVERLAP") && getenv("SAF_WIN_OVERLAP")[0] == '0'))
-    return fail(SAF_E_UNSUPPORTED, "a streaming session takes what the windowed row forms take on two streams (saf_fuse_session_ok)");
+  if (!stream_ok(kv, frames, n_frames, workspace_bytes) || !session_setting_ok())
+    return fail(SAF_E_UNSUPPORTED, "a streaming session takes what the windowed row forms take on two streams, in windows of %d frames (saf_fuse_session_ok)", SAF_WINDOW_FRAMES);
   if (ss->st.have_shape && (ss->feat != kv.feat || ss->workspace != workspace || ss->workspace_bytes != workspace_bytes || ss->stats != stats))
     return fail(SAF_E_INVALID, "a session continues on the same volume, workspace and counters: finish it first");
   if ((rc = poll_latch())) return rc;
@@ -1179,7 +1187,8 @@ int saf_fuse_session_prepare(saf_fuse_session* ss, const saf_volume* vol, const 
   if (rc) return rc;
   if (n_frames <= 0 || !frames) return fail(SAF_E_INVALID, "bad frame array");
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  if (!stream_ok(kv, frames, n_frames, workspace_bytes)) return fail(SAF_E_UNSUPPORTED, "saf_fuse_session_prepare: not a shape a session takes");
+  if (!stream_ok(kv, frames, n_frames, workspace_bytes) || !session_setting_ok())
+    return fail(SAF_E_UNSUPPORTED, "saf_fuse_session_prepare: not a shape or a setting a session takes (saf_fuse_session_ok)");
   return stream_prepare(kv, frames, n_frames, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &ss->st);
 }
 
@@ -1195,9 +1204,16 @@ int saf_fuse_session_finish(saf_fuse_session* ss, void* stream) {
   return rc;
 }
 
-int saf_fuse_session_abandon(saf_fuse_session* ss) {
+int saf_fuse_session_abandon(saf_fuse_session* ss, void* stream) {
   if (!ss) return fail(SAF_E_INVALID, "session is NULL");
   ss->st = WinStream();  // (the open window's classification ran -- TSDF and masks of a volume that is being discarded; no row kernel follows)
+  // ... or is still running: `stream` waits for the classification stream (close_window's cls_done join without the row kernel) --
+  // whoever zeroes the volume behind `stream` zeroes it behind the last TSDF store and counter update of the abandoned frames
+  if (ss->pr) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipEventRecord(ss->pr->join, ss->pr->aux) != hipSuccess || hipStreamWaitEvent(s, ss->pr->join, 0) != hipSuccess)
+      return fail(SAF_E_HIP, "session: could not order the stream behind the abandoned window's classification");
+  }
   return SAF_OK;
 }
 

@@ -1110,14 +1110,14 @@ int launch_mfma_blocks(int ft, const void* feats, int64_t n_rows, int64_t fstrid
   // bw: labels per block -- 64, or 32 where two 32-label tiles of this width do not fit the LDS (feat_dim 768 / 1024: round 6)
   for (int c0 = 0; c0 < L; c0 += bw) {
     const int lb = L - c0 < bw ? L - c0 : bw;
+    // (raw scores are final as a block stores them: the launch that holds column L - 1 -- the last column of ITS block -- writes
+    //  out_last; softmax and surgery take it from the finishing pass)
+    float* last = EPI == SAF_Q_SCORES && c0 + lb == L ? out_last : nullptr;
     int rc = launch_mfma<SAF_Q_SCORES>(ft, feats, n_rows, fstride, D, text + (int64_t)c0 * tstride, lb, tstride, scale, normalize,
-                                       wts ? wts + c0 : nullptr, out, nullptr, s, (int64_t)L, c0);
+                                       wts ? wts + c0 : nullptr, out, last, s, (int64_t)L, c0);
     if (rc) return rc;
   }
-  if (EPI == SAF_Q_SCORES) {
-    if (out_last) return fail(SAF_E_UNSUPPORTED, "query scan: out_last of a raw-score scan over more than 64 labels");
-    return SAF_OK;
-  }
+  if (EPI == SAF_Q_SCORES) return SAF_OK;
   int64_t blocks = (n_rows + 3) / 4;
   const int64_t cap = (int64_t)device_cus() * 16;
   if (blocks > cap) blocks = cap;

@@ -111,7 +111,7 @@ def _fake_volume(n=8, d=16, dtype=_abi.SAF_F32):
 
 def test_object_stats_rejects_bad_arguments_on_the_host():
     l = _lib.lib()
-    assert l.saf_abi_version() == 6 == _abi.ABI_VERSION
+    assert l.saf_abi_version() == 7 == _abi.ABI_VERSION
     P = 4096  # a non-NULL, 256-byte aligned stand-in: every call below returns before anything is launched
     call = lambda vol, slot=P, k=3, norm=_abi.SAF_NORM_L2, count=P, bbox=P, ws=P, wsb=1 << 20: l.saf_object_stats(
         ctypes.byref(vol) if vol is not None else None, slot, k, norm, count, None, None, bbox, None, None, P, ws, wsb, None)

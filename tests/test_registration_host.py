@@ -32,7 +32,7 @@ def test_prototypes_and_struct():
     for name in ("saf_undistort_images", "saf_depth_to_color_workspace_bytes", "saf_depth_to_color", "saf_color_to_depth"):
         assert hasattr(l, name) and name in _abi.PROTOTYPES
     assert ctypes.sizeof(_abi.SafCamera) == 2 * 4 + 4 * 4 + 5 * 4 and _abi.SafCamera.dist.offset == 24
-    assert l.saf_abi_version() == 6  # additive: the version does not move
+    assert l.saf_abi_version() == 7 == _abi.ABI_VERSION  # (these entries were additive under 6; 7: saf_fuse_session_abandon takes a stream)
     assert l.saf_depth_to_color_workspace_bytes(3, _cam()) == 0  # the z-buffer is out_depth itself
 
 
