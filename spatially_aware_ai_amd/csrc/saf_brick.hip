@@ -1163,14 +1163,12 @@ AuxLayout aux_layout(const KVol& kv, size_t avail) {
   a.parity_bytes = per_parity & ~(size_t)255;
   const size_t want = (size_t)nb + nb / 4 + 64, room = (a.parity_bytes - a.segs) / kSegBytes;
   a.cap = (uint32_t)(room < want ? room : want);
-  if (const char* e = getenv("SAF_BRICK_POOL_CAP")) {  // development / tests: a small pool drives bricks into the overflow list
-    const long c = atol(e);
-    if (c >= 0 && (uint32_t)c < a.cap) a.cap = (uint32_t)c;
-  }
   return a;
 }
-BrickPool make_pool(const KVol& kv, void* aux, size_t aux_bytes, int parity, int split, const float** cams) {
-  const AuxLayout a = aux_layout(kv, aux_bytes);
+BrickPool make_pool(const KVol& kv, void* aux, size_t aux_bytes, int parity, int split, const Knobs& kn, const float** cams) {
+  AuxLayout a = aux_layout(kv, aux_bytes);
+  // SAF_BRICK_POOL_CAP: a small pool drives bricks into the overflow list
+  if (kn.brick_pool_cap >= 0 && (uint32_t)kn.brick_pool_cap < a.cap) a.cap = (uint32_t)kn.brick_pool_cap;
   unsigned char* p = static_cast<unsigned char*>(aux) + cmax_bytes(kv.D) + (size_t)parity * a.parity_bytes;
   BrickPool pool;
   pool.segs = p + a.segs;
@@ -1186,24 +1184,12 @@ BrickPool make_pool(const KVol& kv, void* aux, size_t aux_bytes, int parity, int
 
 }  // namespace
 
-// The brick form takes every grid shape (partial bricks are masked) and every feat_dim that is a multiple of 64.  It is
-// the default for the feature widths the frame-ordered row kernel does not take (it wants whole 1 KiB pieces of a row:
-// feat_dim a multiple of 256 up to 1024, of 512 for bf16) -- those used to fall back to the per-frame pipeline -- and what
-// SAF_WIN_FORM=bricks (read per call) asks for; SAF_WIN_FORM=rows never uses it.
-bool brick_form_ok(const KVol& kv) {
-  const char* e = getenv("SAF_WIN_FORM");
-  if (e && e[0] == 'r') return false;
-  if (kv.D % 64 != 0 || kv.D > 8192) return false;
-  const uint32_t nbx = ((uint32_t)kv.nx + kBX - 1) / kBX, nby = ((uint32_t)kv.ny + kBY - 1) / kBY, nbz = ((uint32_t)kv.nz + kBZ - 1) / kBZ;
-  if (nbx >= 1024u || nby >= 1024u || nbz >= 1024u) return false;  // the brick code of a workgroup is three 10-bit fields
-  if (e && e[0] == 'b') return true;
-  const bool rows_take_it = kv.D % 256 == 0 && kv.D <= 1024 && (!kv.bf16 || kv.D % 512 == 0);
-  return !rows_take_it;
-}
-// SAF_BRICK_SPLIT=0 (read per call): no build kernel, the walk kernel builds every brick itself
-bool brick_split() {
-  const char* e = getenv("SAF_BRICK_SPLIT");
-  return !(e && e[0] == '0');
+// What the brick form takes: every feat_dim that is a multiple of 64 up to 8192, and every grid shape (partial bricks are
+// masked) with fewer than 1024 bricks along each axis -- the brick code of a workgroup is three 10-bit fields.  (Whether a call
+// USES it is fuse_route's business, saf_window.hip.)
+bool brick_form_takes(int D, int nx, int ny, int nz) {
+  const uint32_t nbx = ((uint32_t)nx + kBX - 1) / kBX, nby = ((uint32_t)ny + kBY - 1) / kBY, nbz = ((uint32_t)nz + kBZ - 1) / kBZ;
+  return brick_form_takes_width(D) && nbx < 1024u && nby < 1024u && nbz < 1024u;
 }
 
 // What saf_fuse_workspace_bytes reserves (it knows the number of voxels, not the grid's shape): room for the lists and a full
@@ -1217,9 +1203,10 @@ bool brick_aux_fits(const KVol& kv, size_t avail) { return aux_layout(kv, avail)
 // The build kernel of a window (after its classification, on the classification's stream): camera table, pool control
 // words, one workgroup per brick.
 int launch_brick_build(const KVol& kv, const WinArgs& wa, const WinTable* tab, size_t img_bytes, unsigned long long* stats,
-                       const uint32_t* hitmask, uint32_t mask_plane, void* aux, size_t aux_bytes, int parity, hipStream_t s) {
+                       const uint32_t* hitmask, uint32_t mask_plane, void* aux, size_t aux_bytes, int parity, const Knobs& kn,
+                       hipStream_t s) {
   const float* cams;
-  const BrickPool pool = make_pool(kv, aux, aux_bytes, parity, 1, &cams);
+  const BrickPool pool = make_pool(kv, aux, aux_bytes, parity, 1, kn, &cams);
   if (hipMemsetAsync(pool.ctl, 0, sizeof(BrickCtl), s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(brick pool control)");
   hipLaunchKernelGGL(cam_table_kernel, dim3(1), dim3(128), 0, s, tab, wa.F, const_cast<float*>(cams));
   const uint32_t grid = 8u * build_wgs_per_xcd(kv);
@@ -1233,10 +1220,11 @@ int launch_brick_build(const KVol& kv, const WinArgs& wa, const WinTable* tab, s
 
 int launch_fuse_bricks(const KVol& kv, const WinArgs& wa, const WinTable* tab, const float* map_imgs, size_t img_bytes,
                        unsigned long long* stats, unsigned int* ctr, const uint32_t* hitmask, uint32_t mask_plane,
-                       const unsigned long long* cls_acc, void* aux, size_t aux_bytes, int parity, int split, hipStream_t s) {
+                       const unsigned long long* cls_acc, void* aux, size_t aux_bytes, int parity, int split, const Knobs& kn,
+                       hipStream_t s) {
   uint32_t* cmax = static_cast<uint32_t*>(aux);
   const float* cams;
-  BrickPool pool = make_pool(kv, aux, aux_bytes, parity, split, &cams);
+  BrickPool pool = make_pool(kv, aux, aux_bytes, parity, split, kn, &cams);
   // the channels' largest magnitudes over this window's maps (the scales of the fixed-point sums)
   if (hipMemsetAsync(cmax, 0, cmax_bytes(kv.D), s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(channel maxima)");
   hipLaunchKernelGGL(chan_max_kernel, dim3((kv.D + 255) / 256, (wa.F + 7) / 8), dim3(256), 0, s, map_imgs,
@@ -1258,8 +1246,7 @@ int launch_fuse_bricks(const KVol& kv, const WinArgs& wa, const WinTable* tab, c
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));
   }
-  const int wgs_env = getenv("SAF_BRICK_WGS") ? atoi(getenv("SAF_BRICK_WGS")) : 0;
-  const uint32_t grid = (uint32_t)device_cus() * (uint32_t)(wgs_env > 0 ? wgs_env : 2);
+  const uint32_t grid = (uint32_t)device_cus() * (uint32_t)(kn.brick_wgs > 0 ? kn.brick_wgs : 2);
   if (split) {
     pool.split = 2;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kBThreads), lds, s, kv, wa, tab, map_imgs, (uint32_t)img_bytes, stats, ctr, hitmask,

@@ -692,7 +692,7 @@ FuseFn pick_rows(bool g64, bool lds, bool sum, bool bf16) {
 
 int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float* feat_map,
                 const unsigned long long* counts, const unsigned char* half, unsigned long long* stats,
-                const unsigned long long* sweep_done, unsigned long long sweep_target, bool shared_cus,
+                const unsigned long long* sweep_done, unsigned long long sweep_target, bool shared_cus, const Knobs& kn,
                 hipStream_t s) {
   const int D = kv.D, P = kf.npy * kf.npx;
   const bool bf16 = kv.bf16 != 0;
@@ -739,10 +739,9 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
   // ONE per CU is launched so that the other half of the registers, ~80 KB of LDS and 16 wave slots
   // stay free for four sweep blocks of the next frame: both kernels are then resident on every CU
   // and neither can starve the other at dispatch.
-  const int grid_env = getenv("SAF_FUSE_GRID") ? atoi(getenv("SAF_FUSE_GRID")) : 0;
   // one workgroup per CU is enough in-flight rows to saturate HBM (alone: 276 us with 208..256
   // workgroups, 286 us with 512); in the pipeline 13/16 of the CUs (208 on MI355X) measured best
-  int grid = grid_env > 0 ? grid_env : (shared_cus ? (device_cus() * 13) / 16 : device_cus());
+  int grid = kn.fuse_grid > 0 ? kn.fuse_grid : (shared_cus ? (device_cus() * 13) / 16 : device_cus());
   grid = ((grid + kNumLists - 1) / kNumLists) * kNumLists;
   const uint32_t* lists = reinterpret_cast<const uint32_t*>(half + w.lists_off);
   const float* map_t = reinterpret_cast<const float*>(half + w.map_off);
@@ -832,12 +831,12 @@ int launch_classify(const KVol& kv, const FrameJob& job, unsigned char* ws, unsi
 }
 
 int launch_rows(const KVol& kv, const FrameJob& job, unsigned char* ws, unsigned char* buf, int64_t frame_no,
-                uint64_t* stats, bool shared_cus, saf_profiler* prof, hipStream_t s) {
+                uint64_t* stats, bool shared_cus, const Knobs& kn, saf_profiler* prof, hipStream_t s) {
   ScopedPair t(prof, 2, frame_no, s);
   // the fuse kernel starts once the sweeps of frames 0..frame_no have published all their blocks
   const unsigned long long target = (unsigned long long)(frame_no + 1) * job.w.n_blocks;
   return launch_fuse(kv, job.kf, job.w, job.feat_map, counter_set(ws, frame_no), buf,
-                     reinterpret_cast<unsigned long long*>(stats), sweep_done_ptr(ws), target, shared_cus, s);
+                     reinterpret_cast<unsigned long long*>(stats), sweep_done_ptr(ws), target, shared_cus, kn, s);
 }
 
 // The auxiliary stream and events of the two-stream pipeline are pooled per device (creating and destroying
@@ -854,7 +853,7 @@ struct PipeRes {
 std::mutex g_pipe_mu;
 PipeRes* g_pipe_free = nullptr;
 
-PipeRes* pipe_acquire() {
+PipeRes* pipe_acquire(const Knobs& kn) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
   {
@@ -870,11 +869,10 @@ PipeRes* pipe_acquire() {
   PipeRes* r = new PipeRes();
   r->device = dev;
   r->next = nullptr;
-  // SAF_CLS_PRIORITY=1 (read when a device's first pipeline is made; development): the classification stream at the device's
-  // highest priority -- its launches run beside the row kernel AND, behind integrate(), beside the staging of later frames
+  // SAF_CLS_PRIORITY=1 (as the call that makes a device's first pipeline reads it; development): the classification stream at the
+  // device's highest priority -- its launches run beside the row kernel AND, behind integrate(), beside the staging of later frames
   int lo_pri = 0, hi_pri = 0;
-  const char* pe = getenv("SAF_CLS_PRIORITY");
-  const bool pri = pe && atoi(pe) != 0 && hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) == hipSuccess;
+  const bool pri = kn.cls_priority && hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) == hipSuccess;
   bool ok = (pri ? hipStreamCreateWithPriority(&r->aux, hipStreamNonBlocking, hi_pri) : hipStreamCreateWithFlags(&r->aux, hipStreamNonBlocking)) == hipSuccess &&
             hipEventCreateWithFlags(&r->fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&r->join, hipEventDisableTiming) == hipSuccess &&
@@ -890,6 +888,14 @@ void pipe_release(PipeRes* r) {
   std::lock_guard<std::mutex> lk(g_pipe_mu);
   r->next = g_pipe_free;
   g_pipe_free = r;
+}
+// a pipeline's stream and events as the windowed path names them
+WinOverlap overlap_of(const PipeRes* pr) {
+  WinOverlap ov;
+  ov.aux = pr->aux; ov.fork = pr->fork; ov.join = pr->join;
+  ov.cls_done[0] = pr->fused[0]; ov.cls_done[1] = pr->fused[1]; ov.fuse_done[0] = pr->fused[2]; ov.fuse_done[1] = pr->fused[3];
+  ov.tiles = pr->tiles;
+  return ov;
 }
 
 // Host side of the asynchronous error latch (see g_async_latch): one mapped pinned word per device.
@@ -928,6 +934,22 @@ int poll_latch() {
   return SAF_OK;
 }
 
+// What the fusion entry points start with, in two halves (what lies between them differs from entry to entry, and the order of
+// the checks decides which error a bad call reports): the volume and the frame array -- min_frames: 0 where an empty call is
+// allowed --, and the latch of the calls before.
+int fuse_entry(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, int min_frames, KVol* kv) {
+  int rc = make_kvol(vol, kv);
+  if (rc) return rc;
+  if (n_frames < min_frames || (n_frames > 0 && !frames)) return fail(SAF_E_INVALID, "bad frame array");
+  return SAF_OK;
+}
+int latch_entry() {
+  int rc = poll_latch();
+  if (rc) return rc;
+  ensure_latch();
+  return SAF_OK;
+}
+
 #define SAF_HIP_TRY(call)                                                                  \
   do {                                                                                     \
     hipError_t e_ = (call);                                                                \
@@ -944,41 +966,38 @@ int poll_latch() {
 // Everything is ordered after what the caller already queued on `s` (fork event), and complete,
 // as far as `s` is concerned, when the last fuse kernel is (it has waited for every sweep).
 int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
-              uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinSlabs* slabs = nullptr, bool recycled = false) {
+              uint64_t* stats, saf_profiler* prof, hipStream_t s, const Knobs& kn, const WinSlabs* slabs = nullptr, bool recycled = false) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  if (recycled && !window_ok(kv, frames, n_frames, workspace_bytes)) {
+  const bool windowed = fuse_route(kv, frames, n_frames, workspace_bytes, kn).path != kPathPerFrame;
+  if (recycled && !windowed) {
     // the per-frame pipeline reads every row it updates: the rows of weight-0 voxels are zeroed first (of the slabs, if the
     // call names slabs: voxels outside them are not this call's)
     if (slabs && slabs->n > 0) {
       for (int k = 0; k < slabs->n; ++k) {
-        if (slabs->x0[k] < 0 || slabs->nx[k] <= 0 || slabs->x0[k] + slabs->nx[k] > kv.nx) return fail(SAF_E_INVALID, "slab %d outside the volume", k);
-        if ((rc = launch_clear_unwritten(slab_kvol(kv, slabs->x0[k], slabs->nx[k]), nullptr, 0, 0, s))) return rc;
+        if ((rc = check_slab(kv, *slabs, k))) return rc;
+        if ((rc = launch_clear_unwritten(slab_kvol(kv, slabs->x0[k], slabs->nx[k]), nullptr, 0, 0, kn, s))) return rc;
       }
-    } else if ((rc = launch_clear_unwritten(kv, nullptr, 0, 0, s))) {
+    } else if ((rc = launch_clear_unwritten(kv, nullptr, 0, 0, kn, s))) {
       return rc;
     }
     recycled = false;
   }
-  if (window_ok(kv, frames, n_frames, workspace_bytes)) {
-    // SAF_WIN_OVERLAP=0: every kernel of the windowed path on the caller's stream (read per call: same-process A/Bs)
+  if (windowed) {
+    // SAF_WIN_OVERLAP=0: every kernel of the windowed path on the caller's stream (same-process A/Bs)
     // (a call of one window overlaps too: its first window is classified slab by slab beside its own row kernels)
-    const char* ov_env = getenv("SAF_WIN_OVERLAP");
-    PipeRes* pr = (ov_env && ov_env[0] == '0') ? nullptr : pipe_acquire();
-    if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, nullptr, slabs, recycled);
-    WinOverlap ov;
-    ov.aux = pr->aux; ov.fork = pr->fork; ov.join = pr->join;
-    ov.cls_done[0] = pr->fused[0]; ov.cls_done[1] = pr->fused[1]; ov.fuse_done[0] = pr->fused[2]; ov.fuse_done[1] = pr->fused[3];
-    ov.tiles = pr->tiles;
-    rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, &ov, slabs, recycled);
+    PipeRes* pr = kn.win_overlap ? pipe_acquire(kn) : nullptr;
+    if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, nullptr, kn, slabs, recycled);
+    const WinOverlap ov = overlap_of(pr);
+    rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, &ov, kn, slabs, recycled);
     pipe_release(pr);
     return rc;
   }
   if (slabs && slabs->n > 0) {  // the per-frame pipeline, slab after slab (every (slab, frame) pair counts as a frame in stats[2])
     for (int k = 0; k < slabs->n; ++k) {
-      if (slabs->x0[k] < 0 || slabs->nx[k] <= 0 || slabs->x0[k] + slabs->nx[k] > kv.nx) return fail(SAF_E_INVALID, "slab %d outside the volume", k);
-      if ((rc = fuse_many(slab_kvol(kv, slabs->x0[k], slabs->nx[k]), frames, n_frames, workspace, workspace_bytes, stats, prof, s))) return rc;
+      if ((rc = check_slab(kv, *slabs, k))) return rc;
+      if ((rc = fuse_many(slab_kvol(kv, slabs->x0[k], slabs->nx[k]), frames, n_frames, workspace, workspace_bytes, stats, prof, s, kn))) return rc;
       if (slabs->done && slabs->done[k] && hipEventRecord(static_cast<hipEvent_t>(slabs->done[k]), s) != hipSuccess)
         return fail(SAF_E_HIP, "hipEventRecord(slab done)");
     }
@@ -987,18 +1006,17 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
   // counters and the completion counter start at zero; afterwards every sweep zeroes its successor's set
   if (hipMemsetAsync(ws, 0, kHdrBytes, s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(workspace header)");
   // SAF_PIPELINE=0 keeps everything on the caller's stream (debugging / per-kernel timing)
-  const bool pipeline = !(getenv("SAF_PIPELINE") && getenv("SAF_PIPELINE")[0] == '0');
-  if (n_frames == 1 || !pipeline) {
+  if (n_frames == 1 || !kn.pipeline) {
     for (int32_t i = 0; i < n_frames; ++i) {
       FrameJob job;
       if ((rc = make_job(kv, &frames[i], workspace, workspace_bytes, &job))) return rc;
       unsigned char* buf = ws + kHdrBytes;
       if ((rc = launch_classify(kv, job, ws, buf, i, prof, s))) return rc;
-      if ((rc = launch_rows(kv, job, ws, buf, i, stats, false, prof, s))) return rc;
+      if ((rc = launch_rows(kv, job, ws, buf, i, stats, false, kn, prof, s))) return rc;
     }
     return SAF_OK;
   }
-  PipeRes* pr = pipe_acquire();
+  PipeRes* pr = pipe_acquire(kn);
   if (!pr) return fail(SAF_E_HIP, "could not create the sweep stream / events of the per-frame pipeline");
   hipStream_t aux = pr->aux;
   SAF_HIP_TRY(hipEventRecord(pr->fork, s));
@@ -1014,7 +1032,7 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
       SAF_HIP_TRY(hipStreamWaitEvent(aux, pr->fused[(j >> 1) % kEvRing], 0));
     }
     if ((rc = launch_classify(kv, job, ws, buf, i, prof, aux))) goto done;
-    if ((rc = launch_rows(kv, job, ws, buf, i, stats, true, prof, s))) goto done;
+    if ((rc = launch_rows(kv, job, ws, buf, i, stats, true, kn, prof, s))) goto done;
     if (i & 1) SAF_HIP_TRY(hipEventRecord(pr->fused[(i >> 1) % kEvRing], s));
   }
 done:
@@ -1038,10 +1056,7 @@ int saf_abi_version(void) { return SAF_ABI_VERSION; }
 
 size_t saf_fuse_workspace_bytes(int64_t n_vox, int32_t feat_dim, int32_t npy, int32_t npx) {
   if (n_vox <= 0 || feat_dim <= 0 || npy <= 0 || npx <= 0) return 0;
-  // without the volume's dtype: room for the brick form wherever SOME dtype of this width would take it
-  const char* e = getenv("SAF_WIN_FORM");
-  const bool rows_always = feat_dim % 512 == 0 && feat_dim <= 1024;  // f32 and bf16 volumes both take the row kernel
-  const bool bricks = feat_dim % 64 == 0 && feat_dim <= 8192 && !(e && (e[0] == 'r' || e[0] == 's')) && (!rows_always || (e && e[0] == 'b'));
+  const bool bricks = brick_form_sized_for(feat_dim, read_knobs());
   const size_t a = ws_layout(n_vox, feat_dim, npy * npx).total, b = window_workspace_bytes(n_vox, feat_dim, npy * npx, bricks);
   return a > b ? a : b;
 }
@@ -1049,7 +1064,7 @@ size_t saf_fuse_workspace_bytes(int64_t n_vox, int32_t feat_dim, int32_t npy, in
 size_t saf_fuse_workspace_bytes_for(const saf_volume* vol, int32_t npy, int32_t npx) {
   KVol kv;
   if (!vol || npy <= 0 || npx <= 0 || make_kvol(vol, &kv)) return 0;
-  const size_t a = ws_layout(kv.N, kv.D, npy * npx).total, b = window_workspace_bytes(kv.N, kv.D, npy * npx, brick_form_ok(kv));
+  const size_t a = ws_layout(kv.N, kv.D, npy * npx).total, b = window_workspace_bytes(kv.N, kv.D, npy * npx, brick_form_applies(kv, read_knobs()));
   return a > b ? a : b;
 }
 
@@ -1057,56 +1072,52 @@ size_t saf_fuse_workspace_bytes_for_frames(const saf_volume* vol, int32_t npy, i
   KVol kv;
   if (!vol || npy <= 0 || npx <= 0 || height <= 0 || width <= 0 || make_kvol(vol, &kv)) return 0;
   const size_t a = ws_layout(kv.N, kv.D, npy * npx).total;
-  const size_t b = window_workspace_bytes(kv.N, kv.D, npy * npx, brick_form_ok(kv), height, width, kv.labels != nullptr);
+  const size_t b = window_workspace_bytes(kv.N, kv.D, npy * npx, brick_form_applies(kv, read_knobs()), height, width, kv.labels != nullptr);
   return a > b ? a : b;
 }
 
 int saf_fuse_frames_profiled(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
                              size_t workspace_bytes, uint64_t* stats, saf_profiler* profiler, void* stream) {
   KVol kv;
-  int rc = make_kvol(vol, &kv);
+  int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
   if (rc) return rc;
-  if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(SAF_E_INVALID, "bad frame array");
   if (n_frames == 0) return SAF_OK;
-  if ((rc = poll_latch())) return rc;
-  ensure_latch();
-  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, static_cast<hipStream_t>(stream));
+  if ((rc = latch_entry())) return rc;
+  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, static_cast<hipStream_t>(stream), read_knobs());
 }
 
 int saf_fuse_frames_recycled(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
                              size_t workspace_bytes, uint64_t* stats, saf_profiler* profiler, void* stream) {
   KVol kv;
-  int rc = make_kvol(vol, &kv);
+  int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
   if (rc) return rc;
-  if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(SAF_E_INVALID, "bad frame array");
-  if ((rc = poll_latch())) return rc;
-  ensure_latch();
-  if (n_frames == 0) return launch_clear_unwritten(kv, nullptr, 0, 0, static_cast<hipStream_t>(stream));
-  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, static_cast<hipStream_t>(stream), nullptr, true);
+  if ((rc = latch_entry())) return rc;
+  const Knobs kn = read_knobs();
+  if (n_frames == 0) return launch_clear_unwritten(kv, nullptr, 0, 0, kn, static_cast<hipStream_t>(stream));
+  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, static_cast<hipStream_t>(stream), kn, nullptr, true);
 }
 
 int saf_fuse_frames_slabs(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, const int32_t* slab_x0,
                           const int32_t* slab_nx, int32_t n_slabs, void* const* slab_done_events, int32_t recycled,
                           void* workspace, size_t workspace_bytes, uint64_t* stats, saf_profiler* profiler, void* stream) {
   KVol kv;
-  int rc = make_kvol(vol, &kv);
+  int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
   if (rc) return rc;
-  if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(SAF_E_INVALID, "bad frame array");
   if (n_slabs <= 0 || !slab_x0 || !slab_nx) return fail(SAF_E_INVALID, "bad slab list");
-  if ((rc = poll_latch())) return rc;
-  ensure_latch();
+  if ((rc = latch_entry())) return rc;
+  const Knobs kn = read_knobs();
   const WinSlabs sl{n_slabs, slab_x0, slab_nx, slab_done_events};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_frames == 0) {  // nothing to fuse: a recycled volume's slabs are cleared, every event is recorded
     for (int k = 0; k < n_slabs; ++k) {
-      if (slab_x0[k] < 0 || slab_nx[k] <= 0 || slab_x0[k] + slab_nx[k] > kv.nx) return fail(SAF_E_INVALID, "slab %d outside the volume", k);
-      if (recycled && (rc = launch_clear_unwritten(slab_kvol(kv, slab_x0[k], slab_nx[k]), nullptr, 0, 0, s))) return rc;
+      if ((rc = check_slab(kv, sl, k))) return rc;
+      if (recycled && (rc = launch_clear_unwritten(slab_kvol(kv, slab_x0[k], slab_nx[k]), nullptr, 0, 0, kn, s))) return rc;
       if (slab_done_events && slab_done_events[k] && hipEventRecord(static_cast<hipEvent_t>(slab_done_events[k]), s) != hipSuccess)
         return fail(SAF_E_HIP, "hipEventRecord(slab done)");
     }
     return SAF_OK;
   }
-  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, s, &sl, recycled != 0);
+  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, profiler, s, kn, &sl, recycled != 0);
 }
 
 int saf_fuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
@@ -1134,62 +1145,49 @@ struct saf_fuse_session {
 
 saf_fuse_session* saf_fuse_session_create(void) { return new saf_fuse_session; }
 
-// The settings a session runs under: two streams (SAF_WIN_OVERLAP != 0) and windows of SAF_WINDOW_FRAMES frames -- what the
-// caller's ring of frames is cut by (include/saf.h).  Under SAF_WIN_FRAMES=64 the tile region's four slots turn over every 256
-// frames, twice per turn of a 512-frame ring: saf_fuse_frames cuts its own windows there.
-static bool session_setting_ok() {
-  const char* ov = getenv("SAF_WIN_OVERLAP");
-  return !(ov && ov[0] == '0') && window_frames() == SAF_WINDOW_FRAMES;
-}
-
-static bool session_overlap(saf_fuse_session* ss, WinOverlap* ov) {
-  if (!ss->pr && !(ss->pr = pipe_acquire())) return false;
-  PipeRes* pr = ss->pr;
-  ov->aux = pr->aux; ov->fork = pr->fork; ov->join = pr->join;
-  ov->cls_done[0] = pr->fused[0]; ov->cls_done[1] = pr->fused[1]; ov->fuse_done[0] = pr->fused[2]; ov->fuse_done[1] = pr->fused[3];
-  ov->tiles = pr->tiles;
+static bool session_overlap(saf_fuse_session* ss, const Knobs& kn, WinOverlap* ov) {
+  if (!ss->pr && !(ss->pr = pipe_acquire(kn))) return false;
+  *ov = overlap_of(ss->pr);
   return true;
 }
 
 int saf_fuse_session_ok(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
   KVol kv;
   if (make_kvol(vol, &kv) || n_frames <= 0 || !frames) return -1;
-  if (!session_setting_ok()) return 0;
-  return stream_ok(kv, frames, n_frames, workspace_bytes) ? 1 : 0;
+  return fuse_route(kv, frames, n_frames, workspace_bytes, read_knobs()).session ? 1 : 0;
 }
 
 int saf_fuse_session_push(saf_fuse_session* ss, const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
                           size_t workspace_bytes, uint64_t* stats, void* stream, void* ready_event, void* tile_stream) {
   if (!ss) return fail(SAF_E_INVALID, "session is NULL");
   KVol kv;
-  int rc = make_kvol(vol, &kv);
+  int rc = fuse_entry(vol, frames, n_frames, 1, &kv);
   if (rc) return rc;
-  if (n_frames <= 0 || !frames) return fail(SAF_E_INVALID, "bad frame array");
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  if (!stream_ok(kv, frames, n_frames, workspace_bytes) || !session_setting_ok())
+  const Knobs kn = read_knobs();
+  if (!fuse_route(kv, frames, n_frames, workspace_bytes, kn).session)
     return fail(SAF_E_UNSUPPORTED, "a streaming session takes what the windowed row forms take on two streams, in windows of %d frames (saf_fuse_session_ok)", SAF_WINDOW_FRAMES);
   if (ss->st.have_shape && (ss->feat != kv.feat || ss->workspace != workspace || ss->workspace_bytes != workspace_bytes || ss->stats != stats))
     return fail(SAF_E_INVALID, "a session continues on the same volume, workspace and counters: finish it first");
-  if ((rc = poll_latch())) return rc;
-  ensure_latch();
+  if ((rc = latch_entry())) return rc;
   WinOverlap ov;
-  if (!session_overlap(ss, &ov)) return fail(SAF_E_HIP, "could not create the classification stream / events of a session");
+  if (!session_overlap(ss, kn, &ov)) return fail(SAF_E_HIP, "could not create the classification stream / events of a session");
   ss->feat = kv.feat; ss->workspace = workspace; ss->workspace_bytes = workspace_bytes; ss->stats = stats;
   return stream_push(kv, frames, n_frames, workspace, workspace_bytes, stats, static_cast<hipStream_t>(stream),
-                     static_cast<hipEvent_t>(ready_event), static_cast<hipStream_t>(tile_stream), &ov, &ss->st);
+                     static_cast<hipEvent_t>(ready_event), static_cast<hipStream_t>(tile_stream), &ov, kn, &ss->st);
 }
 
 int saf_fuse_session_prepare(saf_fuse_session* ss, const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
                              size_t workspace_bytes, void* stream) {
   if (!ss) return fail(SAF_E_INVALID, "session is NULL");
   KVol kv;
-  int rc = make_kvol(vol, &kv);
+  int rc = fuse_entry(vol, frames, n_frames, 1, &kv);
   if (rc) return rc;
-  if (n_frames <= 0 || !frames) return fail(SAF_E_INVALID, "bad frame array");
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  if (!stream_ok(kv, frames, n_frames, workspace_bytes) || !session_setting_ok())
+  const Knobs kn = read_knobs();
+  if (!fuse_route(kv, frames, n_frames, workspace_bytes, kn).session)
     return fail(SAF_E_UNSUPPORTED, "saf_fuse_session_prepare: not a shape or a setting a session takes (saf_fuse_session_ok)");
-  return stream_prepare(kv, frames, n_frames, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &ss->st);
+  return stream_prepare(kv, frames, n_frames, workspace, workspace_bytes, static_cast<hipStream_t>(stream), kn, &ss->st);
 }
 
 int saf_fuse_session_finish(saf_fuse_session* ss, void* stream) {
@@ -1197,8 +1195,9 @@ int saf_fuse_session_finish(saf_fuse_session* ss, void* stream) {
   int rc = SAF_OK;
   WinOverlap ov;
   if (ss->st.open && ss->st.filled > 0) {
-    if (!session_overlap(ss, &ov)) return fail(SAF_E_HIP, "could not create the classification stream / events of a session");
-    rc = stream_close(ss->workspace, ss->workspace_bytes, ss->stats, static_cast<hipStream_t>(stream), &ov, &ss->st, false);
+    const Knobs kn = read_knobs();
+    if (!session_overlap(ss, kn, &ov)) return fail(SAF_E_HIP, "could not create the classification stream / events of a session");
+    rc = stream_close(ss->workspace, ss->workspace_bytes, ss->stats, static_cast<hipStream_t>(stream), &ov, kn, &ss->st, false);
   }
   ss->st = WinStream();  // the next push starts a new pipeline (its first window's classification alone on the chip)
   return rc;
@@ -1228,7 +1227,7 @@ void saf_fuse_session_destroy(saf_fuse_session* ss) {
 int saf_fuse_path(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
   KVol kv;
   if (make_kvol(vol, &kv) || n_frames <= 0 || !frames) return -1;
-  return window_ok(kv, frames, n_frames, workspace_bytes) ? 1 : 0;
+  return fuse_route(kv, frames, n_frames, workspace_bytes, read_knobs()).path != kPathPerFrame ? 1 : 0;
 }
 
 saf_profiler* saf_profiler_create(int32_t capacity_pairs) {

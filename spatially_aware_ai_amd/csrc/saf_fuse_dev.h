@@ -287,8 +287,28 @@ struct ScopedPair {
 
 // the windowed path (saf_window.hip), called by saf_fuse_frames
 size_t window_workspace_bytes(int64_t n_vox, int D, int P, bool bricks, int H = 0, int W = 0, bool labels = false);
-int window_frames();  // frames per window of this call (SAF_WINDOW_FRAMES, or 64 with SAF_WIN_FRAMES=64)
-bool window_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes);
+// ---- The route of a fusion call: the ONE statement of which path takes it (fuse_route, saf_window.hip).  saf_fuse_path,
+// saf_fuse_session_ok, the session entries, fuse_many, win_plan and the three saf_fuse_workspace_bytes* entries ask these
+// functions and own no rule of their own.
+enum FusePath {
+  kPathPerFrame = 0,  // the per-frame pipeline (saf_fuse.hip)
+  kPathRows,          // windowed: the frame-ordered row kernel (bit-identical to fusing frame after frame)
+  kPathSums,          // windowed: the order-free row kernel (a row's samples of the window summed in registers, one blend per row)
+  kPathBricks,        // windowed: the brick form (saf_brick.hip)
+};
+struct FuseRoute {
+  FusePath path;  // what saf_fuse_frames (and _recycled, _slabs) does with the call
+  bool session;   // a streaming session takes these frames (saf_fuse_session_ok)
+};
+FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn);
+// The two width rules.  The row kernels move whole 1 KiB pieces of a row per wave instruction: feat_dim a multiple of 256 up to
+// 1024 -- of 512 for bf16, where a lane moves 8 channels.  The brick form: brick_form_takes (saf_window_dev.h).
+inline bool row_kernel_takes(int D, bool bf16) { return D % 256 == 0 && D <= 1024 && (!bf16 || D % 512 == 0); }
+// Whether a call on such a volume asks for the brick form (it gets it where the workspace has room for its pools): the default
+// for the widths the row kernel does not take, what SAF_WIN_FORM=bricks asks for, never under SAF_WIN_FORM=rows.
+bool brick_form_applies(const KVol& kv, const Knobs& kn);
+// ... and whether a workspace sized WITHOUT the volume (saf_fuse_workspace_bytes: a width, no dtype, no grid) holds the pools
+bool brick_form_sized_for(int D, const Knobs& kn);
 // Streams / events for running the classification of window w + 1 beside the row kernel of window w (may be NULL:
 // everything on the caller's stream).
 struct WinOverlap {
@@ -315,25 +335,30 @@ struct WinStream {
   long long prepared = 0;   // frames whose depth tiles are computed (stream_prepare runs ahead of stream_push: >= pushed, or behind it when unused)
 };
 int stream_prepare(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes, hipStream_t ts,
-                   WinStream* st);
-bool stream_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes);
+                   const Knobs& kn, WinStream* st);
 int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes, uint64_t* stats,
-                hipStream_t s, hipEvent_t ready, hipStream_t tile_stream, const WinOverlap* ov, WinStream* st);
-int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen);
+                hipStream_t s, hipEvent_t ready, hipStream_t tile_stream, const WinOverlap* ov, const Knobs& kn, WinStream* st);
+int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, const Knobs& kn, WinStream* st,
+                 bool preopen);
 // recycled: the volume's feature rows were not cleared when its scalars were (saf_fuse_frames_recycled) -- the rows of voxels
 // whose weight is still 0 when the call is over are zeroed by it, beside the last window's row kernel where the schedule allows.
 int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
-                       uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const WinSlabs* slabs = nullptr,
-                       bool recycled = false);
+                       uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const Knobs& kn,
+                       const WinSlabs* slabs = nullptr, bool recycled = false);
 // saf_misc.hip (clear_rows): zero the feature rows of the voxels n in [0, kv.N) with weight[n] == 0 and -- masks may be NULL -- no
 // bit set in masks[p * mask_plane + n] for p < n_planes (the hit masks of a window whose row kernel may be running: it writes exactly
 // the rows with a bit set, this kernel only the others).
 int clear_rows(void* feat, const int* weight, int64_t first, int64_t n_rows, int esz, int row_bytes, const uint32_t* masks,
-               size_t mask_plane, int n_planes, hipStream_t s);
-inline int launch_clear_unwritten(const KVol& kv, const uint32_t* masks, size_t mask_plane, int n_planes, hipStream_t s) {
+               size_t mask_plane, int n_planes, const Knobs& kn, hipStream_t s);
+inline int launch_clear_unwritten(const KVol& kv, const uint32_t* masks, size_t mask_plane, int n_planes, const Knobs& kn, hipStream_t s) {
   const int esz = kv.bf16 ? 2 : 4;
-  return clear_rows(kv.feat, kv.weight, 0, (int64_t)kv.N, esz, kv.D * esz, masks, mask_plane, n_planes, s);
+  return clear_rows(kv.feat, kv.weight, 0, (int64_t)kv.N, esz, kv.D * esz, masks, mask_plane, n_planes, kn, s);
 }
 KVol slab_kvol(const KVol& kv, int x0, int nx);
+// slab k of a call's slab list lies inside the volume
+inline int check_slab(const KVol& kv, const WinSlabs& sl, int k) {
+  if (sl.x0[k] < 0 || sl.nx[k] <= 0 || sl.x0[k] + sl.nx[k] > kv.nx) return fail(SAF_E_INVALID, "slab %d outside the volume", k);
+  return SAF_OK;
+}
 
 }  // namespace saf

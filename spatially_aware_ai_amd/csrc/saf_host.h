@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/saf.h"
+#include "saf_knobs.h"
 
 namespace saf {
 

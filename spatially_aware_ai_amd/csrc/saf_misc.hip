@@ -317,14 +317,13 @@ __global__ __launch_bounds__(256) void clear_unwritten_kernel(void* __restrict__
 
 // (declared in saf_fuse_dev.h: the windowed path launches it beside its last row kernel)
 int clear_rows(void* feat, const int* weight, int64_t first, int64_t n_rows, int esz, int row_bytes, const uint32_t* masks,
-               size_t mask_plane, int n_planes, hipStream_t s) {
+               size_t mask_plane, int n_planes, const Knobs& kn, hipStream_t s) {
   if (n_rows <= 0) return SAF_OK;
   // Beside a row kernel (masks given) half the grid.  Measured (profiles/r05/clear_beside.txt): the two kernels do run side by side
   // -- with 2 or 4 workgroups per CU the row kernel beside the clear takes 5 ms longer on the coherent scene, which is what the
   // clear takes alone: the zeros leave through the same per-CU address / store path the row kernel is bound by -- so folding the
   // clear into the call is worth 0.2-0.4 ms of 42.7 there and nothing on depth A; 8 per CU was the best of 2 / 4 / 8 / 16.
-  const char* bpc_env = getenv("SAF_CLEAR_WGS");
-  const int per_cu = bpc_env && atoi(bpc_env) > 0 ? atoi(bpc_env) : (masks ? 8 : 16);
+  const int per_cu = kn.clear_wgs > 0 ? kn.clear_wgs : (masks ? 8 : 16);  // (SAF_CLEAR_WGS)
   if ((uintptr_t)feat & 15) return fail(SAF_E_INVALID, "clear_unwritten_rows: clip_feat must be 16-byte aligned");
   int64_t blocks = (n_rows + 255) / 256;
   const int64_t cap = (int64_t)device_cus() * per_cu;
@@ -480,7 +479,7 @@ int saf_clear_unwritten_rows(const saf_volume* vol, int64_t first_voxel, int64_t
   const int64_t N = n_voxels(vol);
   if (first_voxel < 0 || n_rows < 0 || first_voxel + n_rows > N) return fail(SAF_E_INVALID, "clear_unwritten_rows: bad voxel range");
   const int esz = vol->feat_dtype == SAF_F32 ? 4 : 2;
-  return clear_rows(vol->clip_feat, vol->weight, first_voxel, n_rows, esz, vol->feat_dim * esz, nullptr, 0, 0, static_cast<hipStream_t>(stream));
+  return clear_rows(vol->clip_feat, vol->weight, first_voxel, n_rows, esz, vol->feat_dim * esz, nullptr, 0, 0, read_knobs(), static_cast<hipStream_t>(stream));
 }
 
 int saf_stage_frame(const saf_frame* src, int32_t feat_channels, int64_t feat_stride_c, int64_t feat_stride_y,

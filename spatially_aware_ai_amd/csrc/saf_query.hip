@@ -1009,27 +1009,23 @@ int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, co
   return check_launch(SPLIT == 2 ? "query_split16_kernel" : SPLIT ? "query_split_kernel" : "query_mfma_kernel");
 }
 
-// SAF_Q_SPLIT (read per call): 0 = the fp32 MFMA scan for every shape (development / A-B); default: the split scan where it applies
-inline bool split_wanted(int D) {
-  const char* e = getenv("SAF_Q_SPLIT");
-  return D % 16 == 0 && !(e && atoi(e) == 0);
-}
+// SAF_Q_SPLIT=0: the fp32 MFMA scan for every shape; default: the split scan where it applies
+inline bool split_wanted(int D, const Knobs& kn) { return D % 16 == 0 && kn.q_split; }
 
 template <int EPI, int FT, int TILES>
 int launch_mfma_t(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0,
-                  const TopkArgs& tk) {
-  const bool split = split_wanted(D);
+                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int64_t out_stride,
+                  int out_col0, const TopkArgs& tk) {
+  const bool split = split_wanted(D, kn);
   // (the split scan's label rows take the bytes of the fp32 rows -- two fp16 pieces per value -- plus a scale per label)
   const size_t shmem = (size_t)TILES * 32 * (D + 4) * sizeof(float) + (split ? (size_t)TILES * 32 * sizeof(float) : 0);
   const int per_cu = (int)((160 * 1024) / (shmem + 256)) > 2 ? 2 : (int)((160 * 1024) / (shmem + 256));
-  // SAF_Q_THREADS (read per call; development): 256 or 512 threads per workgroup whatever the tiles leave room for
-  const char* th_env = getenv("SAF_Q_THREADS");
-  const bool wide = th_env ? atoi(th_env) == 512 : per_cu <= 1;
+  // SAF_Q_THREADS: 256 or 512 threads per workgroup whatever the tiles leave room for
+  const bool wide = kn.q_threads ? kn.q_threads == 512 : per_cu <= 1;
 #define SAF_Q_GO(TH, SP) launch_mfma_th<EPI, FT, TILES, TH, SP>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, per_cu, shmem, s, out_stride, out_col0, tk)
   // a 16-bit volume whose rows lie on 16-byte boundaries: one load per k-step in the matrix instruction's layout, one piece per feature
-  const char* e16 = getenv("SAF_Q_SPLIT16");  // (0: through the fp32 form, development / A-B)
-  if (split && FT != SAF_F32 && fstride % 8 == 0 && !(e16 && atoi(e16) == 0)) return wide ? SAF_Q_GO(512, 2) : SAF_Q_GO(256, 2);
+  // (SAF_Q_SPLIT16=0: through the fp32 form)
+  if (split && FT != SAF_F32 && fstride % 8 == 0 && kn.q_split16) return wide ? SAF_Q_GO(512, 2) : SAF_Q_GO(256, 2);
   if (split) return wide ? SAF_Q_GO(512, 1) : SAF_Q_GO(256, 1);
   return wide ? SAF_Q_GO(512, 0) : SAF_Q_GO(256, 0);
 #undef SAF_Q_GO
@@ -1046,25 +1042,25 @@ inline bool mfma_ok(int ft, int64_t fstride, int D, int L, const void* feats) {
 
 template <int EPI, int FT>
 int launch_mfma_f(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int64_t out_stride, int out_col0,
-                  const TopkArgs& tk) {
+                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int64_t out_stride,
+                  int out_col0, const TopkArgs& tk) {
   return L > 32 ? launch_mfma_t<EPI, FT, 2>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, out_stride, out_col0, tk)
+                                            out_last, s, kn, out_stride, out_col0, tk)
                 : launch_mfma_t<EPI, FT, 1>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, out_stride, out_col0, tk);
+                                            out_last, s, kn, out_stride, out_col0, tk);
 }
 
 template <int EPI>
 int launch_mfma(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L,
                 int64_t tstride, float scale, int normalize, const float* wts, float* out, float* out_last,
-                hipStream_t s, int64_t out_stride = 0, int out_col0 = 0, const TopkArgs& tk = TopkArgs{}) {
+                hipStream_t s, const Knobs& kn, int64_t out_stride = 0, int out_col0 = 0, const TopkArgs& tk = TopkArgs{}) {
   switch (ft) {
     case SAF_BF16:
-      return launch_mfma_f<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
+      return launch_mfma_f<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
     case SAF_F16:
-      return launch_mfma_f<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
+      return launch_mfma_f<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
     default:
-      return launch_mfma_f<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, out_stride, out_col0, tk);
+      return launch_mfma_f<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
   }
 }
 
@@ -1106,7 +1102,7 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(float* __restrict__ ou
 
 template <int EPI>
 int launch_mfma_blocks(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                       float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, int bw) {
+                       float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int bw) {
   // bw: labels per block -- 64, or 32 where two 32-label tiles of this width do not fit the LDS (feat_dim 768 / 1024: round 6)
   for (int c0 = 0; c0 < L; c0 += bw) {
     const int lb = L - c0 < bw ? L - c0 : bw;
@@ -1114,7 +1110,7 @@ int launch_mfma_blocks(int ft, const void* feats, int64_t n_rows, int64_t fstrid
     //  out_last; softmax and surgery take it from the finishing pass)
     float* last = EPI == SAF_Q_SCORES && c0 + lb == L ? out_last : nullptr;
     int rc = launch_mfma<SAF_Q_SCORES>(ft, feats, n_rows, fstride, D, text + (int64_t)c0 * tstride, lb, tstride, scale, normalize,
-                                       wts ? wts + c0 : nullptr, out, last, s, (int64_t)L, c0);
+                                       wts ? wts + c0 : nullptr, out, last, s, kn, (int64_t)L, c0);
     if (rc) return rc;
   }
   if (EPI == SAF_Q_SCORES) return SAF_OK;
@@ -1274,23 +1270,24 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
                  : (n_text > 64 && mfma_ok(ft, feat_stride, feat_dim, 64, feats)) ? 64
                  : (n_text > 32 && mfma_ok(ft, feat_stride, feat_dim, 32, feats)) ? 32 : 0;
   const bool blocks = bw != 0;
+  const Knobs kn = read_knobs();
   switch (epilogue) {
     case SAF_Q_SCORES:
       if (blocks)
         return launch_mfma_blocks<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                                nullptr, out, out_last, s, bw);
+                                                nullptr, out, out_last, s, kn, bw);
       if (mfma)
         return launch_mfma<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale,
-                                         normalize, nullptr, out, out_last, s);
+                                         normalize, nullptr, out, out_last, s, kn);
       return launch<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
                                   nullptr, out, out_last, s);
     case SAF_Q_SOFTMAX:
       if (blocks)
         return launch_mfma_blocks<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                                 nullptr, out, out_last, s, bw);
+                                                 nullptr, out, out_last, s, kn, bw);
       if (mfma)
         return launch_mfma<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale,
-                                          normalize, nullptr, out, out_last, s);
+                                          normalize, nullptr, out, out_last, s, kn);
       return launch<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
                                    nullptr, out, out_last, s);
     case SAF_Q_SURGERY: {
@@ -1303,10 +1300,10 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
       if (rc) return rc;
       if (blocks)
         return launch_mfma_blocks<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f, normalize,
-                                                 wts, out, out_last, s, bw);
+                                                 wts, out, out_last, s, kn, bw);
       if (mfma)
         return launch_mfma<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f,
-                                          normalize, wts, out, out_last, s);
+                                          normalize, wts, out, out_last, s, kn);
       return launch<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f, normalize, wts,
                                    out, out_last, s);
     }
@@ -1336,6 +1333,7 @@ int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
   if (bw == 0)
     return launch_topk_rows(feat_dtype, feats, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize, k,
                             out_index, out_prob, s);
+  const Knobs kn = read_knobs();
   TopkArgs tk;
   tk.k = k;
   tk.out_index = out_index;
@@ -1359,7 +1357,7 @@ int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
     tk.first = c0 == 0;
     tk.last = c0 + lb >= n_text;
     const int rc = launch_mfma<EPI_TOPK>(feat_dtype, feats, n_rows, feat_stride, feat_dim, text + (int64_t)c0 * text_stride, lb,
-                                         text_stride, scale, normalize, nullptr, nullptr, nullptr, s, 0, 0, tk);
+                                         text_stride, scale, normalize, nullptr, nullptr, nullptr, s, kn, 0, 0, tk);
     if (rc) return rc;
   }
   return SAF_OK;

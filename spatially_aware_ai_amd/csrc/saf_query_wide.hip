@@ -1578,13 +1578,12 @@ int launch_wide3(const Wide2Args& wa, hipStream_t s) {
 // (SAF_WIDE_ROWS=64 in the environment picks them; the fp32-out heat maps among them spill ten registers), -DSAF_W2_TWO_WGS two
 // workgroups of four waves per CU (SAF_WIDE_ROWS=33).
 template <int FT, int OT, int KS, int EPI>
-int launch_wide2(const Wide2Args& wa, hipStream_t s) {
-  const int rows_env = getenv("SAF_WIDE_ROWS") ? atoi(getenv("SAF_WIDE_ROWS")) : 0;
+int launch_wide2(const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
+  const int rows_env = kn.wide_rows;  // (SAF_WIDE_ROWS)
   (void)rows_env;
   // The scan runs on v_mfma_f32_16x16x32 (query_wide3_kernel: 4-9 % faster than the 32x32x16 form at the same tile per wave, the
-  // chip holds a higher clock on it); SAF_WIDE_MFMA=32 (read per call) selects query_wide2_kernel.
-  const char* shape = getenv("SAF_WIDE_MFMA");
-  if (!(shape && atoi(shape) == 32)) return launch_wide3<FT, OT, KS, EPI>(wa, s);
+  // chip holds a higher clock on it); SAF_WIDE_MFMA=32 selects query_wide2_kernel.
+  if (!kn.wide_mfma32) return launch_wide3<FT, OT, KS, EPI>(wa, s);
 #ifdef SAF_W2_NF2
   if (rows_env == 64) return launch_wide2_nf<FT, OT, KS, EPI, 2, 256>(wa, s);
 #endif
@@ -1598,24 +1597,24 @@ int launch_wide2(const Wide2Args& wa, hipStream_t s) {
 }
 
 template <int FT, int KS>
-int launch_wide2_epi(int epi, int ot, const Wide2Args& wa, hipStream_t s) {
+int launch_wide2_epi(int epi, int ot, const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
   switch (epi) {
     case SAF_QW_SCORES:
       switch (ot) {
-        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_SCORES>(wa, s);
-        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_SCORES>(wa, s);
-        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_SCORES>(wa, s);
+        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_SCORES>(wa, kn, s);
+        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_SCORES>(wa, kn, s);
+        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_SCORES>(wa, kn, s);
       }
       break;
     case SAF_QW_VS_BACKGROUND:
       switch (ot) {
-        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_VS_BACKGROUND>(wa, s);
-        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_VS_BACKGROUND>(wa, s);
-        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_VS_BACKGROUND>(wa, s);
+        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
+        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
+        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
       }
       break;
-    case SAF_QW_ROW_ARGMAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_ROW_ARGMAX>(wa, s);
-    case SAF_QW_QUERY_MAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_QUERY_MAX>(wa, s);
+    case SAF_QW_ROW_ARGMAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_ROW_ARGMAX>(wa, kn, s);
+    case SAF_QW_QUERY_MAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_QUERY_MAX>(wa, kn, s);
   }
   return fail(SAF_E_INVALID, "wide scan: bad epilogue %d / out_dtype %d", epi, ot);
 }
@@ -1761,11 +1760,12 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
     wa.n_rows = n_rows; wa.fstride = feat_stride; wa.text16 = text16; wa.Q = cols; wa.Qpad = Qpad; wa.scale = scale;
     wa.normalize = normalize; wa.n_bg = n_bg; wa.flags = flags; wa.out = out; wa.ostride = out_stride;
     wa.out_index = out_index; wa.out_value = out_value; wa.qkeys = qkeys; wa.row_offset = row_offset;
-    wa.safe_wait = getenv("SAF_W2_SAFE_WAIT") && getenv("SAF_W2_SAFE_WAIT")[0] == '1' ? 1 : 0;
+    const Knobs kn = read_knobs();
+    wa.safe_wait = kn.w2_safe_wait ? 1 : 0;  // (SAF_W2_SAFE_WAIT)
     if (feat_dtype == SAF_BF16)
-      rc = feat_dim == 512 ? launch_wide2_epi<SAF_BF16, 32>(epilogue, out_dtype, wa, s) : launch_wide2_epi<SAF_BF16, 16>(epilogue, out_dtype, wa, s);
+      rc = feat_dim == 512 ? launch_wide2_epi<SAF_BF16, 32>(epilogue, out_dtype, wa, kn, s) : launch_wide2_epi<SAF_BF16, 16>(epilogue, out_dtype, wa, kn, s);
     else
-      rc = feat_dim == 512 ? launch_wide2_epi<SAF_F16, 32>(epilogue, out_dtype, wa, s) : launch_wide2_epi<SAF_F16, 16>(epilogue, out_dtype, wa, s);
+      rc = feat_dim == 512 ? launch_wide2_epi<SAF_F16, 32>(epilogue, out_dtype, wa, kn, s) : launch_wide2_epi<SAF_F16, 16>(epilogue, out_dtype, wa, kn, s);
     if (rc) return rc;
   }
   if (epilogue == SAF_QW_QUERY_MAX) {

@@ -1654,18 +1654,66 @@ size_t window_workspace_bytes(int64_t n_vox, int D, int P, bool bricks, int H, i
   return win_layout(n_vox, D, P, bricks, fr ? depth_px_padded(H, W) : 0, fr && labels ? rgbl_px_padded(H, W) : 0).total;
 }
 
-// SAF_WIN_FORM (read per call): "rows" = the frame-ordered row kernel (bit-identical to fusing frame after frame), "sums" =
-// its order-free form (a row's samples of the window summed in registers, one blend per row: feature values within fp32
-// rounding of the sequential path, everything else exact), "bricks" = saf_brick.hip.  Default: sums.
-bool window_form_sums() {
-  const char* e = getenv("SAF_WIN_FORM");
-  return !e || e[0] == 's';
+// ---------------------------------------------------------------------------------------------
+// The route of a fusion call (declared in saf_fuse_dev.h).  SAF_WIN_FORM picks among the windowed path's row steps by its first
+// letter: "rows" = the frame-ordered row kernel (bit-identical to fusing frame after frame), "sums" = its order-free form
+// (feature values within fp32 rounding of the sequential path, everything else exact), "bricks" = saf_brick.hip.  Unset: sums
+// for the widths the row kernel takes, bricks for the others.
+// ---------------------------------------------------------------------------------------------
+bool brick_form_applies(const KVol& kv, const Knobs& kn) {
+  if (kn.win_form == 'r' || !brick_form_takes(kv.D, kv.nx, kv.ny, kv.nz)) return false;
+  return kn.win_form == 'b' || !row_kernel_takes(kv.D, kv.bf16 != 0);
 }
 
-// Frames per window: 128 (SAF_WINDOW_FRAMES) unless SAF_WIN_FRAMES=64 asks for the shorter form (read per call).
-int window_frames() {
-  const char* e = getenv("SAF_WIN_FRAMES");
-  return e && atoi(e) == 64 ? 64 : kWin;
+// Without the volume: room for the brick form wherever SOME dtype of this width would ask for it (the grid is unknown).
+bool brick_form_sized_for(int D, const Knobs& kn) {
+  if (kn.win_form == 'r' || !brick_form_takes_width(D)) return false;
+  // SPECIAL CASE, kept as found: SAF_WIN_FORM=sums reserves no pools here although brick_form_applies -- and with it the two
+  // sizing entries that know the volume -- still sends the widths the row kernel does not take to the brick form.  Under that
+  // setting a call at, say, feat_dim = 64 takes the brick form or the per-frame pipeline depending on which entry sized its
+  // workspace.  (A behaviour change for a later pull request: drop this line.)
+  if (kn.win_form == 's') return false;
+  return kn.win_form == 'b' || !row_kernel_takes(D, false) || !row_kernel_takes(D, true);
+}
+
+namespace {
+// The row step of a window of this volume, given the (untiled) layout of its workspace: the brick form where the call asks for it
+// and its pools fit behind the layout; else the row kernel where it takes the width -- order-free unless SAF_WIN_FORM names
+// another form or SAF_WIN_MAPS16=0 keeps a bf16 volume's map images in fp32 --; else none (kPathPerFrame).
+FusePath window_form(const KVol& kv, const WinLayout& wl, size_t workspace_bytes, const Knobs& kn) {
+  if (brick_form_applies(kv, kn) && workspace_bytes > wl.cmax_off && brick_aux_fits(kv, workspace_bytes - wl.cmax_off)) return kPathBricks;
+  if (!row_kernel_takes(kv.D, kv.bf16 != 0)) return kPathPerFrame;
+  const bool sums = (kn.win_form == 0 || kn.win_form == 's') && !(kv.bf16 != 0 && !kn.win_maps16);
+  return sums ? kPathSums : kPathRows;
+}
+}  // namespace
+
+// A call needs kWinMinFrames frames for the windowed path and may take the brick form; a session's push may be short, and a
+// session takes the row forms only (the brick form builds its segments per window), on two streams, in windows of
+// SAF_WINDOW_FRAMES frames -- what the caller's ring of frames is cut by (include/saf.h; under SAF_WIN_FRAMES=64 the tile region's
+// four slots turn over twice per turn of a 512-frame ring: saf_fuse_frames cuts its own windows there).
+FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn) {
+  const FuseRoute per_frame{kPathPerFrame, false};
+  if (!kn.window || n_frames < 1) return per_frame;
+  if (kv.bf16 && !kn.window_bf16) return per_frame;
+  const saf_frame& f0 = frames[0];
+  const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
+  const FusePath form = window_form(kv, wl, workspace_bytes, kn);
+  if (form == kPathPerFrame) return per_frame;
+  for (int32_t i = 1; i < n_frames; ++i) {  // one shape for the window's frames
+    const saf_frame& f = frames[i];
+    if (f.height != f0.height || f.width != f0.width || f.npy != f0.npy || f.npx != f0.npx ||
+        f.rgb_bilinear != f0.rgb_bilinear || (f.label_map == nullptr) != (f0.label_map == nullptr))
+      return per_frame;
+  }
+  if (f0.npx + 3 > 255 || f0.npy + 3 > 255) return per_frame;  // a hit's map cell travels as two bytes
+  if (wl.maps_bytes >= (size_t)kTapOutside) return per_frame;  // the taps are buffer loads with 31-bit byte offsets
+  if (workspace_bytes < wl.cmax_off) return per_frame;         // (the brick form's own region: window_form)
+  FuseRoute r;
+  r.path = n_frames >= kWinMinFrames ? form : kPathPerFrame;
+  // (a volume whose calls ask for the brick form has no sessions, even in a workspace too small for the pools)
+  r.session = !brick_form_applies(kv, kn) && kn.win_overlap && !kn.win_frames64;
+  return r;
 }
 
 namespace {
@@ -1677,28 +1725,29 @@ struct WinPlan {
   int P, img_vecs, prep_blocks, split;
   int ts_log2, tiles_x, n_tiles;  // depth tiles of the classification's occlusion cull
   int wlen;                       // frames per window
-  int wgs_env;                    // SAF_WIN_WGS (0: unset)
-  bool tiled, tiled_first, sum, of, maps16, rgbl_on, brick_form, xcd, verify;
+  bool tiled, sum, of, maps16, rgbl_on, brick_form;
   size_t dpx, img_bytes16, win_lds, aux_bytes;
   WinFn fn;  // the row kernel (nullptr: the brick form)
+  Knobs kn;  // the call's knobs
 };
-int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, WinPlan* pl) {
+int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Knobs& kn, WinPlan* pl) {
+  pl->kn = kn;
   pl->H = kf0.H; pl->W = kf0.W; pl->npy = kf0.npy; pl->npx = kf0.npx; pl->rgb_bilinear = kf0.rgb_bilinear;
   const int P = pl->P = kf0.npy * kf0.npx;
   // Two layouts of the workspace: with room for the window's depth images re-laid-out in tiles (a workspace sized by
   // saf_fuse_workspace_bytes_for_frames) or without (the classification then reads the frames' own row-major images).
-  // SAF_CLS_TILED=0 (read per call): never tiled; 2: the first unit of a call reads the tiled copies too (tests: a single-window call).
+  // (SAF_CLS_TILED=0: never tiled)
   const size_t dpx = pl->dpx = depth_px_padded(kf0.H, kf0.W);
   // (a volume that counts labels: the frames-sized layout also holds one window of packed {r, g, b, label} images)
   const size_t rpx = kv.labels ? rgbl_px_padded(kf0.H, kf0.W) : 0;
   const WinLayout wl_lin = win_layout(kv.N, kv.D, P), wl_til = win_layout(kv.N, kv.D, P, false, dpx, rpx);
-  const char* til_env = getenv("SAF_CLS_TILED");
-  pl->tiled = !(til_env && til_env[0] == '0') && dpx * sizeof(float) < (size_t)1 << 31 && workspace_bytes >= wl_til.cmax_off;
-  pl->tiled_first = til_env && til_env[0] == '2';
-  if (pl->tiled && brick_form_ok(kv)) {  // the brick form's pools follow the tile region: both must fit, or neither moves
-    const size_t a_lin = workspace_bytes > wl_lin.cmax_off ? workspace_bytes - wl_lin.cmax_off : 0;
+  const FusePath form = window_form(kv, wl_lin, workspace_bytes, kn);
+  if (form == kPathPerFrame) return fail(SAF_E_UNSUPPORTED, "windowed path: no row kernel for this width");
+  pl->brick_form = form == kPathBricks;
+  pl->tiled = kn.cls_tiled && dpx * sizeof(float) < (size_t)1 << 31 && workspace_bytes >= wl_til.cmax_off;
+  if (pl->tiled && pl->brick_form) {  // the brick form's pools follow the tile region: both must fit, or neither moves
     const size_t a_til = workspace_bytes - wl_til.cmax_off;
-    if (a_lin > 0 && brick_aux_fits(kv, a_lin) && !(a_til > 0 && brick_aux_fits(kv, a_til))) pl->tiled = false;
+    if (!(a_til > 0 && brick_aux_fits(kv, a_til))) pl->tiled = false;
   }
   const WinLayout& wl = pl->wl = pl->tiled ? wl_til : wl_lin;
   if (workspace_bytes < wl.cmax_off) return fail(SAF_E_WORKSPACE, "windowed path: workspace too small");
@@ -1706,16 +1755,13 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, WinPlan*
   pl->img_vecs = (int)(wl.img_bytes / sizeof(float4));
   pl->prep_blocks = (kv.D * (P + 1) + 255) / 256;
   pl->aux_bytes = workspace_bytes - wl.cmax_off;
-  pl->brick_form = brick_form_ok(kv) && pl->aux_bytes > 0 && brick_aux_fits(kv, pl->aux_bytes);
-  pl->split = pl->brick_form && brick_split() ? 1 : 0;
-  // ClipSeemFusion's image side from packed images (SAF_WIN_RGBL=0, read per call: from the frames' own images -- the A/B)
-  pl->rgbl_on = !pl->brick_form && wl.cmax_off > wl.rgbl_off && kf0.rgb_bilinear && kf0.label_map &&
-                !(getenv("SAF_WIN_RGBL") && getenv("SAF_WIN_RGBL")[0] == '0');
-  // SAF_WIN_MAPS16=0 (read per call): a bf16 volume keeps fp32 map images -- it takes the frame-ordered kernel, bit-identical
-  // to the per-frame bf16 pipeline -- instead of the order-free form's bf16 images (one rounding of every tap to the volume's
-  // precision, exact when the backbone emitted bf16: BASELINE config 3).  fp32 volumes are not affected.
-  const char* m16 = getenv("SAF_WIN_MAPS16");
-  pl->of = window_form_sums() && !(kv.bf16 != 0 && m16 && m16[0] == '0');
+  pl->split = pl->brick_form && kn.brick_split ? 1 : 0;
+  // ClipSeemFusion's image side from packed images (SAF_WIN_RGBL=0: from the frames' own images -- the A/B)
+  pl->rgbl_on = !pl->brick_form && wl.cmax_off > wl.rgbl_off && kf0.rgb_bilinear && kf0.label_map && kn.win_rgbl;
+  // The order-free form of a bf16 volume reads bf16 map images (one rounding of every tap to the volume's precision, exact when
+  // the backbone emitted bf16: BASELINE config 3); under SAF_WIN_MAPS16=0 it keeps fp32 images and takes the frame-ordered
+  // kernel, bit-identical to the per-frame bf16 pipeline (window_form).  fp32 volumes are not affected.
+  pl->of = form == kPathSums;
   pl->fn = nullptr;
   pl->win_lds = 0;
   if (!pl->brick_form) {
@@ -1740,12 +1786,7 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, WinPlan*
   pl->ts_log2 = ts_log2;
   pl->tiles_x = (kf0.W + (1 << ts_log2) - 1) >> ts_log2;
   pl->n_tiles = pl->tiles_x * ((kf0.H + (1 << ts_log2) - 1) >> ts_log2);
-  pl->wlen = window_frames();
-  pl->wgs_env = getenv("SAF_WIN_WGS") ? atoi(getenv("SAF_WIN_WGS")) : 0;
-  pl->xcd = !(getenv("SAF_WIN_XCD") && getenv("SAF_WIN_XCD")[0] == '0');
-  // SAF_CLS_VERIFY=1 (read per call): the self-checking classification -- every voxel slot computes the reference's pixel chain
-  // as well and counts disagreements with the guarded path in stats[7] (tests; tools/cls_guard_verify.py)
-  pl->verify = getenv("SAF_CLS_VERIFY") && getenv("SAF_CLS_VERIFY")[0] == '1';
+  pl->wlen = kn.win_frames64 ? 64 : kWin;  // 128 (SAF_WINDOW_FRAMES) unless SAF_WIN_FRAMES=64 asks for the shorter form
   return SAF_OK;
 }
 
@@ -1800,14 +1841,14 @@ WinGeom win_geom(const WinPlan& pl, const KVol& u) {
   // (the frame-ordered form keeps its rows in LDS: with 512-hit chunks 115 KB per workgroup at D = 512 -- ONE fits a CU, and a grid
   //  of two per CU would leave half of the persistent workgroups waiting for the others to finish)
   const int fit = pl.win_lds > 0 ? (int)((160 * 1024) / pl.win_lds) : 2;
-  g.grid = (uint32_t)device_cus() * (pl.wgs_env > 0 ? pl.wgs_env : (pl.of ? SAF_WIN_OF_WPE : (fit < 1 ? 1 : (fit > 2 ? 2 : fit))));
+  g.grid = (uint32_t)device_cus() * (pl.kn.win_wgs > 0 ? pl.kn.win_wgs : (pl.of ? SAF_WIN_OF_WPE : (fit < 1 ? 1 : (fit > 2 ? 2 : fit))));
   if (g.grid > row_wgs) g.grid = row_wgs;
   // the classification's bricks: the brick grid padded to whole 8 x 8 tiles of brick columns
   const uint32_t tx = ((uint32_t)u.nx + 8 * kBrickX - 1) / (8 * kBrickX), ty = ((uint32_t)u.ny + 8 * kBrickY - 1) / (8 * kBrickY);
   const uint32_t nbz = ((uint32_t)u.nz + kBrickZ - 1) / kBrickZ;
   g.cls_wgs = (tx * ty * 64u * nbz + 3u) / 4u;
   // units of the row kernel in XCD-compact order (see the kernel); SAF_WIN_XCD=0: linear order
-  g.xcd_order = pl.xcd && u.nx % 16 == 0 && u.ny % 16 == 0 && u.nz % kUnitVox == 0 && u.N % kPiece == 0 ? 1 : 0;
+  g.xcd_order = pl.kn.win_xcd && u.nx % 16 == 0 && u.ny % 16 == 0 && u.nz % kUnitVox == 0 && u.N % kPiece == 0 ? 1 : 0;
   return g;
 }
 
@@ -1855,7 +1896,9 @@ int launch_classify(const WinPlan& pl, const WinView& v, const TileView& tv, con
   }
   uint32_t* plane = v.masks + (size_t)(g.fb / kClsFrames) * pl.wl.mask_plane;
   ScopedPair t(prof, 1, g.first, cs);
-  const bool verify = pl.verify && stats;
+  // SAF_CLS_VERIFY=1: the self-checking classification -- every voxel slot computes the reference's pixel chain as well and
+  // counts disagreements with the guarded path in stats[7] (tests; tools/cls_guard_verify.py)
+  const bool verify = pl.kn.cls_verify && stats;
   const bool sum = pl.sum;
   auto kfn = use_tiled ? (verify ? (sum ? classify_bricks_kernel<true, true, true> : classify_bricks_kernel<false, true, true>)
                                  : (sum ? classify_bricks_kernel<true, false, true> : classify_bricks_kernel<false, false, true>))
@@ -1900,7 +1943,7 @@ int launch_rows(const WinPlan& pl, const WinView& v, const KVol& kv, int F, bool
   if (pl.brick_form)
     return launch_fuse_bricks(kv, wa, v.tab, v.maps, pl.wl.img_bytes, reinterpret_cast<unsigned long long*>(stats),
                               reinterpret_cast<unsigned int*>(v.hdr), v.masks, pl.wl.mask_plane, v.cls_acc, v.aux, pl.aux_bytes, v.par,
-                              pl.split, s);
+                              pl.split, pl.kn, s);
   const WinGeom g = win_geom(pl, kv);
   hipLaunchKernelGGL(pl.fn, dim3(g.grid), dim3(kWinThreads), pl.win_lds, s, kv, wa, v.tab, v.maps, pl.img_vecs,
                      reinterpret_cast<unsigned long long*>(stats), reinterpret_cast<unsigned int*>(v.hdr), v.masks, pl.wl.mask_plane,
@@ -1908,37 +1951,7 @@ int launch_rows(const WinPlan& pl, const WinView& v, const KVol& kv, int F, bool
   return check_launch("fuse_window_kernel");
 }
 
-// Shapes the windowed path takes; everything else runs the per-frame pipeline.  A call needs kWinMinFrames frames and may take
-// the brick form; a session's push may be short, and a session takes the row forms only.
-bool win_shape_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, int min_frames, bool bricks_allowed) {
-  const bool enabled = !(getenv("SAF_WINDOW") && getenv("SAF_WINDOW")[0] == '0');
-  if (!enabled || n_frames < min_frames) return false;
-  // SAF_WINDOW_BF16=0 keeps bf16 volumes on the per-frame pipeline
-  const bool bf16_on = !(getenv("SAF_WINDOW_BF16") && getenv("SAF_WINDOW_BF16")[0] == '0');
-  if (kv.bf16 && !bf16_on) return false;
-  const saf_frame& f0 = frames[0];
-  const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
-  if (brick_form_ok(kv) && !bricks_allowed) return false;
-  const bool bricks = brick_form_ok(kv) && workspace_bytes > wl.cmax_off && brick_aux_fits(kv, workspace_bytes - wl.cmax_off);
-  if (!bricks) {  // the frame-ordered row kernel: whole 1 KiB pieces of a row per wave instruction
-    if (kv.D % 256 != 0 || kv.D > 1024) return false;
-    if (kv.bf16 && kv.D % 512 != 0) return false;  // a lane moves 8 bf16 channels: 512 per wave
-  }
-  for (int32_t i = 1; i < n_frames; ++i) {
-    const saf_frame& f = frames[i];
-    if (f.height != f0.height || f.width != f0.width || f.npy != f0.npy || f.npx != f0.npx ||
-        f.rgb_bilinear != f0.rgb_bilinear || (f.label_map == nullptr) != (f0.label_map == nullptr))
-      return false;
-  }
-  if (f0.npx + 3 > 255 || f0.npy + 3 > 255) return false;  // a hit's map cell travels as two bytes
-  if (wl.maps_bytes >= (size_t)kTapOutside) return false;  // the taps are buffer loads with 31-bit byte offsets
-  return workspace_bytes >= wl.cmax_off;  // (the brick form's own region was checked above: brick_aux_fits)
-}
 }  // namespace
-
-bool window_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
-  return win_shape_ok(kv, frames, n_frames, workspace_bytes, kWinMinFrames, true);
-}
 
 // x-planes [x0, x0 + nx) of a volume as a volume of their own: the same buffers, offset (a slab of x-planes is a contiguous
 // range of the flat voxel index; the axis table starts at x0, so every decision is that of the full volume's voxels).
@@ -1974,7 +1987,8 @@ struct WinUnit {
 };
 
 int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
-                       uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const WinSlabs* slabs, bool recycled) {
+                       uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const Knobs& kn, const WinSlabs* slabs,
+                       bool recycled) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   KFrame kf0;
@@ -1984,7 +1998,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     if ((rc = make_kframe(&frames[i], &t))) return rc;
   }
   WinPlan pl;
-  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, kn, &pl))) return rc;
   int tile_window[kTileWindows];  // which window's tile maxima a slot of the tile region holds (-1: none)
   for (int k = 0; k < kTileWindows; ++k) tile_window[k] = -1;
   const int wlen = pl.wlen;
@@ -1995,23 +2009,21 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   std::vector<WinUnit> units;
   if (slabs && slabs->n > 0) {
     for (int k = 0; k < slabs->n; ++k) {
-      if (slabs->x0[k] < 0 || slabs->nx[k] <= 0 || slabs->x0[k] + slabs->nx[k] > kv.nx) return fail(SAF_E_INVALID, "slab %d outside the volume", k);
+      if ((rc = check_slab(kv, *slabs, k))) return rc;
       for (int w = 0; w < n_win; ++w)
         units.push_back(WinUnit{slab_kvol(kv, slabs->x0[k], slabs->nx[k]), w * wlen, win_frames(w), k == 0, w + 1 == n_win ? k : -1, k * n_win + w});
     }
   } else {
-    // SAF_WIN_SLABS (read per call; default 1 = off): EVERY window slab by slab, window after window -- units of one size, so
+    // SAF_WIN_SLABS (default 1 = off): EVERY window slab by slab, window after window -- units of one size, so
     // that unit u + 1's classification is as long as unit u's row kernel is; SAF_WIN_W0_SLABS: only the first window (measured:
     // no gain -- the second window's whole classification then has only the last slab's row kernel to hide behind).  Slabs are
     // whole multiples of 16 x-planes (the row kernel's XCD-compact unit order, the classification's bricks).
-    const char* e0 = getenv("SAF_WIN_W0_SLABS");
-    const char* e1 = getenv("SAF_WIN_SLABS");
     auto fit = [&](int n) {
       if (!ov || pl.brick_form || n < 2 || kv.nx % 16 != 0) return 1;
       while (n > 1 && (kv.nx / 16) % n != 0) --n;
       return n;
     };
-    const int ns = fit(e1 ? atoi(e1) : 1), n0 = ns > 1 ? ns : fit(e0 ? atoi(e0) : 1);
+    const int ns = fit(kn.win_slabs), n0 = ns > 1 ? ns : fit(kn.win_w0_slabs);
     for (int w = 0; w < n_win; ++w) {
       const int n = w == 0 ? n0 : ns;
       for (int k = 0; k < n; ++k)
@@ -2032,7 +2044,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     if (hipEventRecord(ov->fork, s) != hipSuccess || hipStreamWaitEvent(cs, ov->fork, 0) != hipSuccess)
       return fail(SAF_E_HIP, "windowed path: could not fork the classification stream");
   }
-  const bool trace = getenv("SAF_WIN_TRACE") != nullptr;  // development: host-side timeline of this call on stderr
+  const bool trace = kn.win_trace;  // SAF_WIN_TRACE: host-side timeline of this call on stderr
   const auto t_call = std::chrono::steady_clock::now();
   auto mark = [&](const char* what, int w) {
     if (trace)
@@ -2048,8 +2060,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   // The later windows' tiles AHEAD of time, on the caller's stream: it is idle until the first window has been classified, and
   // every such pair of small launches inside the classification chain (16 per 512-frame job, ~70 us each beside a row kernel)
   // lengthens the chain that a job's time follows.  Window 0's stay in front of its classification.
-  const bool pre_tiles = ov && ov->tiles && !(slabs && slabs->n > 0) && n_units == n_win && n_win >= 2 &&
-                         !(getenv("SAF_WIN_PRETILES") && getenv("SAF_WIN_PRETILES")[0] == '0');
+  const bool pre_tiles = ov && ov->tiles && !(slabs && slabs->n > 0) && n_units == n_win && n_win >= 2 && kn.win_pretiles;
   if (pre_tiles) {
     for (int w = 1; w < n_win && w < kTileWindows; ++w) {
       depth_tiles(w, w * wlen, win_frames(w), s);
@@ -2075,7 +2086,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     // (unit 0 has the chip to itself -- everything the caller queued before is done, nothing of this call runs yet --, where the
     //  classification is bound by its vector instructions and the tile offset costs 5 % (0.92 vs 0.97 ms per launch): it reads the
     //  frames' own images; the tiled copies pay where the address path is shared, i.e. for every later unit)
-    const bool use_tiled = pl.tiled && (ui > 0 || pl.tiled_first);
+    const bool use_tiled = pl.tiled && (ui > 0 || kn.cls_tiled_first);  // (SAF_CLS_TILED=2: the first unit too -- tests of a single-window call)
     for (int fb = 0; fb < F; fb += kClsFrames) {
       const FrameGroup g{frames, f0 + fb, fb + kClsFrames < F ? kClsFrames : F - fb, fb};
       if ((r = launch_classify(pl, v, tv, u.kv, g, u.count, use_tiled, stats, prof, cs))) return r;
@@ -2086,7 +2097,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
       wa.rgbl = nullptr; wa.rgbl_px = 0; wa.rgbl_tiles_x = 0;
       ScopedPair t(prof, 3, f0, cs);
       if ((r = launch_brick_build(u.kv, wa, v.tab, pl.wl.img_bytes, reinterpret_cast<unsigned long long*>(stats), v.masks, pl.wl.mask_plane,
-                                  v.aux, pl.aux_bytes, v.par, cs)))
+                                  v.aux, pl.aux_bytes, v.par, kn, cs)))
         return r;
     }
     mark("classify: launches queued", ui);
@@ -2099,10 +2110,9 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   // it.  When every unit covers the whole volume they are written on the classification stream BESIDE the last unit's row kernel
   // instead (that stream has nothing left to do): by then every earlier unit has updated `weight`, and the last unit's hit masks
   // say which rows its row kernel writes -- the two kernels' rows are disjoint.  What it buys is small (the row kernel slows down
-  // by nearly what the clear takes: saf_misc.hip, clear_rows).  SAF_WIN_CLEAR_BESIDE=0 (read per call): behind the last row
+  // by nearly what the clear takes: saf_misc.hip, clear_rows).  SAF_WIN_CLEAR_BESIDE=0: behind the last row
   // kernel, on the caller's stream.
-  const bool clear_beside = recycled && ov && !pl.brick_form && !(slabs && slabs->n > 0) && n_units == n_win &&
-                            !(getenv("SAF_WIN_CLEAR_BESIDE") && getenv("SAF_WIN_CLEAR_BESIDE")[0] == '0');
+  const bool clear_beside = recycled && ov && !pl.brick_form && !(slabs && slabs->n > 0) && n_units == n_win && kn.win_clear_beside;
   int maps_of = -1;  // the window whose map images the workspace holds
   for (int ui = 0; ui < n_units && rc == SAF_OK; ++ui) {
     const WinUnit& u = units[ui];
@@ -2113,14 +2123,14 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     if (clear_beside && ui + 1 == n_units) {
       // (queued behind this unit's classification; the row kernel of the unit before must have stored its weights)
       if (ui >= 1 && hipStreamWaitEvent(cs, ov->fuse_done[par ^ 1], 0) != hipSuccess) { rc = fail(SAF_E_HIP, "hipStreamWaitEvent"); break; }
-      if ((rc = launch_clear_unwritten(u.kv, v.masks, pl.wl.mask_plane, (u.F + kClsFrames - 1) / kClsFrames, cs))) break;
+      if ((rc = launch_clear_unwritten(u.kv, v.masks, pl.wl.mask_plane, (u.F + kClsFrames - 1) / kClsFrames, kn, cs))) break;
     }
     // (the slabs of one window share its map images)
     if ((rc = launch_rows(pl, v, u.kv, u.F, maps_of != u.window, stats, prof, u.f0, s))) break;
     maps_of = u.window;
     mark("rows: queued", ui);
     // a finished slab of a recycled volume: its rows that are still unwritten are zeroed before anyone is told it is finished
-    if (u.done >= 0 && recycled && (rc = launch_clear_unwritten(u.kv, nullptr, 0, 0, s))) break;
+    if (u.done >= 0 && recycled && (rc = launch_clear_unwritten(u.kv, nullptr, 0, 0, kn, s))) break;
     if (u.done >= 0 && slabs && slabs->done && slabs->done[u.done] &&
         hipEventRecord(static_cast<hipEvent_t>(slabs->done[u.done]), s) != hipSuccess) { rc = fail(SAF_E_HIP, "hipEventRecord(slab done)"); break; }
     if (ov && hipEventRecord(ov->fuse_done[par], s) != hipSuccess) { rc = fail(SAF_E_HIP, "hipEventRecord"); break; }
@@ -2129,7 +2139,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
   if (ov) {  // whatever was queued on the classification stream is ordered before later work of the caller (error paths too)
     if (hipEventRecord(ov->join, cs) == hipSuccess) (void)hipStreamWaitEvent(s, ov->join, 0);
   }
-  if (recycled && !clear_beside && !(slabs && slabs->n > 0) && rc == SAF_OK) rc = launch_clear_unwritten(kv, nullptr, 0, 0, s);
+  if (recycled && !clear_beside && !(slabs && slabs->n > 0) && rc == SAF_OK) rc = launch_clear_unwritten(kv, nullptr, 0, 0, kn, s);
 #ifdef SAF_WIN_TIMING
   {
     (void)hipStreamSynchronize(s);
@@ -2160,12 +2170,8 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
 // caller's stream, and the next window's launches -- pushed while it runs -- run beside it, as units u and u + 1 of one
 // fuse_many_windowed call do.  A session calls the launchers that fuse_many_windowed calls (win_plan, launch_depth_tiles,
 // launch_classify, open_unit_header, launch_rows) with the same window cuts: results are bit for bit those of one
-// saf_fuse_frames call over the same frames.  (The row forms only: the brick form builds its segments per window.)
+// saf_fuse_frames call over the same frames.  (The row forms only: fuse_route.)
 // ---------------------------------------------------------------------------------------------
-bool stream_ok(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
-  return win_shape_ok(kv, frames, n_frames, workspace_bytes, 1, false);
-}
-
 namespace {
 // the open window's row kernel: behind its last classification launch
 int close_window(const WinPlan& pl, unsigned char* ws, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen) {
@@ -2191,10 +2197,11 @@ int close_window(const WinPlan& pl, unsigned char* ws, uint64_t* stats, hipStrea
 }
 }  // namespace
 
-int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, WinStream* st, bool preopen) {
+int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipStream_t s, const WinOverlap* ov, const Knobs& kn, WinStream* st,
+                 bool preopen) {
   if (!st->open || st->filled == 0) return SAF_OK;
   WinPlan pl;
-  int rc = win_plan(st->kv, st->kf0, workspace_bytes, &pl);
+  int rc = win_plan(st->kv, st->kf0, workspace_bytes, kn, &pl);
   if (rc) return rc;
   return close_window(pl, static_cast<unsigned char*>(workspace), stats, s, ov, st, preopen);
 }
@@ -2204,13 +2211,13 @@ int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipSt
 // long completed, the push finds that out with hipEventQuery and queues its classification launch with NO cross-stream wait in front
 // (a barrier packet between two launches of the classification chain is 0.12 ms of idle chain: profiles/r06/api_b1_timeline.txt).
 int stream_prepare(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes, hipStream_t ts,
-                   WinStream* st) {
+                   const Knobs& kn, WinStream* st) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   KFrame kf0;
   if ((rc = make_kframe(&frames[0], &kf0))) return rc;
   WinPlan pl;
-  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, kn, &pl))) return rc;
   if (st->prepared < st->pushed) st->prepared = st->pushed;
   int done = 0;
   while (done < n_frames) {
@@ -2228,7 +2235,7 @@ int stream_prepare(const KVol& kv, const saf_frame* frames, int32_t n_frames, vo
 }
 
 int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes, uint64_t* stats,
-                hipStream_t s, hipEvent_t ready, hipStream_t tile_stream, const WinOverlap* ov, WinStream* st) {
+                hipStream_t s, hipEvent_t ready, hipStream_t tile_stream, const WinOverlap* ov, const Knobs& kn, WinStream* st) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   KFrame kf0;
@@ -2243,7 +2250,7 @@ int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void*
   if (st->open && st->filled % kClsFrames != 0)
     return fail(SAF_E_INVALID, "the open window holds %d frames: only a window's LAST push may be short of a multiple of %d (finish the session)", st->filled, kClsFrames);
   WinPlan pl;  // built once per push: the window closes below use it too
-  if ((rc = win_plan(kv, kf0, workspace_bytes, &pl))) return rc;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, kn, &pl))) return rc;
   st->kv = kv; st->kf0 = kf0; st->have_shape = true;
   hipStream_t cs = ov->aux;
   // What the classification of these frames waits for: their staging.  With `ready` (an event the caller recorded behind it) ONLY
@@ -2285,7 +2292,7 @@ int stream_push(const KVol& kv, const saf_frame* frames, int32_t n_frames, void*
         return fail(SAF_E_HIP, "session: could not order the classification behind its depth tiles");
     }
     // (the session's first window has the chip to itself: it reads the frames' own images, as a call's first unit does)
-    const bool use_tiled = pl.tiled && (widx > 0 || pl.tiled_first);
+    const bool use_tiled = pl.tiled && (widx > 0 || kn.cls_tiled_first);
     if ((rc = launch_classify(pl, v, tv, kv, g, 1, use_tiled, stats, nullptr, cs))) return rc;
     st->filled += g.n;
     st->pushed += g.n;

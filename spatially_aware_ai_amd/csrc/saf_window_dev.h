@@ -98,14 +98,16 @@ __device__ __forceinline__ void wave_lds_sync() {
 // `map_imgs`: the window's pixel-major map images (img_bytes each), `hitmask`: the window's mask planes.
 // `aux`: the rest of the workspace (saf_fuse_workspace_bytes reserves brick_aux_bytes_est): the channels' largest magnitudes and, per window parity, the camera table and the
 // pool of segments the build kernel (after the window's classification, on its stream) leaves for the walk kernel.
-bool brick_form_ok(const KVol& kv);
-bool brick_split();
+inline bool brick_form_takes_width(int D) { return D % 64 == 0 && D <= 8192; }  // (a sizing entry that knows no grid asks this alone)
+bool brick_form_takes(int D, int nx, int ny, int nz);
 size_t brick_aux_bytes_est(int64_t n_vox, int D);
 bool brick_aux_fits(const KVol& kv, size_t avail);
 int launch_brick_build(const KVol& kv, const WinArgs& wa, const WinTable* tab, size_t img_bytes, unsigned long long* stats,
-                       const uint32_t* hitmask, uint32_t mask_plane, void* aux, size_t aux_bytes, int parity, hipStream_t s);
+                       const uint32_t* hitmask, uint32_t mask_plane, void* aux, size_t aux_bytes, int parity, const Knobs& kn,
+                       hipStream_t s);
 int launch_fuse_bricks(const KVol& kv, const WinArgs& wa, const WinTable* tab, const float* map_imgs, size_t img_bytes,
                        unsigned long long* stats, unsigned int* ctr, const uint32_t* hitmask, uint32_t mask_plane,
-                       const unsigned long long* cls_acc, void* aux, size_t aux_bytes, int parity, int split, hipStream_t s);
+                       const unsigned long long* cls_acc, void* aux, size_t aux_bytes, int parity, int split, const Knobs& kn,
+                       hipStream_t s);
 
 }  // namespace saf
