@@ -60,7 +60,11 @@ typedef struct saf_volume {
   int32_t nx, ny, nz;
   int32_t feat_dim;       /* D = n_clip_feats */
   int32_t n_classes;      /* width of labels_one_hot (143) or 0 when there is no label histogram */
-  int32_t feat_dtype;     /* saf_dtype of clip_feat; SAF_F32 is the reference layout */
+  int32_t feat_dtype;     /* saf_dtype of clip_feat; SAF_F32 is the reference layout.  SAF_BF16 and SAF_F16 (feat_dim a multiple of 8,
+                             16-byte aligned rows): widened exactly, blended in fp32, narrowed with ONE round-to-nearest-even per
+                             update -- what torch.Tensor.to(dtype) does (fp16: subnormals kept, +-inf beyond +-65504).  SAF_F16 is the
+                             dtype saf_query_scan_wide reads in place; it takes SAF_RUNNING_MEAN only (SAF_SUM: SAF_E_UNSUPPORTED --
+                             sums over many frames leave fp16's range, and saf_merge_finalize is fp32-only) */
   int32_t accum_mode;     /* saf_accum_mode */
   float trunc;            /* truncation distance in metres (self.trunc) */
   const float* axis_x;    /* [nx] */
@@ -119,7 +123,10 @@ int saf_abi_version(void);
 size_t saf_fuse_workspace_bytes(int64_t n_voxels, int32_t feat_dim, int32_t npy, int32_t npx);
 /* The same for ONE volume (its grid, width and feature dtype are known): the brick form's segment pools -- 6.5 GB at
  * 256^3 -- are reserved only when that form would run for it (feat_dim a multiple of 64 that the row kernel does not
- * take, or SAF_WIN_FORM=bricks); the default 512-channel f32 / bf16 volumes end at 0.55 GB.  0 for a bad descriptor. */
+ * take, or SAF_WIN_FORM=bricks); the default 512-channel f32 / bf16 volumes end at 0.55 GB.  0 for a bad descriptor.
+ * An SAF_F16 volume gets what an SAF_BF16 volume gets where the row kernel takes it (feat_dim 512, 1024); at every other width
+ * and under SAF_WIN_FORM=bricks it gets LESS: the brick form does not take fp16, so its pools are never reserved (this entry and
+ * saf_fuse_workspace_bytes_for_frames). */
 size_t saf_fuse_workspace_bytes_for(const saf_volume* vol, int32_t npy, int32_t npx);
 /* The same, with room for the frames' depth images (height x width) re-laid-out in 4 x 8-pixel tiles, four windows of 128
  * frames of them (0.63 GB at 640 x 480): with such a workspace the windowed path's classification gathers depth from the
@@ -149,15 +156,21 @@ int saf_fuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspac
  *    SAF_WINDOW_FRAMES frames one classification launch per 32 frames (projection, depth test, TSDF in registers, one
  *    frame-mask word per voxel; any grid) and one row kernel that reads and writes every touched feature row ONCE per
  *    window.  The row kernel's form (environment SAF_WIN_FORM, read per call):
- *      sums   (default where it applies: f32 volume with feat_dim a multiple of 256, bf16 with a multiple of 512, <= 1024) a
+ *      sums   (default where it applies: f32 volume with feat_dim a multiple of 256, bf16 / fp16 with a multiple of 512, <= 1024) a
  *             row's samples of the window are summed in registers and the row is blended once, (w0 old + sum) / (w0 + k): the
  *             running mean of clipfusion.py:715-721 with the window's k updates folded into one -- feature values within fp32
- *             rounding of frame-after-frame fusion (bf16: one rounding per window instead of one per hit), reproducible
- *             bit for bit from run to run.  For a bf16 volume this form also keeps the window's feature maps in bf16 (rounded
- *             once, to nearest even, when they are re-laid for the taps): exact when the backbone emitted bf16 features
- *             (BASELINE config 3), otherwise one more rounding at the volume's own precision per tap;
+ *             rounding of frame-after-frame fusion (bf16 / fp16: one rounding per window instead of one per hit), reproducible
+ *             bit for bit from run to run.  For a bf16 (fp16) volume this form also keeps the window's feature maps in bf16
+ *             (fp16), rounded once, to nearest even, when they are re-laid for the taps: exact when the backbone emitted features
+ *             of that type (BASELINE config 3), otherwise one more rounding at the volume's own precision per tap.  An fp16
+ *             image has fp16's range: a MAP value beyond +-65504 is +-inf in it, and a row that taps it stores NaN (inf x a tap
+ *             weight of 0) where the rows form and the per-frame pipeline store +-inf;
+ *             SAF_WIN_MAPS16=0 keeps fp32 maps and takes the rows form, SAF_WINDOW_BF16=0 the per-frame pipeline (both: bf16
+ *             and fp16 volumes alike);
  *      rows   the same widths, hits applied one by one in frame order: feature rows bit-identical to the per-frame pipeline;
  *      bricks every other width (and on request): brick-resident rows, map taps shared, fixed-point sums; same contract as sums.
+ *             f32 and bf16 volumes only: an fp16 volume's other widths stay on the per-frame pipeline (saf_fuse_path: 0), and
+ *             SAF_WIN_FORM=bricks on an fp16 volume of a width the row kernel takes gets the default form (sums).
  *    SAF_WINDOW=0 in the environment forces the per-frame pipeline. */
 int saf_fuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_frames,
                     void* workspace, size_t workspace_bytes, uint64_t* stats, void* stream);
@@ -471,7 +484,7 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for
  * marching-cubes vertices given in voxel-index coordinates, grid = (v + 0.5) * (1/nvox) * 2 - 1 and
  * 3-D grid_sample(align_corners=False, zeros padding) of the volume:
- *   out_feat [V,D] f32   trilinear sample of clip_feat (volume dtype f32 or bf16)
+ *   out_feat [V,D] f32   trilinear sample of clip_feat (volume dtype f32, bf16 or fp16: 16-bit rows are widened exactly, one fp32 arithmetic)
  *   out_rgb  [V,3] f32   trilinear sample of rgb, clamped to [0,1]
  *   out_obj  [V]   f32   nearest sample of obj_idx [N] i32            (optional pair, may be NULL)
  *   out_seg  [V,3] f32   nearest sample of seg_color [N,3] f32, clamped (optional pair, may be NULL)
@@ -544,7 +557,7 @@ int saf_gather_rows(const void* src, int64_t n_src_rows, int64_t row_bytes, cons
  *              (nx, ny, nz, -1, -1, -1) and zeros elsewhere
  *   n_fused    [K] i64 and weight_sum [K] i64: the FUSED members (vol->weight > 0) and the sum of their weights
  *   rgb_mean   [K,3] f32 mean over the fused members of vol->rgb clamped to [0, 1] (the clamp of saf_sample_vertices)
- *   feat_mean  [K,D] f32 mean over the fused members of the normalised feature row (volume dtype f32 or bf16, any feat_dim >= 1;
+ *   feat_mean  [K,D] f32 mean over the fused members of the normalised feature row (volume dtype f32 or bf16; SAF_F16 volumes: SAF_E_UNSUPPORTED; any feat_dim >= 1;
  *              rows on 16-byte boundaries are read 16 bytes per lane, others element by element); 0 where n_fused is 0
  *   normalize  SAF_NORM_L2 (f / |f|, NaN -> 0: a zero row contributes zeros and still counts in n_fused) or SAF_NORM_L2_CLAMP
  *              (f / max(|f|, 0.1)).  SAF_NORM_NONE returns SAF_E_UNSUPPORTED: raw rows have no bounded range, and the sums below

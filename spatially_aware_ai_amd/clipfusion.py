@@ -84,8 +84,8 @@ class _FusionVolumeMixin:
         self.accum_mode = _abi.SAF_RUNNING_MEAN
         self.register_buffer("tsdf", zeros(n, dtype=torch.float32))
         self.register_buffer("rgb", zeros((n, 3), dtype=torch.float32))
-        if feat_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("feat_dtype must be torch.float32 (the reference layout) or torch.bfloat16")
+        if feat_dtype not in _DT:
+            raise ValueError("feat_dtype must be torch.float32 (the reference layout), torch.bfloat16 or torch.float16")
         self.register_buffer("clip_feat", zeros((n, feat_dim), dtype=feat_dtype))
         self.register_buffer("weight", zeros(n, dtype=torch.int32))
         self.register_buffer("tsdf_weight", zeros(n, dtype=torch.int32))
@@ -147,7 +147,7 @@ class _FusionVolumeMixin:
         p = _abi.ptr
         return _abi.SafVolume(
             nx, ny, nz, int(self.n_clip_feats), 0 if labels is None else int(labels.shape[1]),
-            _abi.SAF_BF16 if b["clip_feat"].dtype == torch.bfloat16 else _abi.SAF_F32, int(self.accum_mode),
+            _DT[b["clip_feat"].dtype], int(self.accum_mode),
             float(self.trunc),
             p(b["axis_x"]), p(b["axis_y"]), p(b["axis_z"]),
             p(b["tsdf"]), p(b["tsdf_weight"]), p(b["weight"]), p(b["rgb"]), p(b["clip_feat"]), p(labels),
@@ -251,9 +251,9 @@ class _FusionVolumeMixin:
         if not self.__dict__.get("defer_frames", True) or bsz > self._DEFER_MAX_BATCH:
             return False
         d = int(self.n_clip_feats)
-        bf16 = self._buffers["clip_feat"].dtype == torch.bfloat16
+        rows16 = self._buffers["clip_feat"].dtype != torch.float32  # bf16 and fp16 rows: 8 channels per 16-byte unit
         # the shapes saf_fuse_frames takes on the windowed path (include/saf.h); others gain nothing from a queue
-        return d <= 1024 and d % (512 if bf16 else 256) == 0 and npy + 3 <= 255 and npx + 3 <= 255
+        return d <= 1024 and d % (512 if rows16 else 256) == 0 and npy + 3 <= 255 and npx + 3 <= 255
 
     def _fuse(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None, rgb_bilinear=False, lazy_feat=None):
         """``lazy_feat`` = (fn, (C, npy, npx)) instead of ``clip_feat_img``: the feature maps of these frames are
@@ -267,6 +267,10 @@ class _FusionVolumeMixin:
                 "this volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
                 "(distributed.gather_shards, or merge_volumes(..., gather=True)) before fusing more frames"
             )
+        if self.accum_mode == _abi.SAF_SUM and self._buffers["clip_feat"].dtype == torch.float16:
+            # (saf_fuse_frames refuses it too; here, so that no such frame is ever queued)
+            raise SafError("SAF_SUM into an fp16 volume is not supported: sums over many frames leave fp16's range (65504) and "
+                           "saf_merge_finalize takes fp32 sums only -- accumulate in torch.float32")
         if clip_feat_img is None:
             fn, fshape = lazy_feat
             lazy_ok = self._defer_ok(bsz, fshape[1], fshape[2]) and all(
@@ -745,8 +749,11 @@ class _FusionVolumeMixin:
         # runs are comparable bit for bit only under the same form
         form = os.environ.get("SAF_WIN_FORM", "sums")
         form = {"s": "sums", "r": "rows", "b": "bricks"}.get(form[:1], "sums")
-        if form == "sums" and self._buffers["clip_feat"].dtype == torch.bfloat16:
-            form = "rows (SAF_WIN_MAPS16=0)" if os.environ.get("SAF_WIN_MAPS16", "1")[:1] == "0" else "sums, bf16 map images"
+        maps16 = {torch.bfloat16: "bf16", torch.float16: "fp16"}.get(self._buffers["clip_feat"].dtype)
+        if form == "bricks" and maps16 == "fp16":
+            form = "sums"  # the brick form does not take fp16 rows: such a request gets the default form
+        if form == "sums" and maps16 is not None:
+            form = "rows (SAF_WIN_MAPS16=0)" if os.environ.get("SAF_WIN_MAPS16", "1")[:1] == "0" else f"sums, {maps16} map images"
         # the windowed path's frame cull: (brick, frame) pairs tested / dropped by reason (include/saf.h, stats[8..12])
         cull = {"pairs": s[8], "behind": s[9], "far": s[10], "frustum": s[11], "occluded": s[12]}
         return {"valid": s[0], "tsdf_valid": s[1], "frames": s[2], "labels_dropped": s[3], "window_rows": s[5],
@@ -846,7 +853,7 @@ class _FusionVolumeMixin:
     def render_query(self, text_features, pose, K, height, width, epilogue="softmax", scale=100.0, normalize=True, **render_kw):
         """``render`` plus ``relevance`` [H,W,L] f32: the text query of ``Clip.run_query`` (epilogue "softmax", or the raw
         "scores") over the feature rows of the voxels the pixels see -- saf_gather_rows on ``clip_feat``, then the scan every
-        other query uses (fp32 and bf16 volumes).  Miss pixels get 0 in every column.  (Feature surgery weighs the labels over
+        other query uses (fp32, bf16 and fp16 volumes).  Miss pixels get 0 in every column.  (Feature surgery weighs the labels over
         the whole row set: not offered per view.)"""
         epi = {"scores": _abi.SAF_Q_SCORES, "softmax": _abi.SAF_Q_SOFTMAX}.get(epilogue)
         if epi is None:

@@ -1230,7 +1230,7 @@ int launch_fuse_bricks(const KVol& kv, const WinArgs& wa, const WinTable* tab, c
   hipLaunchKernelGGL(chan_max_kernel, dim3((kv.D + 255) / 256, (wa.F + 7) / 8), dim3(256), 0, s, map_imgs,
                      (int)(img_bytes / sizeof(float)), kv.D, wa.npy * wa.npx, wa.F, cmax);
   if (!split) hipLaunchKernelGGL(cam_table_kernel, dim3(1), dim3(128), 0, s, tab, wa.F, const_cast<float*>(cams));
-  const bool sum = kv.accum == SAF_SUM, bf16 = kv.bf16 != 0;
+  const bool sum = kv.accum == SAF_SUM, bf16 = kv.e16 == kE16Bf16;
   // behind a build kernel: the walk of the pool's segments (no build code in it), then the overflow list, if any, by a small
   // launch of the instantiation that can build; without a build kernel that instantiation does everything
   BrickFn fn, fn_re;

@@ -55,6 +55,23 @@ __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
+// fp16 <-> f32 exactly as PyTorch does it: widening is exact (subnormals included), narrowing is ONE IEEE conversion, round to
+// nearest even, subnormals kept, +-inf beyond +-65504 (v_cvt_f16_f32 under the kernels' default float mode: round-to-nearest,
+// f16 denormals on; never the round-toward-zero pack conversion).
+__device__ __forceinline__ float f16_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float f16_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+__device__ __forceinline__ uint32_t f32_to_f16_bits(float f) {
+  return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f);
+}
+__device__ __forceinline__ uint32_t pack_f16(float lo, float hi) { return f32_to_f16_bits(lo) | (f32_to_f16_bits(hi) << 16); }
+// The two 16-bit element types of a feature volume behind one name (F16: IEEE half; else bfloat16).
+template <bool F16>
+__device__ __forceinline__ float h16_lo(uint32_t w) { return F16 ? f16_lo(w) : bf16_lo(w); }
+template <bool F16>
+__device__ __forceinline__ float h16_hi(uint32_t w) { return F16 ? f16_hi(w) : bf16_hi(w); }
+template <bool F16>
+__device__ __forceinline__ uint32_t pack_h16(float lo, float hi) { return F16 ? pack_f16(lo, hi) : pack_bf16(lo, hi); }
+
 // n / d for n < 2^31 by multiply-shift (exact; see saf_fuse.hip make_fastdiv).
 struct FastDiv {
   uint32_t mul, shift, d, pad;

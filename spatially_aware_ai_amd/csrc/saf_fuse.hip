@@ -527,8 +527,9 @@ __device__ __forceinline__ RowCtx fetch_row(int src, uint32_t n_l, float a_l, fl
 // row inside the SAME wave instruction as its owner (same loads, same stores).
 // BF16: the feature volume holds bfloat16 (a 16-byte lane access = 8 channels = two map chunks);
 // samples are blended in fp32 exactly as for the fp32 volume and rounded to nearest-even once per
-// update.
-template <int CPL, int R, bool G64, bool LDS_MAP, bool SUM, bool BF16>
+// update.  F16 (with BF16): the 16-bit elements are IEEE half instead -- same layout, same fp32 blend, one nearest-even
+// conversion per update (h16_lo / h16_hi / pack_h16, saf_common.h).
+template <int CPL, int R, bool G64, bool LDS_MAP, bool SUM, bool BF16, bool F16 = false>
 __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame f,
                                                                   const unsigned long long* __restrict__ counts,
                                                                   const uint32_t* __restrict__ lists,
@@ -619,14 +620,14 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
     if (BF16) {                                                                                        \
       const uint32_t w0_ = __builtin_bit_cast(uint32_t, old_[c].x), w1_ = __builtin_bit_cast(uint32_t, old_[c].y); \
       const uint32_t w2_ = __builtin_bit_cast(uint32_t, old_[c].z), w3_ = __builtin_bit_cast(uint32_t, old_[c].w); \
-      const float4 n0_ = blend(SAF_TAPS(c, 0, ctx_), make_float4(bf16_lo(w0_), bf16_hi(w0_), bf16_lo(w1_), bf16_hi(w1_)), \
+      const float4 n0_ = blend(SAF_TAPS(c, 0, ctx_), make_float4(h16_lo<F16>(w0_), h16_hi<F16>(w0_), h16_lo<F16>(w1_), h16_hi<F16>(w1_)), \
                                (ctx_).a, (ctx_).b, sum);                                               \
-      const float4 n1_ = blend(SAF_TAPS(c, KV - 1, ctx_), make_float4(bf16_lo(w2_), bf16_hi(w2_), bf16_lo(w3_), bf16_hi(w3_)), \
+      const float4 n1_ = blend(SAF_TAPS(c, KV - 1, ctx_), make_float4(h16_lo<F16>(w2_), h16_hi<F16>(w2_), h16_lo<F16>(w3_), h16_hi<F16>(w3_)), \
                                (ctx_).a, (ctx_).b, sum);                                               \
-      out_.x = __builtin_bit_cast(float, pack_bf16(n0_.x, n0_.y));                                     \
-      out_.y = __builtin_bit_cast(float, pack_bf16(n0_.z, n0_.w));                                     \
-      out_.z = __builtin_bit_cast(float, pack_bf16(n1_.x, n1_.y));                                     \
-      out_.w = __builtin_bit_cast(float, pack_bf16(n1_.z, n1_.w));                                     \
+      out_.x = __builtin_bit_cast(float, pack_h16<F16>(n0_.x, n0_.y));                                     \
+      out_.y = __builtin_bit_cast(float, pack_h16<F16>(n0_.z, n0_.w));                                     \
+      out_.z = __builtin_bit_cast(float, pack_h16<F16>(n1_.x, n1_.y));                                     \
+      out_.w = __builtin_bit_cast(float, pack_h16<F16>(n1_.z, n1_.w));                                     \
     } else {                                                                                           \
       out_ = blend(SAF_TAPS(c, 0, ctx_), old_[c], (ctx_).a, (ctx_).b, sum);                            \
     }                                                                                                  \
@@ -685,8 +686,15 @@ FuseFn pick_rows3(bool g64, bool lds) {
   return lds ? fuse_rows_kernel<CPL, R, false, true, SUM, BF16> : fuse_rows_kernel<CPL, R, false, false, SUM, BF16>;
 }
 template <int CPL, int R>
-FuseFn pick_rows(bool g64, bool lds, bool sum, bool bf16) {
-  if (bf16) return sum ? pick_rows3<CPL, R, true, true>(g64, lds) : pick_rows3<CPL, R, false, true>(g64, lds);
+FuseFn pick_rows_f16(bool g64, bool lds) {  // fp16 volumes: running mean only (make_kvol)
+  if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, false, true, true> : fuse_rows_kernel<CPL, R, true, false, false, true, true>;
+  return lds ? fuse_rows_kernel<CPL, R, false, true, false, true, true> : fuse_rows_kernel<CPL, R, false, false, false, true, true>;
+}
+// e16: the volume's 16-bit element type (KVol::e16); fp16 volumes have no SAF_SUM (make_kvol)
+template <int CPL, int R>
+FuseFn pick_rows(bool g64, bool lds, bool sum, int e16) {
+  if (e16 == kE16Half) return pick_rows_f16<CPL, R>(g64, lds);
+  if (e16) return sum ? pick_rows3<CPL, R, true, true>(g64, lds) : pick_rows3<CPL, R, false, true>(g64, lds);
   return sum ? pick_rows3<CPL, R, true, false>(g64, lds) : pick_rows3<CPL, R, false, false>(g64, lds);
 }
 
@@ -695,10 +703,10 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
                 const unsigned long long* sweep_done, unsigned long long sweep_target, bool shared_cus, const Knobs& kn,
                 hipStream_t s) {
   const int D = kv.D, P = kf.npy * kf.npx;
-  const bool bf16 = kv.bf16 != 0;
+  const bool rows16 = kv.e16 != 0;  // 16-bit rows (bf16 or fp16): 8 channels per 16-byte unit
   const int VEC = (D % 4 == 0) ? 4 : 1;
   const int DV = D / VEC;
-  const int units = bf16 ? D / 8 : DV;  // 16-byte row units (vector path)
+  const int units = rows16 ? D / 8 : DV;  // 16-byte row units (vector path)
   int g_log2 = 0;
   while ((1 << g_log2) < units && g_log2 < 6) ++g_log2;
   const int G = 1 << g_log2;
@@ -706,22 +714,22 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
   const bool lds = w.lds_map;
   const bool sum = kv.accum == SAF_SUM;
   FuseFn fn;
-  if (bf16) {
-    if (D % 8 != 0 || cpl > 4) return fail(SAF_E_UNSUPPORTED, "bf16 volume needs feat_dim %% 8 == 0 and <= 2048");
+  if (rows16) {
+    if (D % 8 != 0 || cpl > 4) return fail(SAF_E_UNSUPPORTED, "a bf16 / fp16 volume needs feat_dim %% 8 == 0 and <= 2048");
     const bool g64 = G == 64;
     switch (cpl) {
-      case 1: fn = pick_rows<1, 8>(g64, lds, sum, true); break;
-      case 2: fn = pick_rows<2, 4>(g64, lds, sum, true); break;
-      case 3: fn = pick_rows<3, 2>(g64, lds, sum, true); break;
-      default: fn = pick_rows<4, 2>(g64, lds, sum, true); break;
+      case 1: fn = pick_rows<1, 8>(g64, lds, sum, kv.e16); break;
+      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kv.e16); break;
+      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kv.e16); break;
+      default: fn = pick_rows<4, 2>(g64, lds, sum, kv.e16); break;
     }
   } else if (VEC == 4 && cpl >= 1 && cpl <= 4) {
     const bool g64 = G == 64;
     switch (cpl) {
-      case 1: fn = pick_rows<1, 4>(g64, lds, sum, false); break;
-      case 2: fn = pick_rows<2, 4>(g64, lds, sum, false); break;
-      case 3: fn = pick_rows<3, 2>(g64, lds, sum, false); break;
-      default: fn = pick_rows<4, 2>(g64, lds, sum, false); break;
+      case 1: fn = pick_rows<1, 4>(g64, lds, sum, kE16None); break;
+      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kE16None); break;
+      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kE16None); break;
+      default: fn = pick_rows<4, 2>(g64, lds, sum, kE16None); break;
     }
   } else if (VEC == 4) {
     fn = pick_lds<4, 0, 1>(lds);
@@ -756,12 +764,15 @@ int make_kvol(const saf_volume* vol, KVol* kv) {
     return fail(SAF_E_INVALID, "bad volume shape %dx%dx%d D=%d", vol->nx, vol->ny, vol->nz, vol->feat_dim);
   const int64_t N = n_voxels(vol);
   if (N >= (1ll << 31)) return fail(SAF_E_UNSUPPORTED, "volumes of 2^31 voxels or more are not supported");
-  if (vol->feat_dtype != SAF_F32 && vol->feat_dtype != SAF_BF16)
-    return fail(SAF_E_UNSUPPORTED, "feat_dtype %d: SAF_F32 and SAF_BF16 are implemented", vol->feat_dtype);
-  if (vol->feat_dtype == SAF_BF16 && (vol->feat_dim % 8 != 0 || ((uintptr_t)vol->clip_feat & 15)))
-    return fail(SAF_E_UNSUPPORTED, "a bf16 volume needs feat_dim %% 8 == 0 and a 16-byte aligned buffer");
+  if (vol->feat_dtype != SAF_F32 && vol->feat_dtype != SAF_BF16 && vol->feat_dtype != SAF_F16)
+    return fail(SAF_E_UNSUPPORTED, "feat_dtype %d: SAF_F32, SAF_BF16 and SAF_F16 are implemented", vol->feat_dtype);
+  if (vol->feat_dtype != SAF_F32 && (vol->feat_dim % 8 != 0 || ((uintptr_t)vol->clip_feat & 15)))
+    return fail(SAF_E_UNSUPPORTED, "a bf16 / fp16 volume needs feat_dim %% 8 == 0 and a 16-byte aligned buffer");
   if (vol->accum_mode != SAF_RUNNING_MEAN && vol->accum_mode != SAF_SUM)
     return fail(SAF_E_INVALID, "bad accum_mode %d", vol->accum_mode);
+  if (vol->feat_dtype == SAF_F16 && vol->accum_mode == SAF_SUM)
+    return fail(SAF_E_UNSUPPORTED, "SAF_SUM into an fp16 volume is not supported: sums over many frames leave fp16's range (65504) "
+                                   "and saf_merge_finalize takes fp32 sums only -- accumulate in SAF_F32");
   if (!vol->axis_x || !vol->axis_y || !vol->axis_z || !vol->tsdf || !vol->tsdf_weight || !vol->weight || !vol->rgb ||
       !vol->clip_feat)
     return fail(SAF_E_INVALID, "volume has a NULL buffer");
@@ -773,7 +784,7 @@ int make_kvol(const saf_volume* vol, KVol* kv) {
   kv->D = vol->feat_dim;
   kv->n_classes = vol->labels_one_hot ? vol->n_classes : 0;
   kv->accum = vol->accum_mode;
-  kv->bf16 = vol->feat_dtype == SAF_BF16;
+  kv->e16 = vol->feat_dtype == SAF_BF16 ? kE16Bf16 : (vol->feat_dtype == SAF_F16 ? kE16Half : kE16None);
   kv->N = (uint32_t)N;
   kv->trunc = vol->trunc;
   kv->ax = vol->axis_x; kv->ay = vol->axis_y; kv->az = vol->axis_z;

@@ -25,9 +25,12 @@ struct saf_profiler {
 
 namespace saf {
 
+// element type of a volume's feature rows: fp32, or one of the two 16-bit types (same row layout: 8 channels per 16 bytes)
+enum { kE16None = 0, kE16Bf16 = 1, kE16Half = 2 };
+
 // kernel-side descriptors (POD, passed by value; shared by both translation units)
 struct KVol {
-  int nx, ny, nz, D, n_classes, accum, bf16;
+  int nx, ny, nz, D, n_classes, accum, e16;  // e16: kE16None / kE16Bf16 / kE16Half
   uint32_t N;
   float trunc;
   const float *ax, *ay, *az;
@@ -302,8 +305,8 @@ struct FuseRoute {
 };
 FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn);
 // The two width rules.  The row kernels move whole 1 KiB pieces of a row per wave instruction: feat_dim a multiple of 256 up to
-// 1024 -- of 512 for bf16, where a lane moves 8 channels.  The brick form: brick_form_takes (saf_window_dev.h).
-inline bool row_kernel_takes(int D, bool bf16) { return D % 256 == 0 && D <= 1024 && (!bf16 || D % 512 == 0); }
+// 1024 -- of 512 for 16-bit rows (bf16 and fp16), where a lane moves 8 channels.  The brick form: brick_form_takes (saf_window_dev.h).
+inline bool row_kernel_takes(int D, bool rows16) { return D % 256 == 0 && D <= 1024 && (!rows16 || D % 512 == 0); }
 // Whether a call on such a volume asks for the brick form (it gets it where the workspace has room for its pools): the default
 // for the widths the row kernel does not take, what SAF_WIN_FORM=bricks asks for, never under SAF_WIN_FORM=rows.
 bool brick_form_applies(const KVol& kv, const Knobs& kn);
@@ -351,7 +354,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
 int clear_rows(void* feat, const int* weight, int64_t first, int64_t n_rows, int esz, int row_bytes, const uint32_t* masks,
                size_t mask_plane, int n_planes, const Knobs& kn, hipStream_t s);
 inline int launch_clear_unwritten(const KVol& kv, const uint32_t* masks, size_t mask_plane, int n_planes, const Knobs& kn, hipStream_t s) {
-  const int esz = kv.bf16 ? 2 : 4;
+  const int esz = kv.e16 ? 2 : 4;
   return clear_rows(kv.feat, kv.weight, 0, (int64_t)kv.N, esz, kv.D * esz, masks, mask_plane, n_planes, kn, s);
 }
 KVol slab_kvol(const KVol& kv, int x0, int nx);

@@ -166,7 +166,8 @@ __device__ __forceinline__ Axis3 axis_setup(float v_index, int size) {
   return a;
 }
 
-template <bool BF16>
+// FT: the volume's feature dtype (SAF_F32 / SAF_BF16 / SAF_F16); 16-bit rows are widened (exactly), the arithmetic is one
+template <int FT>
 __global__ __launch_bounds__(256) void sample_vertices_kernel(
     int nx, int ny, int nz, int D, const void* __restrict__ feat, const float* __restrict__ rgb,
     const float* __restrict__ verts, int64_t n_verts, float* __restrict__ out_feat, float* __restrict__ out_rgb,
@@ -196,8 +197,9 @@ __global__ __launch_bounds__(256) void sample_vertices_kernel(
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         if (row[c] >= 0) {
-          const float val = BF16 ? __builtin_bit_cast(float, (uint32_t) static_cast<const uint16_t*>(feat)[row[c] * D + ch] << 16)
-                                 : static_cast<const float*>(feat)[row[c] * D + ch];
+          const float val = FT == SAF_BF16 ? bf16_lo(static_cast<const uint16_t*>(feat)[row[c] * D + ch])
+                            : FT == SAF_F16 ? f16_lo(static_cast<const uint16_t*>(feat)[row[c] * D + ch])
+                                            : static_cast<const float*>(feat)[row[c] * D + ch];
           acc += val * w[c];
         }
       }
@@ -417,7 +419,7 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
   if (!vol || !vol->clip_feat || !vol->rgb || !verts_index || !out_feat || !out_rgb || n_verts < 0 ||
       (obj_idx && !out_obj) || (seg_color && !out_seg))
     return fail(SAF_E_INVALID, "sample_vertices: bad arguments");
-  if (vol->feat_dtype != SAF_F32 && vol->feat_dtype != SAF_BF16)
+  if (vol->feat_dtype != SAF_F32 && vol->feat_dtype != SAF_BF16 && vol->feat_dtype != SAF_F16)
     return fail(SAF_E_UNSUPPORTED, "sample_vertices: feature dtype %d", vol->feat_dtype);
   if (n_verts == 0) return SAF_OK;
   int64_t blocks = (n_verts + 3) / 4;
@@ -425,11 +427,15 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
   if (blocks > cap) blocks = cap;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (vol->feat_dtype == SAF_BF16)
-    hipLaunchKernelGGL(sample_vertices_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_BF16>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+                       vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
+                       seg_color, out_seg);
+  else if (vol->feat_dtype == SAF_F16)
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F16>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
   else
-    hipLaunchKernelGGL(sample_vertices_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F32>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
   return check_launch("sample_vertices_kernel");

@@ -82,19 +82,19 @@ __device__ __forceinline__ void file_frames(const ClsArgs& ca, WinTable* __restr
   }
 }
 
-// img_elems: elements (f32, or bf16 when `as_bf16`) from one frame's image to the next.  bf16 images (bf16 volumes in the
+// img_elems: elements (f32, or 16-bit when `e16` names bf16 / fp16) from one frame's image to the next.  16-bit images (bf16 and fp16 volumes in the
 // order-free form): a tap is 16 bytes per 8 channels instead of 32 -- half the bytes through the L1 path that bounds the row
 // kernel, and the window's table (128 frames x 36 cells x D) at 4.7 MB instead of 9.4 sits in an XCD's L2.  The features are
-// rounded ONCE to the volume's precision (round to nearest even); exact when the backbone emitted bf16 (BASELINE config 3).
+// rounded ONCE to the volume's precision (round to nearest even); exact when the backbone emitted that type (bf16: BASELINE config 3).
 __global__ __launch_bounds__(256) void prep_rows_kernel(const WinTable* __restrict__ tab, void* __restrict__ imgs,
-                                                        int img_elems, int D, int P, int as_bf16) {
+                                                        int img_elems, int D, int P, int e16) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= (P + 1) * D) return;
   const float* __restrict__ feat_map = tab->feat_map[blockIdx.y];
   const int c = o % D, p = o / D;
   const float x = p < P ? feat_map[(size_t)c * P + p] : 0.0f;
-  if (as_bf16)
-    static_cast<uint16_t*>(imgs)[(size_t)blockIdx.y * img_elems + o] = (uint16_t)f32_to_bf16_bits(x);
+  if (e16)
+    static_cast<uint16_t*>(imgs)[(size_t)blockIdx.y * img_elems + o] = (uint16_t)(e16 == kE16Half ? f32_to_f16_bits(x) : f32_to_bf16_bits(x));
   else
     static_cast<float*>(imgs)[(size_t)blockIdx.y * img_elems + o] = x;
 }
@@ -764,7 +764,7 @@ __device__ __forceinline__ WinGroupOffs win_group_offsets(const WinCtx<CPL>& cx,
 // NB groups (runs of lanes hl[u] .. hl[u + 1] - 1 of hits in group order): request the four map rows of every group, then
 // blend group after group into the LDS rows (the waits are counted: group u is processed while the rows of groups
 // u+1.. are still in flight).
-template <int NB, int CPL, bool SUM, bool BF16, int SR>
+template <int NB, int CPL, bool SUM, bool BF16, int SR, bool F16>
 __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)[NB + 1], bool first, const WinGroupOffs& go,
                                           const WinHit& rec, const WinRaw<SR, BF16 ? CPL / 2 : 1>& raw) {
   float4 tp[NB][4][CPL];
@@ -797,8 +797,8 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
 #pragma unroll
           for (int k = 0; k < UPL; ++k) {
             const uint4 w = raw.u[r * UPL + k];
-            cx.rows[(r * CPL + 2 * k) * 64 + cx.lane] = make_float4(bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y));
-            cx.rows[(r * CPL + 2 * k + 1) * 64 + cx.lane] = make_float4(bf16_lo(w.z), bf16_hi(w.z), bf16_lo(w.w), bf16_hi(w.w));
+            cx.rows[(r * CPL + 2 * k) * 64 + cx.lane] = make_float4(h16_lo<F16>(w.x), h16_hi<F16>(w.x), h16_lo<F16>(w.y), h16_hi<F16>(w.y));
+            cx.rows[(r * CPL + 2 * k + 1) * 64 + cx.lane] = make_float4(h16_lo<F16>(w.z), h16_hi<F16>(w.z), h16_lo<F16>(w.w), h16_hi<F16>(w.w));
           }
         }
       }
@@ -822,9 +822,9 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
         float4* rp = cx.rows + (r * CPL + c) * 64 + cx.lane;
         const float4 sv = lerp_taps(tp[u][0][c], tp[u][1][c], tp[u][2][c], tp[u][3][c], w);
         float4 nv = blend(sv, *rp, a, b, SUM);
-        if (BF16) {  // the per-frame path stores bf16 after every hit: round to nearest even, keep as f32
-          const uint32_t p01 = pack_bf16(nv.x, nv.y), p23 = pack_bf16(nv.z, nv.w);  // two hardware conversions
-          nv.x = bf16_lo(p01); nv.y = bf16_hi(p01); nv.z = bf16_lo(p23); nv.w = bf16_hi(p23);
+        if (BF16) {  // the per-frame path stores bf16 (fp16) after every hit: round to nearest even, keep as f32
+          const uint32_t p01 = pack_h16<F16>(nv.x, nv.y), p23 = pack_h16<F16>(nv.z, nv.w);  // two hardware conversions
+          nv.x = h16_lo<F16>(p01); nv.y = h16_hi<F16>(p01); nv.z = h16_lo<F16>(p23); nv.w = h16_hi<F16>(p23);
         }
         *rp = nv;
       }
@@ -859,7 +859,7 @@ __device__ __forceinline__ void of_add_row(win_v2f (&a)[2 * CPL], const float4 (
 // So the loops are turned inside out: for every group u and every row R of the sub-chunk (both unrolled), the lanes
 // rm[R] & [hl[u], hl[u + 1]) are that row's hits of that group -- usually none or one -- and each body adds into acc[R]
 // from tp[u] in place.  Within a row the hits stay in (frame, lane) order: the sum is reproducible.
-template <int NB, int CPL, bool SUM, bool BF16, int SR>
+template <int NB, int CPL, bool SUM, bool BF16, int SR, bool F16>
 __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&hl)[NB + 1], int nb, const WinGroupOffs& go,
                                              const WinHit& rec, const unsigned long long (&rm)[SR],
                                              win_v2f (&acc)[SR][2 * CPL]) {
@@ -900,10 +900,10 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
             for (int t = 0; t < 4; ++t) {
               const uint4 w = tq[u][t][k];
               const win_v2f ww = {wt[t], wt[t]};
-              acc[R][4 * k + 0] = __builtin_elementwise_fma((win_v2f){bf16_lo(w.x), bf16_hi(w.x)}, ww, acc[R][4 * k + 0]);
-              acc[R][4 * k + 1] = __builtin_elementwise_fma((win_v2f){bf16_lo(w.y), bf16_hi(w.y)}, ww, acc[R][4 * k + 1]);
-              acc[R][4 * k + 2] = __builtin_elementwise_fma((win_v2f){bf16_lo(w.z), bf16_hi(w.z)}, ww, acc[R][4 * k + 2]);
-              acc[R][4 * k + 3] = __builtin_elementwise_fma((win_v2f){bf16_lo(w.w), bf16_hi(w.w)}, ww, acc[R][4 * k + 3]);
+              acc[R][4 * k + 0] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.x), h16_hi<F16>(w.x)}, ww, acc[R][4 * k + 0]);
+              acc[R][4 * k + 1] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.y), h16_hi<F16>(w.y)}, ww, acc[R][4 * k + 1]);
+              acc[R][4 * k + 2] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.z), h16_hi<F16>(w.z)}, ww, acc[R][4 * k + 2]);
+              acc[R][4 * k + 3] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.w), h16_hi<F16>(w.w)}, ww, acc[R][4 * k + 3]);
             }
           }
         }
@@ -966,7 +966,9 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
 
 
 
-template <int CPL, bool SUM, bool BF16, bool OF>
+// BF16: 16-bit rows (8 channels per 16 bytes); F16 (with BF16): their elements are IEEE half instead of bfloat16 -- the same
+// layout, loads, stores and fp32 arithmetic, another widening and another (nearest-even) narrowing (h16_lo / h16_hi / pack_h16).
+template <int CPL, bool SUM, bool BF16, bool OF, bool F16 = false>
 __device__ __forceinline__ void
 fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
                  unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
@@ -1476,15 +1478,15 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             if constexpr (OF) {
               // ONE instantiation: a batch with fewer than P groups has empty groups at its end (hl[u] = hl[u + 1] = n_pass), whose
               // taps are "outside the map" -- no memory request -- and whose hit loops find no lane
-              win_batch_of<P, CPL, SUM, BF16, SR>(cx, hl, nb, go, srt, rm, acc);
+              win_batch_of<P, CPL, SUM, BF16, SR, F16>(cx, hl, nb, go, srt, rm, acc);
             } else {
             switch (nb) {
-                case 1: { const int h1[2] = {hl[0], hl[1]}; win_batch<1, CPL, SUM, BF16, SR>(cx, h1, first, go, srt, raw); break; }
-                case 2: if constexpr (P >= 2) { const int h2[3] = {hl[0], hl[1], hl[2]}; win_batch<2, CPL, SUM, BF16, SR>(cx, h2, first, go, srt, raw); } break;
-                case 3: if constexpr (P >= 3) { const int h3[4] = {hl[0], hl[1], hl[2], hl[3]}; win_batch<3, CPL, SUM, BF16, SR>(cx, h3, first, go, srt, raw); } break;
-                case 4: if constexpr (P >= 4) { const int h4[5] = {hl[0], hl[1], hl[2], hl[3], hl[4]}; win_batch<4, CPL, SUM, BF16, SR>(cx, h4, first, go, srt, raw); } break;
-                case 5: if constexpr (P >= 5) { const int h5[6] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5]}; win_batch<5, CPL, SUM, BF16, SR>(cx, h5, first, go, srt, raw); } break;
-                default: if constexpr (P >= 6) { const int h6[7] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5], hl[6]}; win_batch<6, CPL, SUM, BF16, SR>(cx, h6, first, go, srt, raw); } break;
+                case 1: { const int h1[2] = {hl[0], hl[1]}; win_batch<1, CPL, SUM, BF16, SR, F16>(cx, h1, first, go, srt, raw); break; }
+                case 2: if constexpr (P >= 2) { const int h2[3] = {hl[0], hl[1], hl[2]}; win_batch<2, CPL, SUM, BF16, SR, F16>(cx, h2, first, go, srt, raw); } break;
+                case 3: if constexpr (P >= 3) { const int h3[4] = {hl[0], hl[1], hl[2], hl[3]}; win_batch<3, CPL, SUM, BF16, SR, F16>(cx, h3, first, go, srt, raw); } break;
+                case 4: if constexpr (P >= 4) { const int h4[5] = {hl[0], hl[1], hl[2], hl[3], hl[4]}; win_batch<4, CPL, SUM, BF16, SR, F16>(cx, h4, first, go, srt, raw); } break;
+                case 5: if constexpr (P >= 5) { const int h5[6] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5]}; win_batch<5, CPL, SUM, BF16, SR, F16>(cx, h5, first, go, srt, raw); } break;
+                default: if constexpr (P >= 6) { const int h6[7] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5], hl[6]}; win_batch<6, CPL, SUM, BF16, SR, F16>(cx, h6, first, go, srt, raw); } break;
               }
             }
             first = false;
@@ -1518,10 +1520,10 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                   const uint4 w = raw.u[r * UPL + k];  // + w0 x old (SUM: + old), then the mean, packed into the same registers
                   const win_v2f a0 = acc[r][4 * k], a1 = acc[r][4 * k + 1], a2 = acc[r][4 * k + 2], a3 = acc[r][4 * k + 3];
                   uint4 q;
-                  q.x = pack_bf16(__builtin_fmaf(bf16_lo(w.x), f, a0.x) * fac, __builtin_fmaf(bf16_hi(w.x), f, a0.y) * fac);
-                  q.y = pack_bf16(__builtin_fmaf(bf16_lo(w.y), f, a1.x) * fac, __builtin_fmaf(bf16_hi(w.y), f, a1.y) * fac);
-                  q.z = pack_bf16(__builtin_fmaf(bf16_lo(w.z), f, a2.x) * fac, __builtin_fmaf(bf16_hi(w.z), f, a2.y) * fac);
-                  q.w = pack_bf16(__builtin_fmaf(bf16_lo(w.w), f, a3.x) * fac, __builtin_fmaf(bf16_hi(w.w), f, a3.y) * fac);
+                  q.x = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.x), f, a0.x) * fac, __builtin_fmaf(h16_hi<F16>(w.x), f, a0.y) * fac);
+                  q.y = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.y), f, a1.x) * fac, __builtin_fmaf(h16_hi<F16>(w.y), f, a1.y) * fac);
+                  q.z = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.z), f, a2.x) * fac, __builtin_fmaf(h16_hi<F16>(w.z), f, a2.y) * fac);
+                  q.w = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.w), f, a3.x) * fac, __builtin_fmaf(h16_hi<F16>(w.w), f, a3.y) * fac);
                   raw.u[r * UPL + k] = q;
                   if (!(SAF_WIN_ABL & 8))
                     st_stream(featb + (row / 2) + lane + k * 64, make_float4(__builtin_bit_cast(float, q.x), __builtin_bit_cast(float, q.y),
@@ -1546,11 +1548,11 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
 #pragma unroll
               for (int k = 0; k < UPL; ++k) {
                 const float4 lo = rows[(r * CPL + 2 * k) * 64 + lane], hi = rows[(r * CPL + 2 * k + 1) * 64 + lane];
-                float4 o;  // the LDS values are bf16-exact already: the packing is lossless
-                o.x = __builtin_bit_cast(float, pack_bf16(lo.x, lo.y));
-                o.y = __builtin_bit_cast(float, pack_bf16(lo.z, lo.w));
-                o.z = __builtin_bit_cast(float, pack_bf16(hi.x, hi.y));
-                o.w = __builtin_bit_cast(float, pack_bf16(hi.z, hi.w));
+                float4 o;  // the LDS values are bf16- (fp16-) exact already: the packing is lossless
+                o.x = __builtin_bit_cast(float, pack_h16<F16>(lo.x, lo.y));
+                o.y = __builtin_bit_cast(float, pack_h16<F16>(lo.z, lo.w));
+                o.z = __builtin_bit_cast(float, pack_h16<F16>(hi.x, hi.y));
+                o.w = __builtin_bit_cast(float, pack_h16<F16>(hi.z, hi.w));
                 st_stream(featb + (row / 2) + lane + k * 64, o);
               }
             } else {
@@ -1600,6 +1602,25 @@ fuse_window_kernel_of176(KVol v, WinArgs wa, const WinTable* __restrict__ tab, c
   fuse_window_body<CPL, SUM, BF16, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
 }
 
+// fp16 volumes (running mean only: make_kvol refuses SAF_SUM): the bf16 instantiations' body with F16 set, under the same
+// register budgets.  Kernels of their own, so that the f32 / bf16 kernels keep their names and their code.
+template <int CPL, bool OF>
+__global__ __launch_bounds__(kWinThreads)
+__attribute__((amdgpu_waves_per_eu(OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE, OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE))) void
+fuse_window_kernel_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
+                       unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
+                       const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
+                       int xcd_order) {
+  fuse_window_body<CPL, false, true, OF, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+}
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(SAF_WIN_OF_VGPRS))) void
+fuse_window_kernel_of176_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
+                             unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
+                             const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
+                             int xcd_order) {
+  fuse_window_body<2, false, true, true, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Windowed (voxel-major) path of saf_fuse_frames: see fuse_window_kernel.
 // Workspace: the common header (piece counter), the kWin pixel-major map images of one window, and the
@@ -1629,12 +1650,19 @@ WinLayout win_layout(int64_t n_vox, int D, int P, bool bricks = false, size_t de
 using WinFn = void (*)(KVol, WinArgs, const WinTable*, const float*, int, unsigned long long*, unsigned int*, const uint32_t*,
                        uint32_t, const unsigned long long*, int);
 template <int CPL, bool OF>
-WinFn pick_win(bool sum, bool bf16) {
+WinFn pick_win(bool sum, int e16) {
+  const bool rows16 = e16 != 0;  // 16-bit rows: the kernels' BF16 parameter (bfloat16 unless F16 says half)
+  if (e16 == kE16Half) {
+    if (CPL % 2 != 0 || sum) return nullptr;
+    constexpr int C2 = CPL % 2 == 0 ? CPL : 2;
+    if (OF && CPL == 2 && SAF_WIN_OF_VGPRS > 0) return fuse_window_kernel_of176_f16;
+    return fuse_window_kernel_f16<C2, OF>;
+  }
   if (OF && CPL == 2 && SAF_WIN_OF_VGPRS > 0) {  // the benchmark's kernels: within 176 registers (see fuse_window_kernel_of176)
-    if (bf16) return sum ? fuse_window_kernel_of176<2, true, true> : fuse_window_kernel_of176<2, false, true>;
+    if (rows16) return sum ? fuse_window_kernel_of176<2, true, true> : fuse_window_kernel_of176<2, false, true>;
     return sum ? fuse_window_kernel_of176<2, true, false> : fuse_window_kernel_of176<2, false, false>;
   }
-  if (bf16) {
+  if (rows16) {
     if (CPL % 2 != 0) return nullptr;
     constexpr int C2 = CPL % 2 == 0 ? CPL : 2;
     return sum ? fuse_window_kernel<C2, true, true, OF> : fuse_window_kernel<C2, false, true, OF>;
@@ -1642,9 +1670,9 @@ WinFn pick_win(bool sum, bool bf16) {
   return sum ? fuse_window_kernel<CPL, true, false, OF> : fuse_window_kernel<CPL, false, false, OF>;
 }
 template <int CPL>
-WinFn pick_win(bool sum, bool bf16, bool of, size_t* lds) {
+WinFn pick_win(bool sum, int e16, bool of, size_t* lds) {
   *lds = of ? WinCfg<CPL, true>::total : WinCfg<CPL, false>::total;
-  return of ? pick_win<CPL, true>(sum, bf16) : pick_win<CPL, false>(sum, bf16);
+  return of ? pick_win<CPL, true>(sum, e16) : pick_win<CPL, false>(sum, e16);
 }
 
 }  // namespace
@@ -1661,8 +1689,9 @@ size_t window_workspace_bytes(int64_t n_vox, int D, int P, bool bricks, int H, i
 // for the widths the row kernel takes, bricks for the others.
 // ---------------------------------------------------------------------------------------------
 bool brick_form_applies(const KVol& kv, const Knobs& kn) {
+  if (kv.e16 == kE16Half) return false;  // the brick form takes f32 and bf16 rows: an fp16 volume's other widths stay on the per-frame pipeline
   if (kn.win_form == 'r' || !brick_form_takes(kv.D, kv.nx, kv.ny, kv.nz)) return false;
-  return kn.win_form == 'b' || !row_kernel_takes(kv.D, kv.bf16 != 0);
+  return kn.win_form == 'b' || !row_kernel_takes(kv.D, kv.e16 != 0);
 }
 
 // Without the volume: room for the brick form wherever SOME dtype of this width would ask for it (the grid is unknown).
@@ -1682,8 +1711,10 @@ namespace {
 // another form or SAF_WIN_MAPS16=0 keeps a bf16 volume's map images in fp32 --; else none (kPathPerFrame).
 FusePath window_form(const KVol& kv, const WinLayout& wl, size_t workspace_bytes, const Knobs& kn) {
   if (brick_form_applies(kv, kn) && workspace_bytes > wl.cmax_off && brick_aux_fits(kv, workspace_bytes - wl.cmax_off)) return kPathBricks;
-  if (!row_kernel_takes(kv.D, kv.bf16 != 0)) return kPathPerFrame;
-  const bool sums = (kn.win_form == 0 || kn.win_form == 's') && !(kv.bf16 != 0 && !kn.win_maps16);
+  if (!row_kernel_takes(kv.D, kv.e16 != 0)) return kPathPerFrame;
+  // (SAF_WIN_FORM=bricks on an fp16 volume, which the brick form does not take: the default form, as if unset)
+  const bool dflt = kn.win_form == 0 || kn.win_form == 's' || (kn.win_form == 'b' && kv.e16 == kE16Half);
+  const bool sums = dflt && !(kv.e16 != 0 && !kn.win_maps16);
   return sums ? kPathSums : kPathRows;
 }
 }  // namespace
@@ -1695,7 +1726,7 @@ FusePath window_form(const KVol& kv, const WinLayout& wl, size_t workspace_bytes
 FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn) {
   const FuseRoute per_frame{kPathPerFrame, false};
   if (!kn.window || n_frames < 1) return per_frame;
-  if (kv.bf16 && !kn.window_bf16) return per_frame;
+  if (kv.e16 && !kn.window_bf16) return per_frame;  // (bf16 and fp16 volumes alike)
   const saf_frame& f0 = frames[0];
   const WinLayout wl = win_layout(kv.N, kv.D, f0.npy * f0.npx);
   const FusePath form = window_form(kv, wl, workspace_bytes, kn);
@@ -1766,18 +1797,19 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Kn
   pl->win_lds = 0;
   if (!pl->brick_form) {
     switch (kv.D / 256) {
-      case 1: pl->fn = pick_win<1>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
-      case 2: pl->fn = pick_win<2>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
-      case 3: pl->fn = pick_win<3>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
-      default: pl->fn = pick_win<4>(pl->sum, kv.bf16 != 0, pl->of, &pl->win_lds); break;
+      case 1: pl->fn = pick_win<1>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
+      case 2: pl->fn = pick_win<2>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
+      case 3: pl->fn = pick_win<3>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
+      default: pl->fn = pick_win<4>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
     }
     if (!pl->fn) return fail(SAF_E_UNSUPPORTED, "windowed path: no row kernel for this width");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)pl->win_lds);
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
   }
-  // bf16 volume in the order-free form: the window's map images are kept in bf16 (what the kernel's BF16 && OF instantiations read)
-  pl->maps16 = !pl->brick_form && pl->of && kv.bf16 != 0 && SAF_WIN_MAPS16_BUILD;
+  // bf16 / fp16 volume in the order-free form: the window's map images are kept in the volume's type (what the kernel's BF16 && OF
+  // instantiations read)
+  pl->maps16 = !pl->brick_form && pl->of && kv.e16 != 0 && SAF_WIN_MAPS16_BUILD;
   pl->img_bytes16 = ((size_t)kv.D * (P + 1) * 2 + 255) & ~(size_t)255;
   if (pl->maps16) pl->img_vecs = (int)(pl->img_bytes16 / sizeof(float4));
   // the depth tiles of the classification's occlusion cull: 16 x 16 pixels, doubled until a frame has at most kMaxDepthTiles
@@ -1798,7 +1830,7 @@ struct WinView {
   unsigned long long* cls_acc;
   WinTable* tab;
   uint32_t* masks;
-  float* maps;          // the window's map images (fp32, or bf16: WinPlan::maps16)
+  float* maps;          // the window's map images (fp32, or the volume's 16-bit type: WinPlan::maps16)
   const float4* rgbl;   // the window's packed {r, g, b, label} images, or nullptr (WinPlan::rgbl_on)
   unsigned char* aux;   // the brick form's channel maxima, camera table and segment pools
 };
@@ -1931,7 +1963,7 @@ int launch_rows(const WinPlan& pl, const WinView& v, const KVol& kv, int F, bool
   if (prep) {
     ScopedPair t(prof, 0, f0, s);
     hipLaunchKernelGGL(prep_rows_kernel, dim3(pl.prep_blocks, F), dim3(256), 0, s, v.tab, static_cast<void*>(v.maps),
-                       pl.maps16 ? (int)(pl.img_bytes16 / 2) : (int)(pl.wl.img_bytes / sizeof(float)), kv.D, pl.P, pl.maps16 ? 1 : 0);
+                       pl.maps16 ? (int)(pl.img_bytes16 / 2) : (int)(pl.wl.img_bytes / sizeof(float)), kv.D, pl.P, pl.maps16 ? kv.e16 : (int)kE16None);
     if ((rc = check_launch("prep_rows_kernel"))) return rc;
     if (wa.rgbl) {
       hipLaunchKernelGGL(prep_rgbl_kernel, dim3((pl.H * pl.W + 255) / 256, F), dim3(256), 0, s, v.tab, const_cast<float4*>(wa.rgbl), pl.H,
@@ -1965,7 +1997,7 @@ KVol slab_kvol(const KVol& kv, int x0, int nx) {
   o.tsdf_w = kv.tsdf_w + rows;
   o.weight = kv.weight + rows;
   o.rgb = kv.rgb + 3 * rows;
-  o.feat = kv.feat + rows * (kv.bf16 ? kv.D / 2 : kv.D);
+  o.feat = kv.feat + rows * (kv.e16 ? kv.D / 2 : kv.D);
   if (kv.labels) o.labels = kv.labels + rows * kv.n_classes;
   return o;
 }

@@ -500,7 +500,7 @@ def slab_descriptor(fusion, x0: int, count: int):
     if not (0 <= x0 and count > 0 and x0 + count <= nx):
         raise ValueError("slab outside the volume")
     rows = x0 * ny * nz
-    esz = 2 if fusion._buffers["clip_feat"].dtype == torch.bfloat16 else 4
+    esz = fusion._buffers["clip_feat"].element_size()  # 4 (f32) or 2 (bf16, fp16)
     out = _abi.SafVolume.from_buffer_copy(vol)
     out.nx = count
     out.axis_x = vol.axis_x + 4 * x0
@@ -553,7 +553,7 @@ def _require_f32_sums(fusion, what):
     if fusion._buffers["clip_feat"].dtype != torch.float32:
         raise SafError(
             f"{what} needs an f32 feature volume (got {fusion._buffers['clip_feat'].dtype}): per-rank SUMS kept in bf16 would "
-            "round every addition to 8 bits; fuse the per-rank shards in f32 and convert after the merge"
+            "round every addition to 8 bits and leave fp16's range; fuse the per-rank shards in f32 and convert after the merge"
         )
 
 
@@ -771,7 +771,8 @@ def gather_shards(fusion, group=None):
 def shard_features_16(fusion, first, count, dtype=torch.float16):
     """The 16-bit copy of a volume's voxel shard that the wide scan reads (cached on the module until the volume
     is fused into, merged or reset again: a merge changes every row but neither the shard range of a one-piece plan, nor the
-    address, nor the frame count -- ``_merge_epoch`` counts the merges).  One pass over count * D * 4 bytes."""
+    address, nor the frame count -- ``_merge_epoch`` counts the merges).  One pass over count * D * 4 bytes -- none at all for a
+    volume that was fused in ``dtype`` (``feat_dtype=torch.float16``): the rows themselves are returned, a view, no copy."""
     key = (first, count, dtype, fusion.clip_feat.data_ptr(), int(fusion.fuse_stats[2]), fusion.__dict__.get("_merge_epoch", 0))
     cached = fusion.__dict__.get("_shard16")
     if cached is not None and cached[0] == key:
