@@ -669,6 +669,83 @@ int saf_color_to_depth(const float* depth, const saf_camera* cam_depth, const sa
                        uint8_t* out_valid, void* stream);
 
 /*
+ * Frame-to-model pose refinement (added under ABI 7: additive, the version number stays; nothing to mirror in the reference, which
+ * fuses with the poses the capture app wrote).  A depth frame and a slightly wrong camera->world pose go in; the pose that puts the
+ * frame's points on the zero set of the fused TSDF comes out, by a fixed Gauss-Newton on the device.  tests/pose_reference.py
+ * restates everything below in NumPy.
+ *
+ * saf_pose_linearize -- residuals, Jacobian rows and the normal equations at one pose, over the pixel lattice
+ * (u, v) = (stride i, stride j), i < ceil(width / stride), j < ceil(height / stride).  Per pixel, fp32, one IEEE operation at a
+ * time in the order written here (grid, origin and voxel_size as in saf_raycast; pose [4,4], K [3,3] and depth [H,W] are DEVICE
+ * pointers):
+ *   point    z = depth[v][u]; the pixel is INVALID unless z > 0 and finite.  d_cam = ((u - K[0][2]) / K[0][0],
+ *            (v - K[1][2]) / K[1][1], 1); q = (z dcx, z dcy, z); lever l_a = (R[a][0] q0 + R[a][1] q1) + R[a][2] q2;
+ *            p_a = l_a + t_a; g_a = (p_a - origin_a) / voxel_size.  A K with skew or a third row other than (0, 0, 1) makes every
+ *            pixel invalid (the call cannot read device memory).
+ *   in-grid  invalid unless 0 <= g_a <= n_a - 1 on every axis (no extrapolation); cell i = floor(g) clamped to [0, n - 2],
+ *            offset f = g - i, per axis; invalid unless all 8 corners have tsdf_weight > 0.
+ *   residual r = trilinear tsdf at g: a + f (b - a) along z, then y, then x (c00, c01, c10, c11 -> c0, c1 -> r, first index x).
+ *   gradient in voxel units from the same intermediates: d/dx = c1 - c0; d/dy = lerp(c01 - c00, c11 - c10, fx);
+ *            d/dz = lerp(lerp(z00, z01, fy), lerp(z10, z11, fy), fx) with zxy the difference of the corner pair along z;
+ *            n = grad / voxel_size (per metre; the TSDF is in units of trunc).
+ *   band     invalid unless |r| < r_max (free space is saturated at +1 and carries no gradient).
+ *   weight   w = 1 if |r| <= huber, else huber / |r|.
+ *   row      J = (n, l x n), each cross-product component as (a b) - (c d): J3 = l1 n2 - l2 n1, J4 = l2 n0 - l0 n2,
+ *            J5 = l0 n1 - l1 n0.  This is d r / d (v, omega) for the update R <- exp([omega]x) R, t <- t + v: a rotation about the
+ *            camera centre.
+ *   terms    in fp64 from these fp32 values: a_i = (double)w (double)J_i; a_i J_j for the 21 entries of the upper triangle
+ *            (row-major: 00 01 .. 05 11 12 ..), a_i r for the 6 right-hand sides, ((double)w r) r for the cost, 1 for the count.
+ *   out_system [32] f64 (device): slots 0..20 H = sum w J^T J, 21..26 b = sum w J r, 27 the cost, 28 n_valid, 29..31 zero.
+ *   out_residual [H,W] f32 and out_jacobian [H,W,6] f32 (each may be NULL): r and J per pixel, NaN where the pixel is invalid or
+ *            off the lattice.
+ * Reduction: one wave owns an 8 x 8 tile of the lattice and adds its 64 pixels' terms in a butterfly over lane distances
+ * 32, 16, .., 1; it writes one partial of 32 doubles per tile to the workspace.  One workgroup then adds the partials: thread
+ * (g, k), g < 8, adds slot k of tiles g, g + 8, .. in that order, and the 8 group sums are added in the order of g.  No
+ * floating-point atomics: the same inputs give the same bytes whatever the scheduling (the guarantee of saf_object_stats).
+ *
+ * saf_pose_refine -- the whole loop, enqueued back to back with no host synchronisation: for level l = 0 .. n_levels - 1,
+ * iters[l] times: linearise at stride strides[l] at the current pose, then one workgroup
+ *   1. adds the partials; K unsupported: status 4.  n_valid < min_valid: status 2;
+ *   2. solves (H + damping diag(H) + 1e-12 I) xi = -b, xi = (v, omega), by Cholesky in fp64; a pivot that is not positive and
+ *      finite: status 3;
+ *   3. updates the pose, kept in fp64 in the workspace: R <- exp([omega]x) R (Rodrigues), t <- t + v;
+ *   4. status 5 if the pose has left the input pose by more than max_shift_t (metres, |t - t_in|) or max_shift_r (radians, the
+ *      angle of R R_in^T), or is not finite;
+ *   5. writes the pose rounded to fp32 for the next linearisation and to pose_out, and appends the log record
+ *      [stride, n_valid, cost / n_valid, |v|, |omega|, status of this step, 0, 0]  (status 0: |v| < tol_t and |omega| < tol_r;
+ *      else 1; or the refusal 2 .. 5, then with the |v|, |omega| computed so far).
+ * A level whose step converges ends there: its remaining iterations are skipped (their log rows stay zero) and the next level
+ * begins; the last level's convergence ends the call with out_status 0.  All iterations used up: out_status 1, pose_out is the
+ * last iterate.  On status 2, 3, 4 or 5 the call ends, a device flag makes the remaining launches return at once, and pose_out
+ * is pose_in byte for byte.  out_log [sum(iters), 8] f64; rows never reached are zero.  pose_out [4,4] f32 (last row 0 0 0 1 on
+ * status 0 / 1), out_status i32: all device memory, as is the workspace of saf_pose_workspace_bytes(height, width, smallest
+ * stride) bytes, 256-byte aligned (0 for a non-positive size or stride).
+ *
+ * SAF_E_INVALID (on the host, nothing is launched) for NULL pointers (the two debug outputs excepted), non-positive sizes,
+ * stride < 1, n_levels < 1, a level with fewer than 1 or more than 1000 iterations, huber or r_max not positive, another
+ * parameter negative, a grid under 2 voxels per axis or of 2^31 voxels or more, a workspace that is small or misaligned.
+ */
+typedef struct saf_pose_params {
+  float huber;       /* |r| up to which a residual has full weight (units of trunc) */
+  float r_max;       /* residuals of this size or more are dropped (units of trunc; below 1: free space is +1) */
+  float damping;     /* Levenberg factor on diag(H) */
+  float tol_t;       /* metres */
+  float tol_r;       /* radians */
+  int32_t min_valid; /* fewer valid pixels than this: status 2 */
+  float max_shift_t; /* metres */
+  float max_shift_r; /* radians */
+} saf_pose_params;
+
+size_t saf_pose_workspace_bytes(int32_t height, int32_t width, int32_t min_stride);
+int saf_pose_linearize(const saf_volume* vol, const float* depth, int32_t height, int32_t width, const float* pose, const float* K,
+                       int32_t stride, float huber, float r_max, double* out_system /*[32]*/, float* out_residual /*[H,W]*/,
+                       float* out_jacobian /*[H,W,6]*/, void* workspace, size_t workspace_bytes, void* stream);
+int saf_pose_refine(const saf_volume* vol, const float* depth, int32_t height, int32_t width, const float* pose_in, const float* K,
+                    const int32_t* strides, const int32_t* iters, int32_t n_levels, const saf_pose_params* params,
+                    float* pose_out /*[4,4]*/, double* out_log /*[sum(iters),8]*/, int32_t* out_status, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
+/*
  * Marching cubes on the TSDF, on the device: the mesh half of extract_mesh (clipfusion.py:723-739,
  * clip_seem_fusion.py:824-842) -- un-fused voxels (weight == 0) act as the reference's NaN mask, faces with a vertex on
  * an edge to an un-fused voxel are dropped, unused vertices never exist.  Two calls, because the sizes are results:

@@ -75,6 +75,19 @@ class SafCamera(C.Structure):
     ]
 
 
+class SafPoseParams(C.Structure):
+    _fields_ = [
+        ("huber", C.c_float),
+        ("r_max", C.c_float),
+        ("damping", C.c_float),
+        ("tol_t", C.c_float),
+        ("tol_r", C.c_float),
+        ("min_valid", C.c_int32),
+        ("max_shift_t", C.c_float),
+        ("max_shift_r", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes); the exported symbols of libsaf_hip.so (include/saf.h)
 PROTOTYPES = {
     "saf_last_error": (C.c_char_p, []),
@@ -199,6 +212,17 @@ PROTOTYPES = {
     "saf_object_stats": (
         C.c_int,
         [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp],
+    ),
+    "saf_pose_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "saf_pose_linearize": (
+        C.c_int,
+        [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp, _fp, C.c_size_t,
+         _fp],
+    ),
+    "saf_pose_refine": (
+        C.c_int,
+        [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+         C.POINTER(SafPoseParams), _fp, _fp, _fp, _fp, C.c_size_t, _fp],
     ),
     "saf_undistort_images": (C.c_int, [_fp, C.c_int32, C.c_int32, C.POINTER(SafCamera), C.POINTER(SafCamera), C.c_int32, _fp, _fp]),
     "saf_depth_to_color_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(SafCamera)]),

@@ -866,6 +866,80 @@ class _FusionVolumeMixin:
         out.relevance = rel.view(out.voxel.shape[0], out.voxel.shape[1], -1)
         return out
 
+    # -- refining a camera pose against the volume (not in the reference: it fuses with the capture app's poses) ------------
+    def refine_pose(self, depth, pose, K, levels=((4, 6), (2, 4), (1, 4)), huber=0.3, r_max=0.9, damping=1e-2, tol_t=None,
+                    tol_r=None, min_valid=100, max_shift_t=None, max_shift_r=0.05):
+        """The pose that puts a depth frame's points on the zero set of the fused TSDF (saf_pose_refine, include/saf.h): a fixed
+        Gauss-Newton on the device, coarse to fine over ``levels`` = ((pixel stride, iterations), ...), started at ``pose``
+        (cam->world [4,4]).  Returns a ``PoseRefinement`` of device tensors; nothing is read back until one of its properties is.
+        ``depth`` [H,W] with ``pose`` [4,4], or [B,H,W] with [B,4,4] (``K`` [3,3] or [B,3,3]): the frames are refined one after the
+        other against the same volume.  Frames still queued behind ``integrate()`` are fused first.
+
+        ``huber`` and ``r_max`` are in units of the truncation distance, ``tol_t`` / ``max_shift_t`` in metres (defaults: 0.05
+        voxel and the truncation distance), ``tol_r`` / ``max_shift_r`` in radians (default ``tol_r``: ``tol_t`` seen over a
+        2.5 m lever).  A frame that cannot be refined -- fewer than ``min_valid`` pixels on observed voxels inside the band
+        (status 2: an empty volume, a pose far off), a singular system (3), an unsupported ``K`` (4), a result farther from
+        ``pose`` than the shift caps (5) -- comes back with its input pose, byte for byte; status 1 (iterations used up) returns
+        the last iterate.  DESIGN 4.16 has the reasons for the defaults and what bounds the basin: the truncation band."""
+        depth = self._f32c(torch.as_tensor(depth), "depth")
+        pose = self._f32c(torch.as_tensor(pose), "pose")
+        K = self._f32c(torch.as_tensor(K), "K")
+        batched = depth.dim() == 3
+        if not batched:
+            depth, pose = depth[None], pose[None]
+        if depth.dim() != 3 or tuple(pose.shape) != (depth.shape[0], 4, 4):
+            raise ValueError("depth must be [H,W] with pose [4,4], or [B,H,W] with pose [B,4,4]")
+        if K.dim() == 2:
+            K = K[None].expand(depth.shape[0], 3, 3)
+        if tuple(K.shape) != (depth.shape[0], 3, 3):
+            raise ValueError("K must be [3,3] or [B,3,3]")
+        if getattr(self, "_shard_stripes", None) is not None or self.x_planes is not None:
+            raise SafError("refine_pose() needs the whole grid: this module holds a slab / the stripes of a voxel-sharded volume")
+        levels = [(int(s), int(n)) for s, n in levels]
+        vol = self._c_volume()  # (joins the queue: the volume holds every frame handed to integrate())
+        dev = self._buffers["tsdf"].device
+        depth, pose, K = depth.to(dev), pose.to(dev), K.contiguous().to(dev)
+        b, height, width = (int(v) for v in depth.shape)
+        vs = float(self.voxel_size)
+        tol_t = 0.05 * vs if tol_t is None else float(tol_t)
+        prm = _abi.SafPoseParams(float(huber), float(r_max), float(damping), tol_t, tol_t / 2.5 if tol_r is None else float(tol_r),
+                                 int(min_valid), float(self.trunc) if max_shift_t is None else float(max_shift_t), float(max_shift_r))
+        n_rows = sum(n for _, n in levels)
+        strides = (C.c_int32 * len(levels))(*[s for s, _ in levels])
+        iters = (C.c_int32 * len(levels))(*[n for _, n in levels])
+        need = lib().saf_pose_workspace_bytes(height, width, min([s for s, _ in levels], default=0))
+        ws = torch.empty(max(int(need), 1), dtype=torch.uint8, device=dev)
+        out_pose = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+        out_log = torch.empty((b, max(n_rows, 0), 8), dtype=torch.float64, device=dev)
+        out_status = torch.empty(b, dtype=torch.int32, device=dev)
+        p = _abi.ptr
+        with torch.cuda.device(dev):
+            for i in range(b):
+                rc = lib().saf_pose_refine(C.byref(vol), p(depth[i]), height, width, p(pose[i]), p(K[i]), strides, iters, len(levels),
+                                           C.byref(prm), p(out_pose[i]), p(out_log[i]), p(out_status[i:i + 1]), p(ws), ws.numel(),
+                                           current_stream_ptr())
+                check(rc, "saf_pose_refine")
+        if not batched:
+            out_pose, out_log, out_status = out_pose[0], out_log[0], out_status[0]
+        return PoseRefinement(pose=out_pose, log=out_log, status=out_status)
+
+    def integrate_refined(self, depth_imgs, rgb_imgs, poses, K, **refine_kw):
+        """``integrate`` with poses that drift: per frame, ``refine_pose`` against the volume as fused so far, then ``integrate``
+        with the refined pose.  Returns the poses used, [B,4,4] on the device.  No host decision is taken: a frame that cannot be
+        refined (an empty volume at the start of a scan, too few valid pixels, ...) is fused with its own pose by the kernel's
+        rule.  Each frame's refinement reads the volume with every earlier frame in it, so this path gives up the deferred
+        queue's overlap by construction: every frame is a flush."""
+        poses = self._f32c(torch.as_tensor(poses), "poses")
+        K = self._f32c(torch.as_tensor(K), "K")
+        if K.dim() == 2:
+            K = K[None].expand(poses.shape[0], 3, 3)
+        used = []
+        for i in range(int(poses.shape[0])):
+            ref = self.refine_pose(depth_imgs[i], poses[i], K[i], **refine_kw)
+            used.append(ref.pose)
+            self.integrate(depth_imgs[i:i + 1], rgb_imgs[i:i + 1], ref.pose[None], K[i:i + 1])
+        return torch.stack(used) if used else poses.new_zeros((0, 4, 4))
+
 
 def _grid_diagonal(voxel_size, nvox):
     return float(voxel_size) * math.sqrt(sum(float(n) ** 2 for n in nvox))
@@ -881,6 +955,39 @@ class RenderResult:
     hit: torch.Tensor
     label: torch.Tensor | None = None      # ClipSeemFusion.render: panoptic class of the voxel, -1 = miss
     relevance: torch.Tensor | None = None  # render_query: [H,W,L]
+
+
+@dataclass
+class PoseRefinement:
+    """What ``refine_pose`` returns: device tensors (a leading batch dimension for a batched call).  ``log`` rows are
+    [stride, n_valid, cost / n_valid, |v|, |omega|, status of the step, 0, 0]; rows never reached are zero.  The properties read
+    the device (a synchronisation) only when they are asked."""
+
+    pose: torch.Tensor    # [4,4] f32: the refined pose, or the input pose where status is 2 .. 5
+    log: torch.Tensor     # [sum(iters), 8] f64
+    status: torch.Tensor  # i32: 0 converged, 1 iterations used up, 2 too few valid pixels, 3 singular, 4 bad K, 5 shift cap
+
+    def _last_row(self):
+        log = self.log.cpu()
+        reached = log[..., 0] > 0
+        last = (reached.long().cumsum(-1) * reached).argmax(-1)
+        row = torch.gather(log, -2, last[..., None, None].expand(*last.shape, 1, 8)).squeeze(-2)
+        return row * reached.any(-1, keepdim=True)
+
+    @property
+    def converged(self):
+        s = self.status.cpu() == 0
+        return bool(s) if s.dim() == 0 else s
+
+    @property
+    def n_valid(self):
+        r = self._last_row()[..., 1].long()
+        return int(r) if r.dim() == 0 else r
+
+    @property
+    def cost(self):
+        r = self._last_row()[..., 2]
+        return float(r) if r.dim() == 0 else r
 
 
 def gather_rows(src, index):

@@ -179,13 +179,17 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
                             config["clip_patch_stride"], clip_model, seg_model, feat_dtype=feat_dtype, device=device).to(device)
     loader = torch.utils.data.DataLoader(dataset, batch_size=1, num_workers=num_workers)
     stage = FrameStager(device)
+    refine_poses = bool(config.get("refine_poses", False))  # not in the reference's config: poses that drift (headsets)
     host = {"loader": 0.0, "stage": 0.0, "integrate": 0.0}  # where the host's time in the loop goes (no device sync inside)
     t_prev = time.perf_counter()
     for rgb_imgs, depth_imgs, poses, K, _ in loader:
         t0 = time.perf_counter()
         depth_d, rgb_d, poses_d, k_d = stage(depth_imgs.float(), rgb_imgs.float(), poses.float(), K.float())
         t1 = time.perf_counter()
-        fusion.integrate(depth_d, rgb_d, poses_d, k_d)
+        if refine_poses:  # (each frame is refined against the volume so far: no deferred queue)
+            fusion.integrate_refined(depth_d, rgb_d, poses_d, k_d)
+        else:
+            fusion.integrate(depth_d, rgb_d, poses_d, k_d)
         t2 = time.perf_counter()
         host["loader"] += t0 - t_prev
         host["stage"] += t1 - t0

@@ -1,0 +1,175 @@
+"""CPU: the pose-refinement contract on its NumPy restatement (tests/pose_reference.py) and the host side of the entry points.
+
+  * saf_pose_linearize / saf_pose_refine refuse bad arguments on the host (no GPU needed: nothing is launched), and
+    saf_pose_workspace_bytes of a bad size is 0;
+  * the conditions the GPU test's inputs were chosen under, re-checked on the restatement over the oracle-fused scene of
+    raycast_reference (never on device output): (a) from every listed perturbation the float64 loop reaches status 0 and ends
+    nearer the true pose than it began, in translation and in rotation; (b) fragile pixels -- validity differs between the
+    float32 and the float64 chain -- are at most 1 % of the lattice per view, pose and stride; (c) at least 30 % of the lattice
+    is valid at the true pose.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import pose_reference as pr
+import raycast_reference as rr
+from spatially_aware_ai_amd import _abi, _lib
+from spatially_aware_ai_amd import synthetic as syn
+
+FRAGILE_CAP = 0.01
+VALID_MIN = 0.30
+
+
+def _fake_volume(n=8):
+    v = _abi.SafVolume()
+    v.nx = v.ny = v.nz = n
+    for f in ("axis_x", "axis_y", "axis_z", "tsdf", "tsdf_weight", "weight", "rgb", "clip_feat"):
+        setattr(v, f, 4096)  # non-NULL, aligned: the descriptor is only inspected
+    return v
+
+
+def _big_volume():
+    v = _fake_volume()
+    v.nx, v.ny, v.nz = 2048, 1024, 1024  # 2^31 voxels
+    return v
+
+
+def test_workspace_bytes():
+    l = _lib.lib()
+    assert l.saf_pose_workspace_bytes(480, 640, 1) >= 80 * 60 * 32 * 8
+    assert l.saf_pose_workspace_bytes(480, 640, 4) < l.saf_pose_workspace_bytes(480, 640, 1)
+    assert l.saf_pose_workspace_bytes(1, 1, 7) > 0
+    for h, w, s in ((0, 640, 1), (480, 0, 1), (-1, 640, 1), (480, 640, 0), (480, 640, -2)):
+        assert l.saf_pose_workspace_bytes(h, w, s) == 0, (h, w, s)
+
+
+def test_linearize_rejects_bad_arguments_on_the_host():
+    l = _lib.lib()
+    vol = _fake_volume()
+    p = 4096  # a non-NULL, 256-byte aligned stand-in for a device pointer; every call below must fail before it would be used
+    need = l.saf_pose_workspace_bytes(4, 4, 1)
+    good = dict(vol=ctypes.byref(vol), depth=p, h=4, w=4, pose=p, K=p, stride=1, huber=0.3, r_max=0.9, system=p, ws=p, bytes=need)
+    bad = [dict(vol=None), dict(depth=None), dict(pose=None), dict(K=None), dict(system=None), dict(ws=None), dict(h=0), dict(w=-3),
+           dict(stride=0), dict(stride=-1), dict(vol=ctypes.byref(_abi.SafVolume())), dict(vol=ctypes.byref(_fake_volume(1))),
+           dict(vol=ctypes.byref(_big_volume())), dict(bytes=need - 1), dict(bytes=0), dict(ws=4096 + 8), dict(ws=4096 + 128)]
+    for change in bad:
+        a = dict(good, **change)
+        rc = l.saf_pose_linearize(a["vol"], a["depth"], a["h"], a["w"], a["pose"], a["K"], a["stride"], a["huber"], a["r_max"],
+                                  a["system"], None, None, a["ws"], a["bytes"], None)
+        assert rc == _abi.SAF_E_INVALID, change
+        assert b"pose linearize" in l.saf_last_error()
+
+
+def test_refine_rejects_bad_arguments_on_the_host():
+    l = _lib.lib()
+    vol = _fake_volume()
+    p = 4096
+    arr = lambda *v: (ctypes.c_int32 * len(v))(*v)
+    prm = _abi.SafPoseParams(0.3, 0.9, 1e-2, 1e-3, 1e-3, 100, 0.1, 0.05)
+    need = l.saf_pose_workspace_bytes(4, 4, 1)
+    good = dict(vol=ctypes.byref(vol), depth=p, h=4, w=4, pose=p, K=p, strides=arr(2, 1), iters=arr(3, 2), n=2, prm=ctypes.byref(prm),
+                out=p, log=p, status=p, ws=p, bytes=need)
+    bad = [dict(vol=None), dict(depth=None), dict(pose=None), dict(K=None), dict(strides=None), dict(iters=None), dict(prm=None),
+           dict(out=None), dict(log=None), dict(status=None), dict(ws=None), dict(h=0), dict(w=-3), dict(n=0), dict(n=-1),
+           dict(strides=arr(2, 0)), dict(strides=arr(-1, 1)), dict(iters=arr(3, 0)), dict(vol=ctypes.byref(_abi.SafVolume())),
+           dict(vol=ctypes.byref(_fake_volume(1))), dict(vol=ctypes.byref(_big_volume())), dict(bytes=need - 1), dict(ws=4096 + 64),
+           # the workspace is sized by the SMALLEST stride of the levels
+           dict(strides=arr(4, 2), bytes=l.saf_pose_workspace_bytes(40, 40, 4), h=40, w=40)]
+    for change in bad:
+        a = dict(good, **change)
+        rc = l.saf_pose_refine(a["vol"], a["depth"], a["h"], a["w"], a["pose"], a["K"], a["strides"], a["iters"], a["n"], a["prm"],
+                               a["out"], a["log"], a["status"], a["ws"], a["bytes"], None)
+        assert rc == _abi.SAF_E_INVALID, {k: v for k, v in change.items()}
+        assert b"pose refine" in l.saf_last_error()
+
+
+def test_refine_pose_has_no_cpu_fallback():
+    import torch
+
+    from spatially_aware_ai_amd import clipfusion
+
+    class FakeClip:
+        feature_dim = 8
+
+    f = clipfusion.ClipFusion(torch.zeros(3), 0.1, torch.tensor([4, 4, 4]), 0.3, False, FakeClip(), None, 10, 10)
+    with pytest.raises(_lib.SafError, match="no CPU fallback"):
+        f.refine_pose(torch.ones(30, 40), torch.eye(4), torch.eye(3))
+    with pytest.raises(_lib.SafError, match="no CPU fallback"):
+        f.integrate_refined(torch.ones(1, 30, 40), torch.zeros(1, 30, 40, 3), torch.eye(4)[None], torch.eye(3)[None])
+
+
+def test_params_struct_matches_the_header():
+    assert ctypes.sizeof(_abi.SafPoseParams) == 32 and _abi.SafPoseParams.min_valid.offset == 20
+
+
+@pytest.fixture(scope="module")
+def fused(oracle):
+    """The scene fused by the CPU oracle, and per view its analytic depth."""
+    sc = rr.scan()
+    grid = syn.make_grid(rr.NVOX, trunc_vox=rr.TRUNC_VOX)
+    assert abs(grid.voxel_size - pr.VOXEL) < 1e-12
+    vol = oracle.OracleVolume(grid.origin, grid.voxel_size, grid.nvox, grid.trunc, rr.DIM, 143)
+    oracle.set_threads(8)
+    try:
+        for f in sc.frames:
+            vol.integrate(f["depth"], f["rgb"], f["pose"], f["K"], f["feat"], [f["labels"].float()], rgb_bilinear=True)
+    finally:
+        oracle.set_threads(1)
+    field = (vol.tsdf.numpy(), vol.tsdf_weight.numpy(), [a.numpy() for a in vol.axes])
+    views = {name: (pose.numpy(), k.numpy(), rr.analytic(pose, k)[0]) for name, pose, k in pr.views()}
+    return field, views
+
+
+def test_perturbations_are_inside_the_band(fused):
+    _, views = fused
+    for name, (pose, k, depth) in views.items():
+        for label, pp, (v, w) in pr.perturbations(name, pose, depth):
+            assert np.linalg.norm(v) <= pr.VOXEL and np.linalg.norm(w) * depth.max() <= pr.VOXEL, label
+            assert pp.dtype == np.float32 and not np.array_equal(pp, pose)
+
+
+def test_the_float64_loop_converges_from_every_perturbation(fused):
+    (tsdf, tw, axes), views = fused
+    for name, (pose, k, depth) in views.items():
+        for label, pp, _ in pr.perturbations(name, pose, depth):
+            out = pr.refine(tsdf, tw, axes, depth, pp, k)
+            d0, d1 = pr.pose_distance(pp, pose), pr.pose_distance(out["pose"], pose)
+            used = int((out["log"][:, 0] > 0).sum())
+            print(f"{label}: status {out['status']} after {used} steps; {d0[0] / pr.VOXEL:.3f} -> {d1[0] / pr.VOXEL:.4f} voxels, "
+                  f"{d0[1] * 1e3:.2f} -> {d1[1] * 1e3:.3f} mrad")
+            assert out["status"] == 0, f"{label}: choose another seed or view"
+            assert d1[0] < d0[0] and d1[1] < d0[1], f"{label}: the restatement does not end nearer the truth"
+
+
+def test_fragile_pixels_are_rare_and_the_views_see_the_volume(fused):
+    (tsdf, tw, axes), views = fused
+    P = pr.PARAMS
+    for name, (pose, k, depth) in views.items():
+        poses = [("true", pose)] + [(label, pp) for label, pp, _ in pr.perturbations(name, pose, depth)]
+        for label, pp in poses:
+            for stride in (1, 2, 4):
+                l64, l32 = (pr.linearize(tsdf, tw, axes, depth, pp, k, stride, P["huber"], P["r_max"], dtype=dt) for dt in (np.float64, np.float32))
+                lattice = pr.lattice_mask(*depth.shape, stride).sum()
+                fr = (l64["valid"] != l32["valid"]).sum() / lattice
+                share = l64["valid"].sum() / lattice
+                print(f"{name} at {label}, stride {stride}: {share:.3f} of the lattice valid, {fr:.4%} fragile")
+                assert fr <= FRAGILE_CAP, f"{name} at {label}: {fr:.3%} fragile pixels; choose another view"
+                if label == "true":
+                    assert share >= VALID_MIN, f"view {name} hardly sees the volume"
+                    assert l64["system"][28] == l64["valid"].sum() and (l64["system"][29:] == 0).all()
+
+
+def test_refusals_of_the_restatement(fused):
+    """The loop's refusals return the input pose: a skewed K (4), nothing valid (2: depth 0 everywhere), a shift cap (5)."""
+    (tsdf, tw, axes), views = fused
+    pose, k, depth = views["look_at"]
+    bad = k.copy()
+    bad[0, 1] = 0.5
+    for kk, dd, prm, want in ((bad, depth, pr.PARAMS, 4), (k, np.zeros_like(depth), pr.PARAMS, 2),
+                              (k, depth, dict(pr.PARAMS, max_shift_t=1e-6), 5)):
+        _, pp, _ = pr.perturbations("look_at", pose, depth)[0]
+        out = pr.refine(tsdf, tw, axes, dd, pp, kk, params=prm)
+        assert out["status"] == want and out["pose"].tobytes() == pp.tobytes()
+        assert out["log"][0, 5] == want and (out["log"][1:] == 0).all()
