@@ -414,6 +414,7 @@ int saf_segmentation_counts(const int32_t* gt, const int32_t* pred, int64_t n, i
  *   feats      [n_rows, feat_stride] SAF_F16 or SAF_BF16, feat_dim in {128, 256, 512}
  *   out        [n_rows, out_stride] of out_dtype (SAF_F32, SAF_F16 or SAF_BF16), out_stride >= n_text
  *   workspace  saf_query_wide_workspace_bytes(n_text, feat_dim) bytes of device scratch
+ * Strides, the columns of `out` that are written and rows with inf / NaN in them: see saf_query_scan_wide_ex below.
  */
 size_t saf_query_wide_workspace_bytes(int32_t n_text, int32_t feat_dim);
 int saf_query_scan_wide(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride,
@@ -438,6 +439,24 @@ int saf_query_scan_wide(const void* feats, int32_t feat_dtype, int64_t n_rows, i
  *                         row (equal scores: the smaller row), -1 / -inf when n_rows = 0; row_offset lets ranks that
  *                         scan voxel shards report global voxel indices.
  * Unused outputs may be NULL.  workspace: saf_query_wide_ex_workspace_bytes(...) bytes, 256-byte aligned.
+ *
+ * Layout (both entry points): feats on 16 bytes and feat_stride a multiple of 8 elements, >= feat_dim; text_stride >= feat_dim;
+ * `out` at any element-aligned base and any out_stride >= its columns (n_text; VS_BACKGROUND: n_text - n_background).  On a
+ * 16-byte base saf_query_scan_wide_ex stores 16 bytes at a time when out_stride is a multiple of 8 elements, and
+ * saf_query_scan_wide four scores at a time (16 bytes of fp32, 8 bytes of 16-bit output) when it is a multiple of 4; anything else
+ * is stored element by element: the values are the same.  Only columns [0, columns) of each of the n_rows rows are written;
+ * whatever lies between the rows stays as it was.
+ *
+ * Rows with an inf or a NaN in them (fp16 fusion can leave them: SAF_F16 above) -- a row is "bad" when its fp32 sum of squares is
+ * not finite:
+ *   SAF_NORM_L2        a bad row is the all-zero row (clip_seem_fusion.py:507-511, nan_to_num of f / |f|): score 0 in every
+ *                      column, ROW_ARGMAX gives (0, 0.0), and it takes part in QUERY_MAX with score 0;
+ *   SAF_NORM_NONE, SAF_NORM_L2_CLAMP   no nan_to_num in the reference: a bad row's scores are the IEEE result, NaN or +-inf;
+ *   in every mode all other rows' outputs are bit for bit what they are without the bad rows.
+ * A NaN score never wins a reduction, wherever its row lies: QUERY_MAX is the maximum over the scores that are not NaN (an infinite
+ * score is a score and wins; equal scores: the smaller row); ROW_ARGMAX of a row is its first maximum over the scores that are not
+ * NaN (a row of NaN scores only: an index in [0, n_text), the value not finite).  A query all of whose scores are NaN or -inf
+ * reports -inf and no particular row.
  */
 enum saf_wide_epilogue { SAF_QW_SCORES = 0, SAF_QW_VS_BACKGROUND = 1, SAF_QW_ROW_ARGMAX = 2, SAF_QW_QUERY_MAX = 3 };
 size_t saf_query_wide_ex_workspace_bytes(int32_t n_text, int32_t feat_dim, int32_t epilogue, int32_t n_background);

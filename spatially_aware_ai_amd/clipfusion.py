@@ -1120,8 +1120,10 @@ def query_scan_wide(feats, text, epilogue="scores", scale=1.0, normalize=True, n
       (eval_scannet_segmentation.py:553-560, the first label of the argsort)
     * ``"query_max"``      -> (value f32 [Q], row int64 [Q]): best row per query, rows numbered from ``row_offset``
 
-    ``out``: an optional preallocated [N, columns] tensor for the two matrix-valued epilogues (row stride a multiple
-    of 8 elements keeps the 16-byte stores of the epilogue aligned; a multiple of 128 bytes is 3-4 % faster at many columns).
+    ``out``: an optional preallocated [N, columns] tensor for the two matrix-valued epilogues, a view at any row stride and
+    base (row stride a multiple of 8 elements on a 16-byte base keeps the 16-byte stores of the epilogue; a multiple of 128 bytes
+    is 3-4 % faster at many columns); only its own elements are written.  Rows with inf / NaN in them: include/saf.h,
+    saf_query_scan_wide_ex.
     """
     require_cuda(feats, "features")
     if feats.dtype not in (torch.float16, torch.bfloat16) or feats.dim() != 2:
@@ -1141,7 +1143,13 @@ def query_scan_wide(feats, text, epilogue="scores", scale=1.0, normalize=True, n
     L = lib()
     norm = _norm_mode(normalize)
     if d == 128 and epi == _abi.SAF_QW_SCORES:  # the narrow shape keeps the first kernel
-        out = torch.empty((n, q), dtype=out_dtype, device=dev)
+        if out is None:
+            out = torch.empty((n, q), dtype=out_dtype, device=dev)
+        else:
+            require_cuda(out, "out")
+            if tuple(out.shape) != (n, q) or out.stride(1) != 1:
+                raise ValueError(f"out must be [{n}, {q}] with unit column stride")
+            out_dtype = out.dtype
         wsb = L.saf_query_wide_workspace_bytes(q, d)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):

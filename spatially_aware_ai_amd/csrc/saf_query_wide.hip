@@ -148,6 +148,11 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
       ss += __shfl_xor(ss, 32);                              // both halves of row r
       // SAF_NORM_L2: nan_to_num, an all-zero row scores 0; SAF_NORM_L2_CLAMP: norm.clamp_min(0.1)
       inv = normalize == SAF_NORM_L2_CLAMP ? scale / fmaxf(sqrtf(ss), 0.1f) : (ss > 0.0f ? scale / sqrtf(ss) : 0.0f);
+      // SAF_NORM_L2, a row with an inf or a NaN in it (ss is inf or NaN in both of its lanes): nan_to_num gives the all-zero row
+      if (normalize == SAF_NORM_L2 && !(ss < INFINITY)) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) a[s] = make_uint4(0u, 0u, 0u, 0u);
+      }
     }
 
     __syncthreads();  // the previous row block is done with both LDS buffers
@@ -358,6 +363,11 @@ struct W2Tile {
   float inv[NF];     // scale / row norm of the lane's feature rows
   int64_t row[NF];   // their true indices (may be >= n_rows on the last block)
   int qt;            // query tile
+  bool bad;          // ROW_ARGMAX / QUERY_MAX (wave-uniform): one of the wave's rows has an inf or a NaN in it and is not zeroed
+                     // (SAF_NORM_NONE, SAF_NORM_L2_CLAMP), so its scores may be NaN.  The interleaved chains seed with their first
+                     // score unconditionally -- a NaN there would make every later `x > best` false and, per query, its key the
+                     // largest --; such a wave's tiles take w2_epilogue, whose chains start at -inf and skip NaN.  A -inf seed in the
+                     // interleaved chains is one v_max_f32 per chain: measured, 0.9 % of the per-query maximum at config 5
 };
 // per-row-block epilogue state (ROW_ARGMAX: running best; VS_BACKGROUND: log-sum-exp of the backgrounds)
 template <int NF>
@@ -557,33 +567,8 @@ __device__ __forceinline__ void w2_fast_piece(int i, const Wide2Args& wa, const 
         }
       }
     }
-  } else if (EPI == SAF_QW_ROW_ARGMAX) {
-    const int q = qbase + 8 * (i >> 2) + (i & 3);
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const float x = c[f][i];               // raw dot products: see w2_epilogue
-      const bool better = x > st.best_v[f];  // queries ascend: the first maximum stays
-      st.best_v[f] = better ? x : st.best_v[f];
-      st.best_q[f] = better ? q : st.best_q[f];
-    }
-  } else {  // SAF_QW_QUERY_MAX (swapped operands: see w2_epilogue): the lane's chain over its rows
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int m = 32 * f + 8 * (i >> 2) + (i & 3);
-      if ((i & 3) == 0) {
-        const float4 v4 = *reinterpret_cast<const float4*>(st.inv_lds + m + 4 * h);
-        fs.iv[f][0] = v4.x; fs.iv[f][1] = v4.y; fs.iv[f][2] = v4.z; fs.iv[f][3] = v4.w;
-      }
-      const float x = c[f][i] * fs.iv[f][i & 3];
-      if (f == 0 && i == 0) {
-        fs.bv = x; fs.bm = m;
-      } else {
-        const bool better = x > fs.bv;  // rows ascend: the first maximum stays
-        fs.bv = better ? x : fs.bv;
-        fs.bm = better ? m : fs.bm;
-      }
-    }
   }
+  // (ROW_ARGMAX and QUERY_MAX have no pieces here: query_wide2_kernel runs their chains inline between the MFMAs)
 }
 
 // NF = 2: 64 rows per wave, 4 waves per workgroup, one wave per SIMD (the whole 512-register file);
@@ -597,6 +582,7 @@ query_wide2_kernel(Wide2Args wa) {
   constexpr int D = KS * 16;
   constexpr int ROWB = D * 2 + 16;  // padded LDS row in bytes: the 16 lanes of a ds_read_b128 group hit distinct bank quads
   constexpr bool kDma = (D == 512);  // a text row is exactly one 1 KiB LDS-DMA piece
+  constexpr bool kReduce = EPI == SAF_QW_ROW_ARGMAX || EPI == SAF_QW_QUERY_MAX;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_tiles[];  // 2 x [32][ROWB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -626,6 +612,7 @@ query_wide2_kernel(Wide2Args wa) {
   float* s_inv = reinterpret_cast<float*>(s_tiles + 2 * kWTile * ROWB) + wave * kRows;  // QUERY_MAX only (W2State::inv_lds)
   st.inv_lds = s_inv;
   cur.qt = 0;
+  cur.bad = false;
   prev = cur;
   f32x16_t acc[2][NF];  // [step parity][fragment]: the tile being accumulated and the previous one awaiting its epilogue
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)s_tiles;
@@ -662,10 +649,11 @@ query_wide2_kernel(Wide2Args wa) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[f][s] = ld_stream_u4(pa + 16 * s);
       }
+      bool bad = false;
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         cur.inv[f] = wa.scale;
-        if (wa.normalize) {
+        if (wa.normalize || kReduce) {  // (the reductions look at every row's sum of squares: W2Tile::bad)
           // the row's squared norm: one v_dot2_f32_{f16,bf16} per pair of elements (exact products, fp32 sums) -- a quarter of the
           // instructions of widening and two FMAs per pair; two chains, added at the end
           float ss = 0.f, ss2 = 0.f;
@@ -681,10 +669,23 @@ query_wide2_kernel(Wide2Args wa) {
           ss += ss2;
           ss += __shfl_xor(ss, 32);
           // SAF_NORM_L2_CLAMP: norm.clamp_min(0.1); SAF_NORM_L2 with nan_to_num: an all-zero row scores 0
-          cur.inv[f] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
-                                                         : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
+          if (wa.normalize)
+            cur.inv[f] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
+                                                           : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
+          // a row with an inf or a NaN in it (ss is inf or NaN in both of its lanes).  SAF_NORM_L2: nan_to_num gives the all-zero
+          // row -- in every epilogue, and once per row block instead of a select per score; otherwise its scores are what IEEE
+          // gives, and the reductions keep NaN out of their chains (W2Tile::bad)
+          if (!(ss < INFINITY)) {
+            if (wa.normalize == SAF_NORM_L2) {
+#pragma unroll
+              for (int s = 0; s < KS; ++s) a[f][s] = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+              bad = true;
+            }
+          }
         }
       }
+      cur.bad = kReduce && __any(bad);
     }
     cur.qt = qt;
     if (qt == 0) W2_STAMP(1);  // a new block's rows: issue, norms (the waits for the data are in the first tile's MFMAs)
@@ -750,6 +751,7 @@ query_wide2_kernel(Wide2Args wa) {
     if (EPI == SAF_QW_VS_BACKGROUND) fast = fast && vec_ok && prev.qt > 0 && (prev.qt + 1) * kWTile <= wa.Q;
     if (EPI == SAF_QW_ROW_ARGMAX) fast = fast && prev.qt > 0 && prev.qt < n_qt - 1;  // first / last tile: reset / write-out
     if (EPI == SAF_QW_QUERY_MAX) fast = fast && (prev.qt + 1) * kWTile <= wa.Q;
+    if (kReduce) fast = fast && !prev.bad;
 #ifdef SAF_W2_NO_FAST
     fast = false;
 #endif
@@ -804,7 +806,7 @@ query_wide2_kernel(Wide2Args wa) {
                 ra_x[f] = pc[f][i];  // raw dot products: see w2_epilogue
               }
               if (i == 0) {
-                ra_v[f] = ra_x[f];
+                ra_v[f] = ra_x[f];  // (never NaN: a wave with a row that can score NaN takes w2_epilogue, see W2Tile::bad)
                 ra_i[f] = 0;
               } else {
                 ra_b[f] = ra_x[f] > ra_v[f];  // queries ascend: the first maximum stays
@@ -932,6 +934,7 @@ struct W3Tile {
   float inv[2];     // scale / row norm of the lane's row of block rb
   int64_t row[2];   // its true index (may be >= n_rows on the last block)
   int qt;
+  bool bad;         // as W2Tile::bad: the wave's tiles of this row block take w3_epilogue
 };
 struct W3State {
   float best_v[2];
@@ -1168,7 +1171,7 @@ __device__ __forceinline__ void w3_piece(int k, const Wide2Args& wa, const f32x4
     const int rb = k >> 3, j = k & 7;
     const float x = pacc[rb][j >> 2][j & 3];  // raw dot products: see w2_epilogue
     if (j == 0) {
-      fs.cv = x; fs.ci = 0;
+      fs.cv = x; fs.ci = 0;  // (never NaN: see W3Tile::bad)
     } else {
       const bool better = x > fs.cv;  // the lane's queries ascend: the first maximum stays
       fs.cv = better ? x : fs.cv;
@@ -1188,7 +1191,7 @@ __device__ __forceinline__ void w3_piece(int k, const Wide2Args& wa, const f32x4
     const float x = pacc[rb][qb][i] * fs.iv[i];
     const int m = 16 * rb + 4 * g + i;
     if ((k & 7) == 0) {
-      fs.cv = x; fs.ci = m;
+      fs.cv = x; fs.ci = m;  // (never NaN: see W3Tile::bad)
     } else {
       const bool better = x > fs.cv;  // the lane's rows ascend: the first maximum stays
       fs.cv = better ? x : fs.cv;
@@ -1224,6 +1227,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   constexpr int ROWB = D * 2 + 16;        // padded LDS row: the 16 lanes of a fragment's row group hit distinct bank quads
   constexpr bool kDma = (D == 512);
   constexpr bool kSwap = EPI == SAF_QW_QUERY_MAX;
+  constexpr bool kReduce = EPI == SAF_QW_ROW_ARGMAX || EPI == SAF_QW_QUERY_MAX;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_tiles[];  // 2 x [32][ROWB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
@@ -1262,6 +1266,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   st.pair = 0;
   bool pair_staged = false;  // the previous tile's halves wait in the LDS (wave-uniform)
   cur.qt = 0;
+  cur.bad = false;
   prev = cur;
   f32x4_t acc[2][2][2];  // [step parity][row block][query block]
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)s_tiles;
@@ -1328,10 +1333,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         pref_base = wa.feats + (pref_ok ? row0n : 0) * wa.fstride;
         pref_cnt = 0;
       }
+      bool bad = false;
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
         cur.inv[rb] = wa.scale;
-        if (wa.normalize) {
+        if (wa.normalize || kReduce) {  // (the reductions look at every row's sum of squares: W3Tile::bad)
           float ss = 0.f, ss2 = 0.f;
 #pragma unroll
           for (int s = 0; s < S; ++s) {
@@ -1345,10 +1351,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           ss += ss2;
           ss += __shfl_xor(ss, 16);
           ss += __shfl_xor(ss, 32);
-          cur.inv[rb] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
-                                                          : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
+          if (wa.normalize)
+            cur.inv[rb] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
+                                                            : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
+          // a row with an inf or a NaN in it (ss is inf or NaN in all four of its lanes): SAF_NORM_L2: the all-zero row; otherwise
+          // the reductions keep its NaN scores out of their chains (see query_wide2_kernel)
+          if (!(ss < INFINITY)) {
+            if (wa.normalize == SAF_NORM_L2) {
+#pragma unroll
+              for (int s = 0; s < S; ++s) a[rb][s] = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+              bad = true;
+            }
+          }
         }
       }
+      cur.bad = kReduce && __any(bad);
     }
     cur.qt = qt;
     const unsigned char* curb = s_tiles + (size_t)(step & 1) * kWTile * ROWB;
@@ -1395,6 +1413,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (EPI == SAF_QW_VS_BACKGROUND) fast = fast && vec_ok && prev.qt > 0 && (prev.qt + 1) * kWTile <= wa.Q;
     if (EPI == SAF_QW_ROW_ARGMAX) fast = fast && prev.qt > 0 && prev.qt < n_qt - 1;  // first / last tile: reset / write-out
     if (EPI == SAF_QW_QUERY_MAX) fast = fast && (prev.qt + 1) * kWTile <= wa.Q;
+    if (kReduce) fast = fast && !prev.bad;
 #ifdef SAF_W3_NO_FAST
     fast = false;
 #endif
@@ -1667,10 +1686,12 @@ int saf_query_scan_wide(const void* feats, int32_t feat_dtype, int64_t n_rows, i
                         void* stream) {
   if (feat_dtype != SAF_F16 && feat_dtype != SAF_BF16)
     return fail(SAF_E_UNSUPPORTED, "wide scan: features must be SAF_F16 or SAF_BF16");
-  if (!feats || !text || !out || n_rows < 0 || n_text <= 0 || feat_stride < feat_dim || text_stride < feat_dim ||
-      out_stride < n_text)
-    return fail(SAF_E_INVALID, "wide scan: bad arguments");
-  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0) return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned");
+  if (!feats || !text || !out || n_rows < 0 || n_text <= 0) return fail(SAF_E_INVALID, "wide scan: bad arguments");
+  if (feat_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: feat_stride %lld is below feat_dim %d", (long long)feat_stride, feat_dim);
+  if (text_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: text_stride %lld is below feat_dim %d", (long long)text_stride, feat_dim);
+  if (out_stride < n_text) return fail(SAF_E_INVALID, "wide scan: out_stride %lld is below n_text %d", (long long)out_stride, n_text);
+  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0)
+    return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned (feats on 16 bytes, feat_stride a multiple of 8)");
   if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < saf_query_wide_workspace_bytes(n_text, feat_dim))
     return fail(SAF_E_WORKSPACE, "wide scan: workspace needs %zu bytes", saf_query_wide_workspace_bytes(n_text, feat_dim));
   if (n_rows == 0) return SAF_OK;
@@ -1708,20 +1729,22 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
     return fail(SAF_E_UNSUPPORTED, "wide scan: features must be SAF_F16 or SAF_BF16");
   if (feat_dim != 256 && feat_dim != 512)
     return fail(SAF_E_UNSUPPORTED, "wide scan (fused epilogues): feat_dim must be 256 or 512 (got %d)", feat_dim);
-  if ((!feats && n_rows > 0) || !text || n_rows < 0 || n_text <= 0 || feat_stride < feat_dim || text_stride < feat_dim)
-    return fail(SAF_E_INVALID, "wide scan: bad arguments");
-  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0) return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned");
+  if ((!feats && n_rows > 0) || !text || n_rows < 0 || n_text <= 0) return fail(SAF_E_INVALID, "wide scan: bad arguments");
+  if (feat_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: feat_stride %lld is below feat_dim %d", (long long)feat_stride, feat_dim);
+  if (text_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: text_stride %lld is below feat_dim %d", (long long)text_stride, feat_dim);
+  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0)
+    return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned (feats on 16 bytes, feat_stride a multiple of 8)");
   int n_bg = 0, n_out_cols = n_text;
   switch (epilogue) {
     case SAF_QW_SCORES:
-      if ((!out && n_rows > 0) || out_stride < n_text) return fail(SAF_E_INVALID, "wide scan: SCORES needs out [n_rows, >= n_text]");
+      if ((!out && n_rows > 0) || out_stride < n_text) return fail(SAF_E_INVALID, "wide scan: SCORES needs out [n_rows, out_stride >= n_text]");
       break;
     case SAF_QW_VS_BACKGROUND:
       n_bg = n_background;
       n_out_cols = n_text - n_bg;
       if (n_bg < 1 || n_bg > kWTile || n_out_cols < 1)
         return fail(SAF_E_INVALID, "wide scan: VS_BACKGROUND needs 1..32 background rows followed by at least one target");
-      if ((!out && n_rows > 0) || out_stride < n_out_cols) return fail(SAF_E_INVALID, "wide scan: VS_BACKGROUND needs out [n_rows, >= n_text - n_background]");
+      if ((!out && n_rows > 0) || out_stride < n_out_cols) return fail(SAF_E_INVALID, "wide scan: VS_BACKGROUND needs out [n_rows, out_stride >= n_text - n_background]");
       if (!(scale > 0.0f)) return fail(SAF_E_INVALID, "wide scan: VS_BACKGROUND needs a positive scale");
       break;
     case SAF_QW_ROW_ARGMAX:
