@@ -5,8 +5,11 @@ ufunc call below is one IEEE operation of csrc/saf_raycast.hip, in its order); `
 double precision -- the reference the device is held to.  The inputs are the fp32 values the device sees (axis tables,
 pose, K, step_vox, z_near, z_far as C floats) in both cases.
 
-Also here: the scene and the views the ray-cast tests share, and the masks they compare on.
+Also here: the scenes and the views the ray-cast tests share, and the masks they compare on: the fused room of
+tests/test_raycast_gpu.py (scan / views / analytic) and the hand-written non-cubic volume of tests/test_raycast_edges.py
+(edge_scene / edge_views / edge_analytic).
 """
+import functools
 import math
 
 import numpy as np
@@ -224,3 +227,161 @@ def analytic(pose, k):
     depth, surface = syn._analytic_scene(pose, k, w, h)
     depth = torch.where(torch.isfinite(depth) & (depth > 0), depth, torch.zeros_like(depth))
     return depth.numpy(), surface.numpy()
+
+
+# ---- the edge scene of tests/test_raycast_host.py and tests/test_raycast_edges.py: a hand-written 20 x 24 x 28 volume (the field
+# of tests/test_pose_gpu.py::_edge_field, restated: that module uploads on import of its Field).  A non-cubic grid catches index
+# order; the floor lies inside the last cell of z; a hole (tsdf_weight = 0) sits on the floor and a patch of weight = 0 on a wall.
+E_NVOX, E_VS, E_TRUNC_VOX = (20, 24, 28), 0.0625, 3.0  # (voxel size and origin are exact in fp32)
+E_ORG = np.array([0.125, 0.25, 0.375])
+E_WALL_X, E_WALL_Y, E_FLOOR_Z, E_CENTRE, E_RADIUS = 17.5, 21.3, 26.4, np.array([9.0, 11.0, 14.0]), 4.0  # in grid coordinates
+E_OBSERVED = (slice(1, 19), slice(1, 23), slice(2, 28))
+E_HOLE = (slice(8, 11), slice(9, 13), slice(24, 28))       # tsdf_weight = 0: an unobserved patch on the floor
+E_UNCOLOURED = (slice(16, 19), slice(11, 21), slice(6, 16))  # weight = 0, tsdf_weight still 1: 300 voxels around the wall x = 17.5
+E_SEED = 2028
+E_SURFACES = ("wall_x", "wall_y", "floor", "sphere")
+
+
+def edge_scene(hole=True):
+    """dict(tsdf [N] f32, tsdf_weight [N] i32, weight [N] i32, rgb [N,3] f32, axes [3 tables f32], nvox).  tsdf = the signed
+    distance (positive on the camera's side) to the nearest of two walls, a floor and a sphere, in units of 3 voxels, clipped to
+    [-1, 1]; tsdf_weight 1 inside the box [1, 18] x [1, 22] x [2, 27] (it reaches the last voxel plane of z) except the hole."""
+    nx, ny, nz = E_NVOX
+    g = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"), axis=-1).astype(np.float64)
+    sd = np.min(np.stack([E_WALL_X - g[..., 0], E_WALL_Y - g[..., 1], E_FLOOR_Z - g[..., 2],
+                          np.linalg.norm(g - E_CENTRE, axis=-1) - E_RADIUS]), axis=0)
+    tsdf = np.clip(sd / E_TRUNC_VOX, -1.0, 1.0).astype(np.float32)
+    tw = np.zeros(E_NVOX, dtype=np.int32)
+    tw[E_OBSERVED] = 1
+    if hole:
+        tw[E_HOLE] = 0
+    weight = np.ones(E_NVOX, dtype=np.int32)
+    weight[E_UNCOLOURED] = 0
+    rgb = np.random.default_rng(E_SEED).random((nx * ny * nz, 3), dtype=np.float32)
+    axes = [(np.arange(n, dtype=np.float64) * E_VS + E_ORG[a]).astype(np.float32) for a, n in enumerate(E_NVOX)]
+    return dict(tsdf=tsdf.reshape(-1), tsdf_weight=tw.reshape(-1), weight=weight.reshape(-1), rgb=rgb, axes=axes, nvox=E_NVOX)
+
+
+def _look(eye_g, fwd, f_or_k, width, height):
+    """(pose, K) f32 of a camera at grid point eye_g looking along fwd (image x = fwd x world z: un-rolled); f_or_k is a focal
+    length for test_pose_gpu.py::_edge_camera's intrinsics (fy = 1.1 fx, cy off-centre by 0.25) or a whole K."""
+    fwd = np.asarray(fwd, dtype=np.float64)
+    fwd = fwd / np.linalg.norm(fwd)
+    right = np.cross(fwd, [0.0, 0.0, 1.0])
+    right /= np.linalg.norm(right)
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = right, np.cross(fwd, right), fwd, E_ORG + E_VS * np.asarray(eye_g, dtype=np.float64)
+    if np.ndim(f_or_k) == 0:
+        f = float(f_or_k)
+        f_or_k = [[f, 0, (width - 1) / 2], [0, 1.1 * f, (height - 1) / 2 + 0.25], [0, 0, 1]]
+    return pose.astype(np.float32), np.array(f_or_k, dtype=np.float32)
+
+
+def _inside(width, height):
+    """test_pose_gpu.py::_edge_camera: inside the box at grid (3, 4, 5), looking at the far corner."""
+    return _look([3.0, 4.0, 5.0], np.array([14.0, 17.0, 24.0]) - [3.0, 4.0, 5.0], 0.8 * max(width, 2), width, height)
+
+
+E_INSIDE_SIZES = ((61, 45), (200, 24), (37, 19), (17, 33), (16, 16), (8, 8), (5, 3), (1, 1))  # width x height
+
+
+def edge_views():
+    """[(name, pose [4,4] f32, K [3,3] f32, height, width, kwargs of raycast / saf_raycast)].
+
+    inside_WxH      16 x 16-pixel blocks: 12 (8 + a remainder of 4), 26 (remainder 2), 6 and 6 (fewer than the 8 XCDs; 17 wide: one
+                    lane over a block), then single blocks: full, one wave, less than a wave's 8 x 8 tile, one pixel;
+    inside_61x45_*  other steps, a near plane inside the room, a far plane in front of most surfaces;
+    axis_aligned    identity rotation, the eye on a voxel centre in x and y: column u = 10 has gdx == 0, row v = 8 has gdy == 0, the
+                    centre pixel both, and it sees the floor 21.4 voxels away; axis_aligned_off: the same from (5.3, 6.7, 5);
+    outside         from grid (-6, 11.2, 14.3) along +x: every ray enters through the face x = 0 and crosses the unobserved shell;
+    nothing         the inside camera turned 180 degrees about its y axis: it looks at the unobserved corner, every pixel a miss;
+    degenerate_*    fx = 0, a NaN and an inf in the pose's translation: all misses.
+    (No step_vox = 1.0: on this scene the restatement itself is fragile on 6.8 % of the pixels at that step.)"""
+    out = []
+    for w, h in E_INSIDE_SIZES:
+        out.append((f"inside_{w}x{h}", *_inside(w, h), h, w, {}))
+    pose, k = _inside(61, 45)
+    for tag, kw in (("step0.25", dict(step_vox=0.25)), ("step0.37", dict(step_vox=0.37)), ("near0.3", dict(z_near=0.3)),
+                    ("near0.3_far0.9", dict(z_near=0.3, z_far=0.9))):
+        out.append((f"inside_61x45_{tag}", pose, k, 45, 61, kw))
+    flat_k = [[50, 0, 10], [0, 50, 8], [0, 0, 1]]
+    for name, eye in (("axis_aligned", [5.0, 6.0, 5.0]), ("axis_aligned_off", [5.3, 6.7, 5.0])):
+        p = np.eye(4)
+        p[:3, 3] = E_ORG + E_VS * np.array(eye)
+        out.append((name, p.astype(np.float32), np.array(flat_k, dtype=np.float32), 17, 21, {}))
+    out.append(("outside", *_look([-6.0, 11.2, 14.3], [1.0, 0.0, 0.0], [[40, 0, 16], [0, 40, 14], [0, 0, 1]], 33, 29), 29, 33, {}))
+    pose, k = _inside(37, 19)
+    back = pose.copy()
+    back[:3, 0], back[:3, 2] = -pose[:3, 0], -pose[:3, 2]
+    out.append(("nothing", back, k, 19, 37, {}))
+    pose, k = _inside(8, 8)
+    bad_k, nan_pose, inf_pose = k.copy(), pose.copy(), pose.copy()
+    bad_k[0, 0], nan_pose[0, 3], inf_pose[1, 3] = 0.0, np.nan, np.inf
+    out += [("degenerate_fx0", pose, bad_k, 8, 8, {}), ("degenerate_nan", nan_pose, k, 8, 8, {}), ("degenerate_inf", inf_pose, k, 8, 8, {})]
+    return out
+
+
+def edge_analytic(pose, K, height, width):
+    """(depth [H,W] f64: camera z of the nearest of the four surfaces along every pixel's ray, 0 where there is none; surface
+    [H,W] int: its index in E_SURFACES, -1; floor_xy [H,W,2]: where the ray meets the floor's plane, in grid coordinates)."""
+    P, Km = np.asarray(pose, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    v, u = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dc = np.stack(((u - Km[0, 2]) / Km[0, 0], (v - Km[1, 2]) / Km[1, 1], np.ones_like(u)), axis=-1)
+        o = (P[:3, 3] - E_ORG) / E_VS
+        d = (dc @ P[:3, :3].T) / E_VS
+        cands = [(at - o[axis]) / d[..., axis] for axis, at in ((0, E_WALL_X), (1, E_WALL_Y), (2, E_FLOOR_Z))]
+        oc = o - E_CENTRE
+        a, b, c = (d * d).sum(-1), 2 * (d @ oc), oc @ oc - E_RADIUS ** 2
+        disc = b * b - 4 * a * c
+        cands.append(np.where(disc > 0, (-b - np.sqrt(np.abs(disc))) / (2 * a), np.inf))
+        z = np.stack(cands)
+        z = np.where(z > 0, z, np.inf)
+        floor_xy = (o + cands[2][..., None] * d)[..., :2]
+    depth = z.min(axis=0)
+    surface = np.where(np.isfinite(depth), z.argmin(axis=0), -1)
+    return np.where(np.isfinite(depth), depth, 0.0), surface, floor_xy
+
+
+def edge_hole_footprint(pose, K, height, width):
+    """[H,W] bool: the floor is the nearest analytic surface and the ray meets it between the hole's voxel centres."""
+    _, surface, xy = edge_analytic(pose, K, height, width)
+    hx, hy = E_HOLE[0], E_HOLE[1]
+    with np.errstate(invalid="ignore"):
+        return ((surface == E_SURFACES.index("floor")) & (xy[..., 0] >= hx.start) & (xy[..., 0] <= hx.stop - 1) &
+                (xy[..., 1] >= hy.start) & (xy[..., 1] <= hy.stop - 1))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference():
+    """(scene, {name: (float64 run, float32 run)}) of the restatement over edge_views(), computed once; read-only."""
+    sc = edge_scene()
+    runs = {}
+    with np.errstate(all="ignore"):  # (the degenerate views divide by zero and carry NaN on purpose)
+        for name, pose, k, h, w, kw in edge_views():
+            runs[name] = tuple(raycast(sc["tsdf"], sc["tsdf_weight"], sc["axes"], pose, k, h, w, dtype=dt, **kw) for dt in (np.float64, np.float32))
+    for r in runs.values():
+        for x in r:
+            for a in x.values():
+                a.setflags(write=False)
+    return sc, runs
+
+
+def edge_counts(name):
+    """What a case exercises, from the float64 run alone: dict(pixels, hits, fragile, last_cell [H,W] bool (hits whose point has
+    g_z in [nz - 2, nz - 1]), hole [H,W] bool (edge_hole_footprint), hole_broken (those of them that miss or hit elsewhere than
+    the floor's two voxel planes), uncoloured [H,W] bool (hits on voxels with weight == 0))."""
+    sc, runs = edge_reference()
+    pose, k, h, w = next(c[1:5] for c in edge_views() if c[0] == name)
+    r64, r32 = runs[name]
+    nz = E_NVOX[2]
+    out = dict(pixels=h * w, hits=int(r64["hit"].sum()), fragile=fragile(r64, r32))
+    if np.isfinite(pose).all() and k[0, 0] != 0:
+        gz = point_in_grid(r64["depth"], sc["axes"], pose, k)[..., 2]
+        out["last_cell"] = r64["hit"] & (gz >= nz - 2) & (gz <= nz - 1)
+        out["hole"] = edge_hole_footprint(pose, k, h, w)
+    else:
+        out["last_cell"] = out["hole"] = np.zeros((h, w), dtype=bool)
+    out["hole_broken"] = out["hole"] & (~r64["hit"] | (r64["voxel"] % nz < nz - 2))
+    out["uncoloured"] = r64["hit"] & (sc["weight"][np.maximum(r64["voxel"], 0)] == 0)
+    return out
