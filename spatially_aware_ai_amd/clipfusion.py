@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
+from ._frame_queue import FrameQueue, StagingRing
 from ._lib import SafError, check, current_stream_ptr, lib, require_cuda
 
 _FRAME_WORDS = C.sizeof(_abi.SafFrame) // 8
@@ -115,19 +116,16 @@ class _FusionVolumeMixin:
         self._workspace = None
         self._shard_stripes = None  # [(first, count)] while the volume holds only its reduce-scattered stripes of a merged job
         self.__dict__.setdefault("defer_frames", True)  # queue small integrate() calls into 128-frame windows
-        self.__dict__["_pending_n"] = 0
-        self.__dict__["_stage"] = None
         self.__dict__["_feat_stale"] = False
-        self.__dict__["_session"] = None       # saf_fuse_session handle of the queue's flushes (created at the first one)
-        self.__dict__["_session_open"] = False  # a pushed window's row kernel is still owed (saf_fuse_session_finish)
-        self.__dict__["_fs"] = None             # the queue's own stream: a flush runs beside the staging of later frames
-        self.__dict__["_fs_event"] = None       # recorded behind the last finish: whoever reads the volume waits for it
+        # the queue behind integrate() (_frame_queue.py).  Not a registered buffer, so reading it never enters __getattr__; until
+        # this line has run there is none, and "no queue yet" reads as "idle" (__setattr__ is reached above)
+        self.__dict__["_queue"] = FrameQueue()
 
     def __del__(self):
-        h = self.__dict__.get("_session")
-        if h:
+        q = self.__dict__.get("_queue")
+        if q is not None:
             try:
-                lib().saf_fuse_session_destroy(h)
+                q.close()  # (destroys the session)
             except Exception:  # noqa: BLE001 -- interpreter shutdown
                 pass
 
@@ -229,18 +227,8 @@ class _FusionVolumeMixin:
         return (_abi.SafFrame * bsz).from_buffer(arr), (depth_imgs, rgb_imgs, poses, K, feat, labs), npy, npx
 
     # -- the deferred window queue ---------------------------------------------------------------
-    # The reference calls integrate() with ONE frame per DataLoader batch (clip_seem_fusion.py:303-313,
-    # clipfusion.py:1120-1133).  One frame per C call would run the per-frame pipeline; the windowed path
-    # (saf_fuse_frames with 16+ frames: every touched feature row travels to HBM once per 128-frame window)
-    # needs many frames in one call.  Small calls are therefore queued -- their inputs copied into a staging ring
-    # of four windows (512 slots) -- and handed to the library 32 at a time (round 6): every 32 staged frames are pushed into a
-    # streaming session (saf_fuse_session_push) on a stream of the queue's own -- one classification launch, which runs beside
-    # the row kernel of the window before; the 128th frame of a window brings its row kernel -- and the caller's stream goes on
-    # staging the next frames into the ring's other quarters meanwhile (rounds 2-5: one saf_fuse_frames call per flush on the
-    # caller's stream -- every flush exposed its first window's classification, 3.7 ms, could not start before the window's
-    # last frame was staged, 3 ms, and later frames' staging kernels queued behind the flush, 3 ms: 0.86-0.90 of the bulk rate).  Whatever reads or replaces the volume -- the registered buffers (attribute access, state_dict, .to()), stats(),
-    # extract_mesh, the merge -- pushes what is staged, finishes the session and lets its stream wait for it.
-    # The device paths are bit-identical, so a caller cannot tell -- except by speed.
+    # (what it is and why: _frame_queue.py, which owns its state; here are the decisions -- queue or fuse now, what a flush hands
+    #  over, session or one call -- and the knobs, readable and overridable per instance)
     _DEFER_MAX_BATCH = 15  # calls of 16+ frames take the windowed path by themselves
     # up to four windows per flush (from the second one on, a window is classified beside its predecessor's rows); a full
     # window is flushed earlier when the device has finished the previous flush and would otherwise idle
@@ -305,101 +293,13 @@ class _FusionVolumeMixin:
                     raise ValueError("label map must be [H,W]")
         # frames queued together share the shapes and, for deferred features, the backbone call and its autocast state
         key = (h, w, tuple(fshape), label_maps is not None, bool(rgb_bilinear), None if lazy is None else (id(lazy[0]),) + lazy[1:])
-        st = self.__dict__.get("_stage")
-        if st is None or st["key"] != key:
+        q = self.__dict__["_queue"]
+        ring = q.ring
+        if ring is None or ring.key != key:
             self._flush_pending(final=True)  # (the old ring's frames; the session of the old shape)
-            dev = self._buffers["tsdf"].device
-            n = self._QUEUE_FRAMES
-            mk = lambda *shape: torch.empty((n,) + shape, dtype=torch.float32, device=dev)
-            st = {"key": key, "depth": mk(h, w), "rgb": mk(h, w, 3), "pose": mk(4, 4), "K": mk(3, 3),
-                  "feat": mk(*key[2]), "labels": mk(h, w) if label_maps is not None else None, "lazy": lazy,
-                  # the frames staged and not yet handed over lie in slots [ring0, ring0 + _pending_n); free_ev[q]: the event
-                  # behind the row kernel that reads quarter q's frames (None: free); held: quarters whose row kernel is owed
-                  "ring0": 0, "free_ev": [None] * (self._QUEUE_FRAMES // _abi.SAF_WINDOW_FRAMES), "sess_frames": 0,
-                  # borrow_inputs: per slot the addresses of the caller's depth / rgb / label images that were NOT copied (0: the
-                  # ring's) and the tensors themselves, held until the slot is staged again (behind its row kernel's event)
-                  "bptr": np.zeros((n, 3), dtype=np.int64), "brefs": [None] * n,
-                  "src": _abi.SafFrame(h, w, None, None, None, None, None, key[2][1], key[2][2], None, 0),
-                  "dst": _abi.SafFrame(h, w, None, None, None, None, None, key[2][1], key[2][2], None, 0)}
-            # base addresses and byte strides of the ring's slots (no tensor views per call)
-            st["base"] = tuple(st[k].data_ptr() if st[k] is not None else 0 for k in ("depth", "rgb", "pose", "K", "feat", "labels"))
-            st["step"] = (4 * h * w, 12 * h * w, 64, 36, 4 * key[2][0] * key[2][1] * key[2][2], 4 * h * w)
-            self.__dict__["_stage"] = st
-        dev = self._buffers["tsdf"].device
-        with torch.cuda.device(dev):
-            # current_stream(dev), not current_stream(): without a device torch asks is_available() first, which looks up
-            # an environment variable by raising and catching a KeyError -- up to 100 us per call in a long-lived process
-            stream = torch.cuda.current_stream(dev)
-            fast = lazy is not None or (
-                all(t.dtype == f32 for t in (depth_imgs, rgb_imgs, poses, K, clip_feat_img)) and depth_imgs.is_contiguous()
-                and rgb_imgs.is_contiguous() and poses.is_contiguous() and K.is_contiguous() and
-                (label_maps is None or all(m.dtype == f32 and m.is_contiguous() for m in label_maps)))
-            src, dst, base, step = st["src"], st["dst"], st["base"], st["step"]
-            # (a deferred backbone reads the queued frames' rgb from the ring: nothing to borrow there)
-            borrow = fast and lazy is None and bool(self.__dict__.get("borrow_inputs", _BORROW_DEFAULT))
-            raw_stream = stream.cuda_stream
-            win = _abi.SAF_WINDOW_FRAMES
-            if fast:
-                fs = (0, 0, 0, 0) if lazy is not None else clip_feat_img.stride()
-                sp = (depth_imgs.data_ptr(), rgb_imgs.data_ptr(), poses.data_ptr(), K.data_ptr(),
-                      0 if lazy is not None else clip_feat_img.data_ptr())
-            for i in range(bsz):
-                k = self.__dict__["_pending_n"]
-                if st["ring0"] + k >= self._QUEUE_FRAMES:
-                    # a full ring means an earlier flush failed and kept its frames: try again (it re-raises) -- never
-                    # stage into a slot beyond the ring
-                    self._flush_pending()
-                    k = self.__dict__["_pending_n"]
-                    if st["ring0"] + k >= self._QUEUE_FRAMES:
-                        raise SafError("the staging ring is full and could not be flushed")
-                slot = st["ring0"] + k
-                if slot % win == 0:  # a quarter of the ring is reused: the row kernel that read its frames must be done
-                    ev = st["free_ev"][slot // win]
-                    if ev is not None:
-                        stream.wait_event(ev)
-                        st["free_ev"][slot // win] = None
-                if fast:  # one launch per frame (saf_stage_frame); addresses by arithmetic: no tensor views, no new descriptors
-                    src.depth, src.rgb, src.pose = sp[0] + i * step[0], sp[1] + i * step[1], sp[2] + i * 64
-                    src.K, src.feat_map = sp[3] + i * 36, (None if lazy is not None else sp[4] + i * fs[0] * 4)
-                    dst.depth, dst.rgb, dst.pose = base[0] + slot * step[0], base[1] + slot * step[1], base[2] + slot * step[2]
-                    dst.K, dst.feat_map = base[3] + slot * step[3], base[4] + slot * step[4]
-                    if label_maps is not None:
-                        src.label_map, dst.label_map = label_maps[i].data_ptr(), base[5] + slot * step[5]
-                    if borrow:  # the images stay where the caller has them: 5 MB per frame that are not copied
-                        st["bptr"][slot] = (src.depth, src.rgb, src.label_map or 0)
-                        st["brefs"][slot] = (depth_imgs, rgb_imgs, None if label_maps is None else label_maps[i])
-                        src.depth = src.rgb = src.label_map = dst.depth = dst.rgb = dst.label_map = None
-                    elif st["brefs"][slot] is not None:
-                        st["bptr"][slot] = 0
-                        st["brefs"][slot] = None
-                    check(lib().saf_stage_frame(C.byref(src), key[2][0], fs[1], fs[2], fs[3], C.byref(dst), raw_stream),
-                          "saf_stage_frame")
-                else:  # other dtypes / layouts: PyTorch copies convert
-                    if st["brefs"][slot] is not None:
-                        st["bptr"][slot] = 0
-                        st["brefs"][slot] = None
-                    st["depth"][slot].copy_(depth_imgs[i], non_blocking=True)
-                    st["rgb"][slot].copy_(rgb_imgs[i], non_blocking=True)
-                    st["pose"][slot].copy_(poses[i], non_blocking=True)
-                    st["K"][slot].copy_(K[i], non_blocking=True)
-                    st["feat"][slot].copy_(clip_feat_img[i], non_blocking=True)
-                    if label_maps is not None:
-                        st["labels"][slot].copy_(label_maps[i], non_blocking=True)
-                self.__dict__["_pending_n"] = k + 1
-                if (slot + 1) % self._PUSH_FRAMES == 0:
-                    # one classification launch's worth of frames is staged: their depth tiles are computed now, behind the staging
-                    # on this stream, and the chunk BEFORE them is handed over -- its staging and tiles have completed meanwhile
-                    # (the host needs 0.7 ms to stage 32 frames), so its launch is queued with no cross-stream wait in front
-                    # (a session's FIRST window is pushed chunk by chunk at once, each launch waiting for its frames: nothing runs
-                    #  beside it yet, a barrier in front of a launch costs nothing there, and the scan starts 0.7 ms earlier)
-                    self._prepare_chunk(st, slot + 1 - self._PUSH_FRAMES, self._PUSH_FRAMES, stream)
-                    if st["sess_frames"] < win:
-                        self._flush_pending()
-                    elif self.__dict__["_pending_n"] > self._PUSH_FRAMES:
-                        self._flush_pending(keep=self._PUSH_FRAMES)
-            if fast:  # the sources are read asynchronously on this stream
-                for t in (depth_imgs, rgb_imgs, poses, K) + (() if lazy is not None else (clip_feat_img,)) + tuple(label_maps or ()):
-                    t.record_stream(stream)
+            ring = q.ring = StagingRing(key, lazy, self._QUEUE_FRAMES, self._buffers["tsdf"].device)
+        q.stage(self, ring, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps,
+                bool(self.__dict__.get("borrow_inputs", _BORROW_DEFAULT)))
 
     def flush(self):
         """Bring the registered buffers up to date: fuse the frames queued behind integrate() and finish a deferred
@@ -423,106 +323,61 @@ class _FusionVolumeMixin:
 
     def _queue_busy(self):
         """Frames staged but not handed over, or a pushed window whose row kernel is still owed."""
-        return bool(self.__dict__.get("_pending_n", 0) or self.__dict__.get("_session_open"))
-
-    def _wait_for_queue(self):
-        """The current stream waits for what the queue's stream has been given (readers of the volume)."""
-        ev = self.__dict__.get("_fs_event")
-        if ev is not None:
-            dev = self._buffers["tsdf"].device
-            torch.cuda.current_stream(dev).wait_event(ev)
-
-    def _finish_session(self):
-        """Launch the row kernel of the window the session still holds (on the queue's stream) and let the current stream wait."""
-        if not self.__dict__.get("_session_open"):
-            self._wait_for_queue()
-            return
-        dev = self._buffers["tsdf"].device
-        fs = self.__dict__["_fs"]
-        with torch.cuda.device(dev):
-            rc = lib().saf_fuse_session_finish(self.__dict__["_session"], fs.cuda_stream)
-            self.__dict__["_session_open"] = False
-            ev = fs.record_event()
-            self.__dict__["_fs_event"] = ev
-            st = self.__dict__.get("_stage")
-            if st is not None:  # the open window's frames (and, conservatively, everybody's) are free behind `ev`
-                st["free_ev"] = [ev] * len(st["free_ev"])
-                st["sess_frames"] = 0
-                st["chunk_ready"] = {}
-            if rc != 0:  # its windows are classified and partly fused: nothing to retry
-                self.__dict__["_poisoned"] = "the queue's session could not launch its last row kernel; the volume is incomplete: reset() it"
-            check(rc, "saf_fuse_session_finish")
-            torch.cuda.current_stream(dev).wait_event(ev)
-
-    def _prepare_chunk(self, st, lo, n, stream):
-        """``saf_fuse_session_prepare`` for the staged frames in ring slots [lo, lo + n): their depth tiles, on ``stream`` behind
-        their staging, and the event a later push looks at (``hipEventQuery``).  A shape no session takes: nothing to do."""
-        if self.__dict__.get("_poisoned") or getattr(self, "_shard_stripes", None) is not None:
-            return
-        sl = slice(lo, lo + n)
-        labs = None if st["labels"] is None else st["labels"][sl]
-        arr, _keep, npy, npx = self._make_frames(st["depth"][sl], st["rgb"][sl], st["pose"][sl], st["K"][sl], st["feat"][sl], labs, st["key"][4],
-                                                 borrowed=st["bptr"][sl])
-        vol = self._c_volume(for_fuse=True)
-        ws = self._get_workspace(npy, npx, (int(st["depth"].shape[1]), int(st["depth"].shape[2])))
-        L = lib()
-        if L.saf_fuse_session_ok(C.byref(vol), arr, n, ws.numel()) != 1:
-            return
-        if self.__dict__.get("_session") is None:
-            self.__dict__["_session"] = L.saf_fuse_session_create()
-        if L.saf_fuse_session_prepare(self.__dict__["_session"], C.byref(vol), arr, n, ws.data_ptr(), ws.numel(), stream.cuda_stream) == 0:
-            st.setdefault("chunk_ready", {})[lo + n] = stream.record_event()  # keyed by the slot behind the chunk
+        q = self.__dict__.get("_queue")
+        return q is not None and q.busy()
 
     def _flush_pending(self, final=False, keep=0):
         """Hand the staged frames to the library.  ``final``: somebody is about to look -- the session is finished behind them
         (its last window's rows launched, the current stream waits); else the frames but the newest ``keep`` are pushed into
         the session (the newest chunk's staging and depth tiles are still running: it follows one chunk later, wait-free)."""
-        n = self.__dict__.get("_pending_n", 0) - (0 if final else keep)
-        keep = self.__dict__.get("_pending_n", 0) - n
+        q = self.__dict__.get("_queue")
+        if q is None:
+            return
+        n = q.pending - (0 if final else keep)
+        keep = q.pending - n
         if n <= 0:
             if final:
-                self._finish_session()
+                q.finish_session(self)
             return
         self._check_poisoned()
-        self.__dict__["_pending_n"] = 0  # first: the buffer accesses below must not re-enter
-        self.__dict__["_fuse_launched"] = False
-        st = self.__dict__["_stage"]
-        lo = st["ring0"]
+        q.pending = 0  # first: the buffer accesses below must not re-enter
+        q.launched = False
+        ring = q.ring
+        lo = ring.ring0
         sl = slice(lo, lo + n)
         try:
-            labs = None if st["labels"] is None else st["labels"][sl]
-            feat = st["feat"][sl]
-            if st.get("lazy") is not None:  # the queued frames' feature maps, in one backbone batch
-                fn, ac_on, ac_dtype = st["lazy"]
+            labs = None if ring.labels is None else ring.labels[sl]
+            feat = ring.feat[sl]
+            if ring.lazy is not None:  # the queued frames' feature maps, in one backbone batch
+                fn, ac_on, ac_dtype = ring.lazy
                 with torch.no_grad(), torch.autocast("cuda", dtype=ac_dtype, enabled=ac_on):
-                    feat = fn(st["rgb"][sl])
-                if tuple(feat.shape) != (n,) + tuple(st["key"][2]):
-                    raise SafError(f"the backbone returned {tuple(feat.shape)} for {n} frames, expected {(n,) + tuple(st['key'][2])}")
+                    feat = fn(ring.rgb[sl])
+                if tuple(feat.shape) != (n,) + tuple(ring.key[2]):
+                    raise SafError(f"the backbone returned {tuple(feat.shape)} for {n} frames, expected {(n,) + tuple(ring.key[2])}")
                 # into the ring: the last window's row kernel reads its maps when the NEXT push launches it -- a temporary of
                 # this call would be back in the allocator's hands by then (the ring's quarters are guarded by events)
-                st["feat"][sl].copy_(feat)
-                feat = st["feat"][sl]
-            self._fuse_now(st["depth"][sl], st["rgb"][sl], st["pose"][sl], st["K"][sl], feat, labs, st["key"][4], staged=(lo, n, final))
+                ring.feat[sl].copy_(feat)
+                feat = ring.feat[sl]
+            # (looked up on the instance at every flush: a test replaces it there)
+            self._fuse_now(ring.depth[sl], ring.rgb[sl], ring.pose[sl], ring.K[sl], feat, labs, ring.key[4], staged=(lo, n, final))
         except BaseException as exc:
-            if not self.__dict__.get("_fuse_launched"):
+            if not q.launched:
                 # the backbone, the descriptors or the argument checks at the entry of the fuse call failed (out of
                 # memory, an unsupported tiling) BEFORE any kernel touched the volume: the frames stay queued -- the next
                 # access raises again instead of reading a volume that silently lacks them
-                self.__dict__["_pending_n"] = n + keep
+                q.pending = n + keep
             else:
                 # the call failed after launching some of its windows: fusing the same frames again would count them
                 # twice, dropping them would lose them silently.  Neither: the volume is unusable until reset().
                 self.__dict__["_poisoned"] = f"a flush of {n} queued frames failed part-way ({exc!r}); the volume is incomplete: reset() it"
             raise
-        self.__dict__["_pending_n"] = keep
+        q.pending = keep
         if final:
-            self._finish_session()
-            st["ring0"] = 0  # (every quarter now carries the event of the finish, or of the call on the current stream)
-            if any(r is not None for r in st["brefs"]):  # lent images: read by now as far as this stream can tell -- let them go
-                st["brefs"] = [None] * len(st["brefs"])
-                st["bptr"][:] = 0
+            q.finish_session(self)
+            ring.ring0 = 0  # (every quarter now carries the event of the finish, or of the call on the current stream)
+            ring.release_borrowed()  # lent images: read by now as far as this stream can tell -- let them go
         else:
-            st["ring0"] = (lo + n) % self._QUEUE_FRAMES  # the next frames follow in the ring (a session's windows are its quarters)
+            ring.ring0 = (lo + n) % self._QUEUE_FRAMES  # the next frames follow in the ring (a session's windows are its quarters)
 
     def _check_poisoned(self):
         msg = self.__dict__.get("_poisoned")
@@ -532,19 +387,23 @@ class _FusionVolumeMixin:
     @property
     def pending_frames(self):
         """Frames staged behind integrate() and not yet handed to the fuse call (a completed window is handed over at once)."""
-        return self.__dict__.get("_pending_n", 0)
+        q = self.__dict__.get("_queue")
+        return 0 if q is None else q.pending
 
     def __getattr__(self, name):
         # registered buffers live in _buffers, so every read of one comes through here
         if name in _VOLUME_BUFFERS:
             if self.__dict__.get("_poisoned"):
                 self._check_poisoned()
+            q = self.__dict__.get("_queue")
             if name == "clip_feat" and self.__dict__.get("_feat_stale"):
                 self._sync_volume()  # queued frames AND the deferred clear: the rows are about to be looked at
-            elif self.__dict__.get("_pending_n", 0) or self.__dict__.get("_session_open"):
+            elif q is None:
+                pass
+            elif q.pending or q.session_open:
                 self._flush_pending(final=True)
-            elif self.__dict__.get("_fs_event") is not None:
-                self._wait_for_queue()  # (a reader on another stream than the one that finished the session)
+            elif q.event is not None:
+                q.wait(self)  # (a reader on another stream than the one that finished the session)
         return super().__getattr__(name)
 
     def __setattr__(self, name, value):
@@ -555,17 +414,10 @@ class _FusionVolumeMixin:
     def _apply(self, fn, *args, **kwargs):  # .to() / .cuda() / .cpu() / .float()
         if self._queue_busy() or self.__dict__.get("_feat_stale"):
             self._sync_volume()
-        self._wait_for_queue()
-        # the session's classification stream and events belong to the device the module leaves (the flush above has joined them)
-        h = self.__dict__.get("_session")
-        if h:
-            lib().saf_fuse_session_destroy(h)
-        self.__dict__["_session"] = None
-        self.__dict__["_session_open"] = False
-        self.__dict__["_stage"] = None
-        self.__dict__["_fs"] = None  # (a stream of the old device)
-        self.__dict__["_fs_event"] = None
-        self.__dict__["_fs_seen"] = None
+        q = self.__dict__.get("_queue")
+        if q is not None:
+            q.wait(self)
+            q.close()  # the session, the queue's stream and the ring belong to the device the module leaves
         return super()._apply(fn, *args, **kwargs)
 
     def _save_to_state_dict(self, *args, **kwargs):
@@ -585,90 +437,35 @@ class _FusionVolumeMixin:
         self._sync_volume()
         return super().named_buffers(*args, **kwargs)
 
-    def _queue_stream(self, dev, tensors):
-        """The queue's own stream (created at the first push); ``tensors`` it is about to use are marked for the allocator
-        (record_stream, once per allocation: whoever frees them -- a deleted module, a regrown workspace -- must not hand the
-        memory out while that stream still reads it)."""
-        fs = self.__dict__.get("_fs")
-        if fs is None:
-            fs = torch.cuda.Stream(device=dev)
-            self.__dict__["_fs"] = fs
-            self.__dict__["_fs_seen"] = set()
-        seen = self.__dict__.get("_fs_seen")
-        if seen is None:
-            seen = self.__dict__["_fs_seen"] = set()
-        for t in tensors:
-            if t is not None and t.data_ptr() not in seen:
-                seen.add(t.data_ptr())
-                t.record_stream(fs)
-        return fs
-
     def _fuse_now(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None, rgb_bilinear=False, staged=None):
         """``staged`` = (first ring slot, frames, final): the frames lie in the queue's staging ring -- where the windowed
         two-stream path takes them they are PUSHED into the queue's session on its own stream (their last window's row kernel
-        stays owed: ``_finish_session``); everything else is one call on the current stream, behind the session."""
+        stays owed: ``FrameQueue.finish_session``); everything else is one call on the current stream, behind the session."""
         if getattr(self, "_shard_stripes", None) is not None:
             raise SafError(
                 "this volume holds only its reduce-scattered voxel stripes "
                 f"({len(self._shard_stripes)} of them) of a merged job; all_gather it (distributed.gather_shards, or "
                 "merge_volumes(..., gather=True)) before fusing more frames"
             )
+        q = self.__dict__["_queue"]
         arr, keep, npy, npx = self._make_frames(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, rgb_bilinear,
-                                                borrowed=None if staged is None else self.__dict__["_stage"]["bptr"][staged[0]:staged[0] + staged[1]])
+                                                borrowed=None if staged is None else q.ring.bptr[staged[0]:staged[0] + staged[1]])
         vol = self._c_volume(for_fuse=True)
         ws = self._get_workspace(npy, npx, (int(depth_imgs.shape[1]), int(depth_imgs.shape[2])))
         L = lib()
         windowed = L.saf_fuse_path(C.byref(vol), arr, len(arr), ws.numel()) == 1
         # the module's device, not the caller's current one, owns the launch (and its current stream)
         dev = self._buffers["tsdf"].device
-        st = self.__dict__.get("_stage")
         win = _abi.SAF_WINDOW_FRAMES
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             # (a flush of a few frames with no window open takes the per-frame pipeline, as a direct call of that size does)
-            if staged is not None and (self.__dict__.get("_session_open") or len(arr) >= 16) and \
+            if staged is not None and (q.session_open or len(arr) >= 16) and \
                     L.saf_fuse_session_ok(C.byref(vol), arr, len(arr), ws.numel()) == 1:
-                lo, n, _final = staged
-                b = self._buffers
-                fs = self._queue_stream(dev, [ws, st["depth"], st["rgb"], st["pose"], st["K"], st["feat"], st["labels"]] +
-                                        [b.get(k) for k in ("tsdf", "tsdf_weight", "weight", "rgb", "clip_feat", "labels_one_hot",
-                                                            "axis_x", "axis_y", "axis_z", "fuse_stats")])
-                # the staging kernels (and a deferred backbone's maps) of these frames: what their classification waits for -- NOT
-                # the queue's stream, where the previous window's row kernel sits (the launches are to run beside it).  The
-                # session's first push also orders the queue's stream behind the caller's (reset()'s zeroing, an earlier finish)
-                # (a chunk whose tiles were prepared a chunk ago brings the event recorded behind them -- completed by now, the
-                #  library finds, and waits for nothing; anything else: an event behind what this stream holds now)
-                ready = (st.get("chunk_ready") or {}).pop(lo + n, None)
-                if ready is None or st.get("lazy") is not None:  # (a deferred backbone has just written these frames' maps: behind THAT)
-                    ready = stream.record_event()
-                for k in [k for k in (st.get("chunk_ready") or {}) if k <= lo + n]:
-                    del st["chunk_ready"][k]
-                if not self.__dict__.get("_session_open"):
-                    fs.wait_event(ready)
-                if self.__dict__.get("_session") is None:
-                    self.__dict__["_session"] = L.saf_fuse_session_create()
-                # (the depth tiles of these frames: on the caller's stream, behind their staging -- out of the classification chain)
-                rc = L.saf_fuse_session_push(self.__dict__["_session"], C.byref(vol), arr, len(arr), ws.data_ptr(), ws.numel(),
-                                             b["fuse_stats"].data_ptr(), fs.cuda_stream, ready.cuda_event, stream.cuda_stream)
-                st.setdefault("ready_evs", []).append(ready)  # (kept alive while the device may still wait for them)
-                del st["ready_evs"][:-8]
-                # SAF_E_INVALID / _WORKSPACE / _UNSUPPORTED come from the checks at the entry (every frame descriptor is validated
-                # before the first launch); a HIP error may have left some windows fused (see _flush_pending)
-                self.__dict__["_fuse_launched"] = rc == 0 or rc == _abi.SAF_E_HIP
-                if rc == 0:
-                    self.__dict__["_session_open"] = True
-                    ev = fs.record_event()
-                    self.__dict__["_fs_event"] = ev
-                    # the session's windows are the ring's quarters (a session starts at slot 0): the windows this push completed
-                    # have their row kernels queued -- behind `ev` their frames are free
-                    w0, w1 = st["sess_frames"] // win, (st["sess_frames"] + n) // win
-                    for w in range(w0, w1):
-                        st["free_ev"][w % len(st["free_ev"])] = ev
-                    st["sess_frames"] += n
-                check(rc, "saf_fuse_session_push")
+                q.push(self, vol, arr, ws, staged[0], staged[1], dev, stream)
                 return
             # one call on the current stream: whatever the session still owes comes first
-            self._finish_session()
+            q.finish_session(self)
             # after a lazy reset() the feature rows still hold the previous scan: the windowed path never reads a weight-0 row
             # (the clear stays owed until somebody looks: _sync_volume); the per-frame pipeline reads the rows it updates --
             # saf_fuse_frames_recycled zeroes the unwritten rows first
@@ -683,12 +480,12 @@ class _FusionVolumeMixin:
                 )
             if stale and rc == 0:  # (the recycled call: every weight-0 row is zero behind it)
                 self.__dict__["_feat_stale"] = False
-            self.__dict__["_fuse_launched"] = rc == 0 or rc == _abi.SAF_E_HIP
+            q.launched = rc == 0 or rc == _abi.SAF_E_HIP
             check(rc, "saf_fuse_frames")
             if staged is not None:  # the ring's slots of these frames are read on this stream
                 ev = stream.record_event()
-                for q in range(staged[0] // win, (staged[0] + staged[1] - 1) // win + 1):
-                    st["free_ev"][q] = ev
+                for quarter in range(staged[0] // win, (staged[0] + staged[1] - 1) // win + 1):
+                    q.ring.free_ev[quarter] = ev
             # the launches are asynchronous: keep inputs alive until the stream has consumed them
             for t in keep[:5]:
                 t.record_stream(stream)
@@ -702,27 +499,12 @@ class _FusionVolumeMixin:
         caller who wants them per scan zeroes ``fuse_stats``.  ``lazy``: the 4*D*N bytes of ``clip_feat`` are not cleared here -- a voxel
         with weight 0 has a zero row by contract and the windowed fuse path never reads such rows; the rows still
         unwritten are zeroed when something first looks (any buffer access, state_dict, the merge, flush())."""
-        self.__dict__["_pending_n"] = 0  # frames still queued would be fused into a volume that is being discarded
+        q = self.__dict__["_queue"]
+        q.pending = 0  # frames still queued would be fused into a volume that is being discarded
         self.__dict__["_poisoned"] = None
         self.__dict__["_feat_stale"] = False
         b = self._buffers
-        fs = self.__dict__.get("_fs")
-        if fs is not None:
-            # a pushed window whose row kernel is still owed is dropped with the volume; what the queue's stream and the
-            # library's classification stream already run must finish before the buffers are zeroed here: the abandon lets
-            # the queue's stream wait for the classification stream, the event recorded behind that wait covers both
-            if self.__dict__.get("_session") is not None:
-                with torch.cuda.device(b["tsdf"].device):
-                    check(lib().saf_fuse_session_abandon(self.__dict__["_session"], fs.cuda_stream), "saf_fuse_session_abandon")
-            self.__dict__["_session_open"] = False
-            ev = fs.record_event()
-            self.__dict__["_fs_event"] = ev
-            torch.cuda.current_stream(b["tsdf"].device).wait_event(ev)
-            st = self.__dict__.get("_stage")
-            if st is not None:
-                st["sess_frames"], st["ring0"] = 0, 0
-                st["free_ev"] = [ev] * len(st["free_ev"])
-                st["chunk_ready"] = {}
+        q.abandon(b["tsdf"].device)  # (the open window goes with the volume; this stream waits for what the queue's still runs)
         lazy = bool(lazy) and b["clip_feat"].is_cuda
         for name in ("rgb", "tsdf", "weight", "tsdf_weight", "labels_one_hot") + (() if lazy else ("clip_feat",)):
             t = b.get(name)

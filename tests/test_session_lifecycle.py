@@ -122,7 +122,7 @@ def _scan_reset_scan(s, config, n_before):
     seem, fdt, dim, dev_a, dev_b, fresh = _reset_case(s, config)
     mod = _build(s["grid"], seem, fdt, dim)
     _feed(mod, dev_a[:n_before])
-    assert mod.__dict__["_session"] is not None and mod.__dict__["_session_open"], "scan A must leave a session with a window open"
+    assert mod.__dict__["_queue"].session is not None and mod.__dict__["_queue"].session_open, "scan A must leave a session with a window open"
     mod.reset()  # at once: nothing has been read, the classification launches of the last pushes are queued or running
     # the counters go on counting over reset() by contract (the benchmark counts a job's frames over its resets): zeroed here, on
     # the stream reset() has just ordered behind the abandoned session -- without a read (`_buffers` does not flush) -- they are a
@@ -188,12 +188,12 @@ def test_move_mid_scan():
     dev = _upload(_small_frames(8101, 200, dim), dim, seem)
     moved, stayed = _build(grid, seem, fdt, dim), _build(grid, seem, fdt, dim)
     _feed(moved, dev[:100])
-    assert moved.__dict__["_session"] is not None and moved._queue_busy()
+    assert moved.__dict__["_queue"].session is not None and moved._queue_busy()
     moved = moved.cuda()
-    assert moved.__dict__["_session"] is None and not moved.__dict__["_session_open"] and moved.pending_frames == 0
+    assert moved.__dict__["_queue"].session is None and not moved.__dict__["_queue"].session_open and moved.pending_frames == 0
     _feed(moved, dev[100:])
     _feed(stayed, dev)
-    assert moved.pending_frames > 0 and moved.__dict__["_session"] is not None, "the second half must run in a session again"
+    assert moved.pending_frames > 0 and moved.__dict__["_queue"].session is not None, "the second half must run in a session again"
     _assert_equal(moved, stayed, seem, "a module moved mid-scan against one that was not")
     assert moved.stats()["window_rows"] > 0
 

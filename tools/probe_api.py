@@ -21,7 +21,7 @@ def job(times=None):
 job(); torch.cuda.synchronize()
 for ring in (int(x) for x in (sys.argv[1:] or ["256", "512"])):
     fz._QUEUE_FRAMES = ring
-    fz.__dict__["_stage"] = None
+    fz.__dict__["_queue"].ring = None
     job(); torch.cuda.synchronize()
     ts = []
     t0 = time.perf_counter(); job(ts); th = time.perf_counter() - t0; torch.cuda.synchronize(); tt = time.perf_counter() - t0
