@@ -109,7 +109,11 @@ typedef struct saf_frame {
  *      frame): [8] (brick, frame) pairs tested, and of those dropped because the brick lies [9] behind the camera, [10]
  *      farther than the frame's largest depth + trunc, [11] outside the view frustum, [12] more than trunc behind the largest
  *      depth of the pixels it projects onto (occluded).  A dropped pair has no valid and no tsdf-valid voxel; tests assert that
- *      every reason fires on the cameras they fuzz.  [13..15] reserved (0). */
+ *      every reason fires on the cameras they fuzz.
+ *  [13] [14] saf_unfuse_frames only (forward fusion leaves them 0): updates it skipped because the voxel's count was already 0 --
+ *      [13] on the weight side (valid voxels: weight, rgb, feature row, label count), [14] on the tsdf_weight side (tsdf-valid
+ *      voxels).  Non-zero means a frame was taken out that was never fused, or was fused under another pose.
+ *  [15] reserved (0). */
 #define SAF_STATS_WORDS 16
 /* frames per window of the windowed path of saf_fuse_frames (stats[5] and [6] count per window); SAF_WIN_FRAMES=64 in the
  * environment selects 64-frame windows */
@@ -174,6 +178,34 @@ int saf_fuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspac
  *    SAF_WINDOW=0 in the environment forces the per-frame pipeline. */
 int saf_fuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_frames,
                     void* workspace, size_t workspace_bytes, uint64_t* stats, void* stream);
+
+/* Take n_frames fused frames OUT of the volume again, in the order given (new capability: the de-integration step of a map
+ * that follows pose corrections; clipfusion.py has no counterpart -- its running means, :715-721 and clip_seem_fusion.py:736-744,
+ * :808-822, only ever grow).  Same descriptors and workspace as saf_fuse_frames; always the per-frame pipeline run backwards (one
+ * sweep + one row kernel per frame), whatever saf_fuse_path says forward, at every width and grid that pipeline takes.
+ * Which voxels a frame touches depends on the frame (depth, pose, K) and the grid only, never on the volume's state: the valid /
+ * tsdf-valid sets and the samples (clamped sdf, rgb, feature taps, label) are computed by the forward kernels' own code, so a
+ * frame leaves exactly the voxels it entered.  Per touched voxel with count w (weight, resp. tsdf_weight) before, w' = w - 1 after:
+ *   w' >= 1   x' = x * b - s * r   with  r = 1 / (float)w',  b = (float)w * r   -- in this order: r by IEEE division, b one rounded
+ *             product, x * b and s * r rounded separately, then one rounded difference (no FMA).  The TSDF takes r from the
+ *             hardware reciprocal (1 ulp), as the forward sweep does.  One removal adds about five roundings of the size of the
+ *             values involved, and an error already in the mean of w samples grows to w / (w - 1) of itself.
+ *   w' == 0   the voxel returns to its constructed state: exact zeros for the TSDF value, rgb and the whole feature row (never
+ *             x - s).  A volume with every frame taken out again is bit for bit a fresh one, and "a weight-0 voxel has a zero
+ *             row" holds without a clear pass.
+ *   w  == 0   guard: the update is skipped, nothing of the voxel is written, stats[13] (weight side) / stats[14] (tsdf_weight
+ *             side) count it.  Counts never go negative.
+ *   labels    minus one in the class the frame votes for, unless that count is already 0 (skipped, not counted); a label outside
+ *             [0, n_classes) was dropped forward (stats[3]) and is skipped here.
+ * stats[0..3] are not touched.  SAF_E_UNSUPPORTED, before anything is launched, for feat_dtype SAF_BF16 / SAF_F16 (a stored
+ * 16-bit mean carries 2^-9 / 2^-12 relative rounding, which a removal multiplies by about w) and for accum_mode SAF_SUM (sums
+ * belong to the multi-rank job).  A volume that saf_fuse_frames_recycled would take (rows of weight-0 voxels not yet cleared)
+ * must be cleared first (saf_clear_unwritten_rows): the guard never reads such rows, but w' == 0 relies on nothing else holding
+ * them. */
+int saf_unfuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_frames,
+                      void* workspace, size_t workspace_bytes, uint64_t* stats, void* stream);
+int saf_unfuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspace,
+                     size_t workspace_bytes, uint64_t* stats, void* stream);
 
 /* Copy one frame's inputs (depth, rgb, pose, K, feature map, label map -- all f32) from `src` into the buffers `dst`
  * points to, in ONE launch: the host queue behind integrate() keeps the frames of small calls in a staging ring until a

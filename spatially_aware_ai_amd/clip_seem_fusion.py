@@ -55,21 +55,27 @@ class ClipSeemFusion(_FusionVolumeMixin, torch.nn.Module):
     def integrate(self, depth_imgs, rgb_imgs, poses, K):
         """Reference clip_seem_fusion.py:676-822.  (The reference indexes ``labels[i]`` on a
         size-1 dimension and therefore only works for B = 1; any B works here.)"""
+        if not self.scale_patches_by_depth:
+            lazy = _lazy_clip_features(self, rgb_imgs)
+            if lazy is not None:  # the ViT runs when the queue is flushed, on all queued frames at once
+                rgb_chw = rgb_imgs.permute(0, 3, 1, 2)
+                label_maps = [self.segmentation_model.run_on_image(rgb_chw[i]).float().contiguous() for i in range(len(rgb_imgs))]
+                return self._fuse(depth_imgs, rgb_imgs, poses, K, None, label_maps, True, lazy_feat=lazy)
+        clip_feat_img, label_maps = self._frame_maps(depth_imgs, rgb_imgs, K)
+        self._fuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, True)
+
+    def _frame_maps(self, depth_imgs, rgb_imgs, K):
+        """The backbone calls of ``integrate``: (feature maps, label maps) -- shared with ``deintegrate`` / ``reintegrate``."""
         rgb_chw = rgb_imgs.permute(0, 3, 1, 2)
         if self.scale_patches_by_depth:
             clip_feat_img = self.clip.img_inference_tiled_depthscaled(
                 rgb_chw, depth_imgs, K, patch_stride=self.clip_patch_stride
             )
         else:
-            lazy = _lazy_clip_features(self, rgb_imgs)
-            if lazy is not None:  # the ViT runs when the queue is flushed, on all queued frames at once
-                label_maps = [self.segmentation_model.run_on_image(rgb_chw[i]).float().contiguous() for i in range(len(rgb_imgs))]
-                return self._fuse(depth_imgs, rgb_imgs, poses, K, None, label_maps, True, lazy_feat=lazy)
             clip_feat_img = self.clip.img_inference_tiled(
                 rgb_chw, patch_size=self.clip_patch_size, patch_stride=self.clip_patch_stride
             )
-        label_maps = [self.segmentation_model.run_on_image(rgb_chw[i]).float() for i in range(len(rgb_imgs))]
-        self._fuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, True)
+        return clip_feat_img, [self.segmentation_model.run_on_image(rgb_chw[i]).float() for i in range(len(rgb_imgs))]
 
     def extract_mesh(self, marching_cubes=None):
         """Reference clip_seem_fusion.py:824-888: the 6-tuple (verts_world, faces, vertex_colors,

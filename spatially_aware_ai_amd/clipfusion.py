@@ -522,6 +522,75 @@ class _FusionVolumeMixin:
         the benchmark and the parity tests)."""
         self._fuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, self._rgb_bilinear)
 
+    # -- taking fused frames out again (not in the reference: its running means only ever grow) --------------------------------
+    def _unfuse(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict):
+        """``saf_unfuse_frames`` (include/saf.h) behind everything handed to ``integrate()`` so far.  Returns the two skip
+        counters as they stood before the call (``strict``; a device sync) or None."""
+        if getattr(self, "_shard_stripes", None) is not None:
+            raise SafError(
+                "this volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
+                "(distributed.gather_shards, or merge_volumes(..., gather=True)) before taking frames out of it"
+            )
+        if self._buffers["clip_feat"].dtype != torch.float32:
+            raise SafError("frames are taken out of torch.float32 volumes only: a stored bf16 / fp16 mean carries 2^-9 / 2^-12 relative "
+                           "rounding, which taking a frame out multiplies by about the voxel's count (DESIGN 4.17)")
+        if self.accum_mode != _abi.SAF_RUNNING_MEAN:
+            raise SafError("frames are taken out of running means only: a SAF_SUM volume belongs to the multi-rank job (DESIGN 4.17)")
+        self._check_poisoned()
+        # what flush() does: the frames still queued, the row kernel a session owes, a deferred clear -- the current stream waits
+        self._sync_volume()
+        arr, keep, npy, npx = self._make_frames(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, self._rgb_bilinear)
+        vol = self._c_volume(for_fuse=True)
+        ws = self._get_workspace(npy, npx, (int(depth_imgs.shape[1]), int(depth_imgs.shape[2])))
+        dev = self._buffers["tsdf"].device
+        stats = self._buffers["fuse_stats"]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            before = stats[13:15].tolist() if strict else None
+            check(lib().saf_unfuse_frames(C.byref(vol), arr, len(arr), ws.data_ptr(), ws.numel(), stats.data_ptr(), stream.cuda_stream),
+                  "saf_unfuse_frames")
+            # the launches are asynchronous: keep inputs alive until the stream has consumed them
+            for t in keep[:5]:
+                t.record_stream(stream)
+            for t in keep[5] or ():
+                t.record_stream(stream)
+        return before
+
+    def _unfuse_strict(self, before):
+        if before is not None:
+            after = self._buffers["fuse_stats"][13:15].tolist()  # (synchronises)
+            if after != before:
+                raise SafError(f"de-integration skipped {after[0] - before[0]} valid and {after[1] - before[1]} tsdf-valid voxel updates "
+                               "whose count was already 0: these frames were not fused under these poses")
+
+    def deintegrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None, strict=False):
+        """The mirror of ``integrate_features``: take these frames OUT of the volume again, given the inputs they were fused with
+        (depth, pose and ``K`` decide which voxels a frame touches; rgb, feature and label maps what leaves them).  Frames still
+        queued behind ``integrate()`` are fused first.  A voxel whose last frame leaves is zero again, bit for bit; every other
+        running mean is within fp32 rounding of the mean without the frame.  A touched voxel whose count is already
+        0 -- the frame was never fused, or under another pose -- is skipped and counted (``stats()["deintegrate_skipped"]``);
+        ``strict=True`` synchronises and raises ``SafError`` if that happened during this call.  float32 running-mean volumes
+        only; a voxel-sharded (striped) volume is refused."""
+        self._unfuse_strict(self._unfuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict))
+
+    def reintegrate_features(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, clip_feat_img, label_maps=None, strict=False):
+        """Move fused frames to corrected poses: ``deintegrate_features`` under ``old_poses``, ``integrate_features`` under
+        ``new_poses``, with the same maps.  ``strict`` as there (the frames are put back either way)."""
+        before = self._unfuse(depth_imgs, rgb_imgs, old_poses, K, clip_feat_img, label_maps, strict)
+        self._fuse(depth_imgs, rgb_imgs, new_poses, K, clip_feat_img, label_maps, self._rgb_bilinear)
+        self._unfuse_strict(before)
+
+    def deintegrate(self, depth_imgs, rgb_imgs, poses, K, strict=False):
+        """The mirror of ``integrate``: the same backbone calls yield the feature (and label) maps, then ``deintegrate_features``."""
+        feat, label_maps = self._frame_maps(depth_imgs, rgb_imgs, K)
+        self.deintegrate_features(depth_imgs, rgb_imgs, poses, K, feat, label_maps, strict=strict)
+
+    def reintegrate(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, strict=False):
+        """What a user of ``refine_pose`` calls when a pose is corrected after its frame was fused: the frames leave the volume
+        under ``old_poses`` and enter it again under ``new_poses``.  The backbones run ONCE."""
+        feat, label_maps = self._frame_maps(depth_imgs, rgb_imgs, K)
+        self.reintegrate_features(depth_imgs, rgb_imgs, old_poses, new_poses, K, feat, label_maps, strict=strict)
+
     def stats(self):
         """dict of counters accumulated by the kernels (forces a device sync)."""
         s = self.fuse_stats.cpu().tolist()
@@ -539,7 +608,8 @@ class _FusionVolumeMixin:
         # the windowed path's frame cull: (brick, frame) pairs tested / dropped by reason (include/saf.h, stats[8..12])
         cull = {"pairs": s[8], "behind": s[9], "far": s[10], "frustum": s[11], "occluded": s[12]}
         return {"valid": s[0], "tsdf_valid": s[1], "frames": s[2], "labels_dropped": s[3], "window_rows": s[5],
-                "window_tsdf_voxels": s[6], "window_form": form, "cull": cull}
+                "window_tsdf_voxels": s[6], "window_form": form, "cull": cull,
+                "deintegrate_skipped": {"valid": s[13], "tsdf_valid": s[14]}}
 
     def sample_mesh_vertices(self, verts_index, voxel_obj_idx=None, objects_segmentation_color=None):
         """The sampling half of ``extract_mesh`` (reference clipfusion.py:741-760, clip_seem_fusion.py:843-878)
@@ -1250,18 +1320,22 @@ class ClipFusion(_FusionVolumeMixin, torch.nn.Module):
         """Fuse a batch of frames (reference clipfusion.py:627-721).  Batch elements are folded in
         one after the other; for B > 1 the reference updates the TSDF jointly over the batch
         (:681-695), which is the same mean up to fp32 rounding."""
-        if self.scale_patches_by_depth:
-            clip_feat_img = self.clip.img_inference_tiled_depthscaled(
-                rgb_imgs.permute(0, 3, 1, 2), depth_imgs, K, patch_stride=self.clip_patch_stride
-            )
-        else:
+        if not self.scale_patches_by_depth:
             lazy = _lazy_clip_features(self, rgb_imgs)
             if lazy is not None:
                 return self._fuse(depth_imgs, rgb_imgs, poses, K, None, None, False, lazy_feat=lazy)
-            clip_feat_img = self.clip.img_inference_tiled(
-                rgb_imgs.permute(0, 3, 1, 2), patch_size=self.clip_patch_size, patch_stride=self.clip_patch_stride
-            )
+        clip_feat_img, _ = self._frame_maps(depth_imgs, rgb_imgs, K)
         self._fuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, None, False)
+
+    def _frame_maps(self, depth_imgs, rgb_imgs, K):
+        """The backbone call of ``integrate``: (feature maps, None) -- shared with ``deintegrate`` / ``reintegrate``."""
+        if self.scale_patches_by_depth:
+            return self.clip.img_inference_tiled_depthscaled(
+                rgb_imgs.permute(0, 3, 1, 2), depth_imgs, K, patch_stride=self.clip_patch_stride
+            ), None
+        return self.clip.img_inference_tiled(
+            rgb_imgs.permute(0, 3, 1, 2), patch_size=self.clip_patch_size, patch_stride=self.clip_patch_stride
+        ), None
 
 
 # --------------------------------------------------------------------------------------------

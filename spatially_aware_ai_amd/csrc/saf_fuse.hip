@@ -20,6 +20,9 @@
 // (bit-identical).  All arithmetic that selects voxels is shared with the oracle's restatement in
 // spirit and checked bit-for-bit against it (saf_common.h); the device building blocks shared with the
 // windowed path live in saf_fuse_dev.h.
+//
+// saf_unfuse_frames runs the same pipeline BACKWARDS (template flag UNDO on the three kernels): a fused frame is taken out of
+// the running means exactly where it went in -- same sets, same samples, the blend turned round.
 #include <mutex>
 
 #include "saf_window_dev.h"
@@ -124,6 +127,10 @@ __device__ __forceinline__ uint32_t sdiv(uint32_t t, const SmallDiv& f) {
   return (uint32_t)(((float)t + 0.5f) * f.r);
 }
 
+// UNDO (saf_unfuse_frames): the same pass with phase D turned round -- the frame's clamped sdf is taken OUT of the TSDF
+// running mean (include/saf.h has the op order); a tsdf-valid voxel whose count is already 0 is skipped and counted in the
+// high word of the list counter in place of the tsdf-valid count (unfuse folds it into stats[14]).
+template <bool UNDO = false>
 __global__ __launch_bounds__(kSweepThreads) void sweep_kernel(KVol v, KFrame f,
                                                                unsigned long long* __restrict__ counts,
                                                                unsigned long long* __restrict__ next_counts,
@@ -224,6 +231,22 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_kernel(KVol v, KFrame f,
       for (int j = 0; j < kRun; ++j) {
         if (tv[j]) {
           const float t = sdf[j] > 1.0f ? 1.0f : sdf[j];
+          if constexpr (UNDO) {
+            if (w0[j] <= 0) {
+              ++nt_local;  // guard: nothing of this frame is in the voxel
+            } else {
+              const int wn = w0[j] - 1;
+              if (wn == 0) {
+                told[j] = 0.0f;  // back to the constructed state
+              } else {
+                // tsdf * (tsdf_weight / new_weight) - sdf / new_weight: phase D's shape with the roles turned round
+                const float rw = __builtin_amdgcn_rcpf((float)wn);
+                told[j] = told[j] * ((float)w0[j] * rw) - t * rw;
+              }
+              w0[j] = wn;
+            }
+            continue;
+          }
           const int w1 = w0[j] + 1;
           if (v.accum == SAF_SUM) {
             told[j] = told[j] + t;
@@ -340,6 +363,8 @@ __device__ __forceinline__ bool wait_for_sweep(const unsigned long long* __restr
 }
 
 // Once per frame (block 0, thread 0): fold the per-list counters into the caller's statistics.
+// UNDO: nothing is fused -- the high words are the sweep's skipped tsdf-valid voxels (stats[14]).
+template <bool UNDO = false>
 __device__ __forceinline__ void add_frame_stats(const unsigned long long* __restrict__ counts,
                                                 unsigned long long* __restrict__ stats) {
   if (stats && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -349,6 +374,10 @@ __device__ __forceinline__ void add_frame_stats(const unsigned long long* __rest
       nv += c & 0xffffffffull;
       nt += c >> 32;
     }
+    if constexpr (UNDO) {
+      if (nt) atomicAdd(&stats[14], nt);
+      return;
+    }
     atomicAdd(&stats[0], nv);
     atomicAdd(&stats[1], nt);
     atomicAdd(&stats[2], 1ull);
@@ -357,7 +386,8 @@ __device__ __forceinline__ void add_frame_stats(const unsigned long long* __rest
 
 // VEC: floats per lane access (4 when D % 4 == 0).  CPL: vector chunks per lane (compile-time,
 // 0 = runtime loop).  U: voxel rows in flight per lane group.  LDS_MAP: feature map staged in LDS.
-template <int VEC, int CPL, int U, bool LDS_MAP>
+// UNDO: the frame is taken out again (saf_unfuse_frames; unblend / fuse_scalars<true>, saf_fuse_dev.h).
+template <int VEC, int CPL, int U, bool LDS_MAP, bool UNDO = false>
 __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(KVol v, KFrame f,
                                                              const unsigned long long* __restrict__ counts,
                                                              const uint32_t* __restrict__ lists, uint32_t list_cap,
@@ -392,7 +422,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(KVol v, KFrame f,
   const uint32_t wg_in_list = blockIdx.x / kNumLists, wgs_per_list = gridDim.x / kNumLists;
   const uint32_t count = (uint32_t)__hip_atomic_load(&counts[list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint32_t* lst = lists + (size_t)list * list_cap;
-  add_frame_stats(counts, stats);
+  add_frame_stats<UNDO>(counts, stats);
   const uint32_t sid = (wg_in_list * (kFuseThreads / 64) + wave) * epw + slot;
   const uint32_t stride = wgs_per_list * (kFuseThreads / 64) * epw;
   V* feat = reinterpret_cast<V*>(v.feat);
@@ -445,7 +475,16 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(KVol v, KFrame f,
     for (int j = 0; j < U; ++j) {
       if (act[j]) {
         // a = 1 / new_weight ; b = weight * a                    clipfusion.py:716-717
-        a[j] = 1.0f / (float)(w0[j] + 1);
+        if constexpr (UNDO) {
+          if (w0[j] <= 0) {  // guard: nothing of this frame is in the voxel, nothing of it is written
+            if (gl == 0 && stats) atomicAdd(&stats[13], 1ull);
+            continue;
+          }
+          // a = 1 / new_weight (0: the voxel goes back to its constructed state) ; b = weight * a
+          a[j] = w0[j] > 1 ? 1.0f / (float)(w0[j] - 1) : 0.0f;
+        } else {
+          a[j] = 1.0f / (float)(w0[j] + 1);
+        }
         b[j] = (float)w0[j] * a[j];
         const Taps t = tp[j];
         if (CPL > 0) {
@@ -455,7 +494,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(KVol v, KFrame f,
             if (ch < DV) {
               const int mb = ch * ppad;
               const V s = lerp_taps(map[mb + t.o_nw], map[mb + t.o_ne], map[mb + t.o_sw], map[mb + t.o_se], bf[j]);
-              feat[(int64_t)n[j] * DV + ch] = blend(s, old[j][c], a[j], b[j], sum);
+              feat[(int64_t)n[j] * DV + ch] = UNDO ? unblend(s, old[j][c], a[j], b[j]) : blend(s, old[j][c], a[j], b[j], sum);
             }
           }
         } else {
@@ -463,10 +502,10 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(KVol v, KFrame f,
             const int mb = ch * ppad;
             const V s = lerp_taps(map[mb + t.o_nw], map[mb + t.o_ne], map[mb + t.o_sw], map[mb + t.o_se], bf[j]);
             V* dst = feat + (int64_t)n[j] * DV + ch;
-            *dst = blend(s, *dst, a[j], b[j], sum);
+            *dst = UNDO ? unblend(s, *dst, a[j], b[j]) : blend(s, *dst, a[j], b[j], sum);
           }
         }
-        fuse_scalars(v, f, cam, n[j], gx[j], gy[j], w0[j], a[j], b[j], gl, G, stats);
+        fuse_scalars<UNDO>(v, f, cam, n[j], gx[j], gy[j], w0[j], a[j], b[j], gl, G, stats);
       }
     }
   }
@@ -529,7 +568,9 @@ __device__ __forceinline__ RowCtx fetch_row(int src, uint32_t n_l, float a_l, fl
 // samples are blended in fp32 exactly as for the fp32 volume and rounded to nearest-even once per
 // update.  F16 (with BF16): the 16-bit elements are IEEE half instead -- same layout, same fp32 blend, one nearest-even
 // conversion per update (h16_lo / h16_hi / pack_h16, saf_common.h).
-template <int CPL, int R, bool G64, bool LDS_MAP, bool SUM, bool BF16, bool F16 = false>
+// UNDO (f32 running means only): the frame is taken out again.  A row's case travels in the broadcast `a`: -1 = guard (the
+// voxel's count is 0: nothing is stored), 0 = the count returns to 0 (exact zeros are stored), else 1 / new_weight.
+template <int CPL, int R, bool G64, bool LDS_MAP, bool SUM, bool BF16, bool F16 = false, bool UNDO = false>
 __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame f,
                                                                   const unsigned long long* __restrict__ counts,
                                                                   const uint32_t* __restrict__ lists,
@@ -555,7 +596,8 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
   const Cam cam = load_cam(f.pose, f.K, f.W, f.H);
   const float half_px = (float)f.npx / 2.0f, half_py = (float)f.npy / 2.0f;
   constexpr bool sum = SUM;
-  add_frame_stats(counts, stats);
+  static_assert(!UNDO || (!SUM && !BF16), "frames are taken out of f32 running means only");
+  add_frame_stats<UNDO>(counts, stats);
 
   const int G = G64 ? 64 : (1 << g_log2);
   const int lane = tid & 63, wave = tid >> 6;
@@ -594,7 +636,10 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
       const Proj p = project(cam, v.ax[ix], v.ay[iy], v.az[iz]);
       const int w0 = v.weight[n_l];
       // a = 1 / new_weight ; b = weight * a                        clipfusion.py:716-717
-      a_l = 1.0f / (float)(w0 + 1);
+      if constexpr (UNDO)
+        a_l = w0 <= 0 ? -1.0f : (w0 > 1 ? 1.0f / (float)(w0 - 1) : 0.0f);
+      else
+        a_l = 1.0f / (float)(w0 + 1);
       b_l = (float)w0 * a_l;
       const float x = unnormalize(p.gx, half_px), y = unnormalize(p.gy, half_py);
       const float xw = __builtin_floorf(x), yn = __builtin_floorf(y);
@@ -603,7 +648,11 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
       // tap cell, clamped to [-1, size] (everything outside is zero padding anyway)
       const int x0 = (int)fminf(fmaxf(xw, -1.0f), (float)f.npx), y0 = (int)fminf(fmaxf(yn, -1.0f), (float)f.npy);
       xy_l = (x0 + 1) | ((y0 + 1) << 16);
-      fuse_scalars_lane(v, f, cam, n_l, p.gx, p.gy, w0, a_l, b_l, stats);
+      if (!UNDO || w0 > 0) fuse_scalars_lane<UNDO>(v, f, cam, n_l, p.gx, p.gy, w0, a_l, b_l, stats);
+    }
+    if constexpr (UNDO) {  // the batch's guarded voxels, one atomic per wave
+      const unsigned long long skipped = __ballot(a_l < 0.0f);
+      if (stats && lane == 0 && skipped) atomicAdd(&stats[13], (unsigned long long)__popcll(skipped));
     }
     // ---------------- row loop: groups of G lanes, R rows in flight per group ----------------
     const int steps = (nb + epw - 1) / epw;
@@ -628,10 +677,12 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
       out_.y = __builtin_bit_cast(float, pack_h16<F16>(n0_.z, n0_.w));                                     \
       out_.z = __builtin_bit_cast(float, pack_h16<F16>(n1_.x, n1_.y));                                     \
       out_.w = __builtin_bit_cast(float, pack_h16<F16>(n1_.z, n1_.w));                                     \
+    } else if (UNDO) {                                                                                 \
+      out_ = unblend(SAF_TAPS(c, 0, ctx_), old_[c], (ctx_).a, (ctx_).b);                               \
     } else {                                                                                           \
       out_ = blend(SAF_TAPS(c, 0, ctx_), old_[c], (ctx_).a, (ctx_).b, sum);                            \
     }                                                                                                  \
-    st_stream(&feat[(int64_t)(ctx_).n * DU + chs[c]], out_);                                           \
+    if (!UNDO || (ctx_).a >= 0.0f) st_stream(&feat[(int64_t)(ctx_).n * DU + chs[c]], out_);            \
   }
     int i0 = 0;
     if (steps >= R) {
@@ -675,7 +726,8 @@ using FuseFn = void (*)(KVol, KFrame, const unsigned long long*, const uint32_t*
                         const float*, int, unsigned long long*, const unsigned long long*, unsigned long long);
 
 template <int VEC, int CPL, int U>
-FuseFn pick_lds(bool lds) {
+FuseFn pick_lds(bool lds, bool undo) {
+  if (undo) return lds ? fuse_kernel<VEC, CPL, U, true, true> : fuse_kernel<VEC, CPL, U, false, true>;
   return lds ? fuse_kernel<VEC, CPL, U, true> : fuse_kernel<VEC, CPL, U, false>;
 }
 
@@ -690,9 +742,15 @@ FuseFn pick_rows_f16(bool g64, bool lds) {  // fp16 volumes: running mean only (
   if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, false, true, true> : fuse_rows_kernel<CPL, R, true, false, false, true, true>;
   return lds ? fuse_rows_kernel<CPL, R, false, true, false, true, true> : fuse_rows_kernel<CPL, R, false, false, false, true, true>;
 }
+template <int CPL, int R>
+FuseFn pick_rows_undo(bool g64, bool lds) {  // saf_unfuse_frames: f32 running means only
+  if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, false, false, false, true> : fuse_rows_kernel<CPL, R, true, false, false, false, false, true>;
+  return lds ? fuse_rows_kernel<CPL, R, false, true, false, false, false, true> : fuse_rows_kernel<CPL, R, false, false, false, false, false, true>;
+}
 // e16: the volume's 16-bit element type (KVol::e16); fp16 volumes have no SAF_SUM (make_kvol)
 template <int CPL, int R>
-FuseFn pick_rows(bool g64, bool lds, bool sum, int e16) {
+FuseFn pick_rows(bool g64, bool lds, bool sum, int e16, bool undo = false) {
+  if (undo) return pick_rows_undo<CPL, R>(g64, lds);
   if (e16 == kE16Half) return pick_rows_f16<CPL, R>(g64, lds);
   if (e16) return sum ? pick_rows3<CPL, R, true, true>(g64, lds) : pick_rows3<CPL, R, false, true>(g64, lds);
   return sum ? pick_rows3<CPL, R, true, false>(g64, lds) : pick_rows3<CPL, R, false, false>(g64, lds);
@@ -701,7 +759,7 @@ FuseFn pick_rows(bool g64, bool lds, bool sum, int e16) {
 int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float* feat_map,
                 const unsigned long long* counts, const unsigned char* half, unsigned long long* stats,
                 const unsigned long long* sweep_done, unsigned long long sweep_target, bool shared_cus, const Knobs& kn,
-                hipStream_t s) {
+                hipStream_t s, bool undo = false) {
   const int D = kv.D, P = kf.npy * kf.npx;
   const bool rows16 = kv.e16 != 0;  // 16-bit rows (bf16 or fp16): 8 channels per 16-byte unit
   const int VEC = (D % 4 == 0) ? 4 : 1;
@@ -726,15 +784,15 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
   } else if (VEC == 4 && cpl >= 1 && cpl <= 4) {
     const bool g64 = G == 64;
     switch (cpl) {
-      case 1: fn = pick_rows<1, 4>(g64, lds, sum, kE16None); break;
-      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kE16None); break;
-      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kE16None); break;
-      default: fn = pick_rows<4, 2>(g64, lds, sum, kE16None); break;
+      case 1: fn = pick_rows<1, 4>(g64, lds, sum, kE16None, undo); break;
+      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kE16None, undo); break;
+      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kE16None, undo); break;
+      default: fn = pick_rows<4, 2>(g64, lds, sum, kE16None, undo); break;
     }
   } else if (VEC == 4) {
-    fn = pick_lds<4, 0, 1>(lds);
+    fn = pick_lds<4, 0, 1>(lds, undo);
   } else {
-    fn = (cpl == 1) ? pick_lds<1, 1, 4>(lds) : pick_lds<1, 0, 1>(lds);
+    fn = (cpl == 1) ? pick_lds<1, 1, 4>(lds, undo) : pick_lds<1, 0, 1>(lds, undo);
   }
   const size_t shmem = lds ? lds_map_bytes(D, P) : 0;
   if (shmem > 64 * 1024) {
@@ -823,7 +881,7 @@ inline unsigned long long* sweep_done_ptr(unsigned char* ws) {
 
 // sweep (and, for maps too large for LDS, the map image) of frame `frame_no` into list buffer `buf`
 int launch_classify(const KVol& kv, const FrameJob& job, unsigned char* ws, unsigned char* buf, int64_t frame_no,
-                    saf_profiler* prof, hipStream_t s) {
+                    saf_profiler* prof, hipStream_t s, bool undo = false) {
   const WsLayout& w = job.w;
   uint32_t* lists = reinterpret_cast<uint32_t*>(buf + w.lists_off);
   int rc;
@@ -836,18 +894,18 @@ int launch_classify(const KVol& kv, const FrameJob& job, unsigned char* ws, unsi
     if ((rc = check_launch("prep_kernel"))) return rc;
   }
   ScopedPair t(prof, 1, frame_no, s);
-  hipLaunchKernelGGL(sweep_kernel, dim3(w.n_blocks), dim3(kSweepThreads), 0, s, kv, job.kf,
+  hipLaunchKernelGGL(undo ? sweep_kernel<true> : sweep_kernel<false>, dim3(w.n_blocks), dim3(kSweepThreads), 0, s, kv, job.kf,
                      counter_set(ws, frame_no), counter_set(ws, frame_no + 1), lists, w.list_cap, sweep_done_ptr(ws));
   return check_launch("sweep_kernel");
 }
 
 int launch_rows(const KVol& kv, const FrameJob& job, unsigned char* ws, unsigned char* buf, int64_t frame_no,
-                uint64_t* stats, bool shared_cus, const Knobs& kn, saf_profiler* prof, hipStream_t s) {
+                uint64_t* stats, bool shared_cus, const Knobs& kn, saf_profiler* prof, hipStream_t s, bool undo = false) {
   ScopedPair t(prof, 2, frame_no, s);
   // the fuse kernel starts once the sweeps of frames 0..frame_no have published all their blocks
   const unsigned long long target = (unsigned long long)(frame_no + 1) * job.w.n_blocks;
   return launch_fuse(kv, job.kf, job.w, job.feat_map, counter_set(ws, frame_no), buf,
-                     reinterpret_cast<unsigned long long*>(stats), sweep_done_ptr(ws), target, shared_cus, kn, s);
+                     reinterpret_cast<unsigned long long*>(stats), sweep_done_ptr(ws), target, shared_cus, kn, s, undo);
 }
 
 // The auxiliary stream and events of the two-stream pipeline are pooled per device (creating and destroying
@@ -977,11 +1035,13 @@ int latch_entry() {
 // Everything is ordered after what the caller already queued on `s` (fork event), and complete,
 // as far as `s` is concerned, when the last fuse kernel is (it has waited for every sweep).
 int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
-              uint64_t* stats, saf_profiler* prof, hipStream_t s, const Knobs& kn, const WinSlabs* slabs = nullptr, bool recycled = false) {
+              uint64_t* stats, saf_profiler* prof, hipStream_t s, const Knobs& kn, const WinSlabs* slabs = nullptr, bool recycled = false,
+              bool undo = false) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
-  const bool windowed = fuse_route(kv, frames, n_frames, workspace_bytes, kn).path != kPathPerFrame;
+  // undo (saf_unfuse_frames: no slabs, not recycled): always the per-frame pipeline below, its kernels run backwards
+  const bool windowed = !undo && fuse_route(kv, frames, n_frames, workspace_bytes, kn).path != kPathPerFrame;
   if (recycled && !windowed) {
     // the per-frame pipeline reads every row it updates: the rows of weight-0 voxels are zeroed first (of the slabs, if the
     // call names slabs: voxels outside them are not this call's)
@@ -1022,8 +1082,8 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
       FrameJob job;
       if ((rc = make_job(kv, &frames[i], workspace, workspace_bytes, &job))) return rc;
       unsigned char* buf = ws + kHdrBytes;
-      if ((rc = launch_classify(kv, job, ws, buf, i, prof, s))) return rc;
-      if ((rc = launch_rows(kv, job, ws, buf, i, stats, false, kn, prof, s))) return rc;
+      if ((rc = launch_classify(kv, job, ws, buf, i, prof, s, undo))) return rc;
+      if ((rc = launch_rows(kv, job, ws, buf, i, stats, false, kn, prof, s, undo))) return rc;
     }
     return SAF_OK;
   }
@@ -1042,8 +1102,8 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
       const int32_t j = (i - kListBuffers) | 1;
       SAF_HIP_TRY(hipStreamWaitEvent(aux, pr->fused[(j >> 1) % kEvRing], 0));
     }
-    if ((rc = launch_classify(kv, job, ws, buf, i, prof, aux))) goto done;
-    if ((rc = launch_rows(kv, job, ws, buf, i, stats, true, kn, prof, s))) goto done;
+    if ((rc = launch_classify(kv, job, ws, buf, i, prof, aux, undo))) goto done;
+    if ((rc = launch_rows(kv, job, ws, buf, i, stats, true, kn, prof, s, undo))) goto done;
     if (i & 1) SAF_HIP_TRY(hipEventRecord(pr->fused[(i >> 1) % kEvRing], s));
   }
 done:
@@ -1140,6 +1200,28 @@ int saf_fuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspac
                    uint64_t* stats, void* stream) {
   if (!frame) return fail(SAF_E_INVALID, "frame is NULL");
   return saf_fuse_frames_profiled(vol, frame, 1, workspace, workspace_bytes, stats, nullptr, stream);
+}
+
+int saf_unfuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
+                      size_t workspace_bytes, uint64_t* stats, void* stream) {
+  KVol kv;
+  int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
+  if (rc) return rc;
+  if (vol->feat_dtype != SAF_F32)
+    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames takes SAF_F32 volumes only: a stored bf16 / fp16 mean carries 2^-9 / 2^-12 "
+                                   "relative rounding, which taking a frame out multiplies by about the voxel's count");
+  if (vol->accum_mode != SAF_RUNNING_MEAN)
+    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames takes SAF_RUNNING_MEAN volumes only (sums belong to the multi-rank job)");
+  if (n_frames == 0) return SAF_OK;
+  if ((rc = latch_entry())) return rc;
+  return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, static_cast<hipStream_t>(stream), read_knobs(),
+                   nullptr, false, true);
+}
+
+int saf_unfuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspace, size_t workspace_bytes,
+                     uint64_t* stats, void* stream) {
+  if (!frame) return fail(SAF_E_INVALID, "frame is NULL");
+  return saf_unfuse_frames(vol, frame, 1, workspace, workspace_bytes, stats, stream);
 }
 
 int saf_poll_async_error(void) { return poll_latch(); }

@@ -112,6 +112,14 @@ __device__ __forceinline__ float blend(float s, float old, float a, float b, boo
   return sum ? old + s : s * a + old * b;
 }
 
+// The blend turned round (saf_unfuse_frames): a sample leaves a running mean.  r = 1 / new_weight, b = weight * r:
+// old * b - s * r, two rounded products and one rounded difference (no FMA: contraction is off in these units).  r == 0 stands
+// for new_weight == 0: the voxel returns to its constructed state, exact zeros whatever the sample holds.
+__device__ __forceinline__ float unblend(float s, float old, float r, float b) { return r == 0.0f ? 0.0f : old * b - s * r; }
+__device__ __forceinline__ float4 unblend(float4 s, float4 old, float r, float b) {
+  return make_float4(unblend(s.x, old.x, r, b), unblend(s.y, old.y, r, b), unblend(s.z, old.z, r, b), unblend(s.w, old.w, r, b));
+}
+
 struct Taps {
   int o_nw, o_ne, o_sw, o_se;  // tap positions in [0, P]; P = the zero column (outside the map)
 };
@@ -128,6 +136,8 @@ __device__ __forceinline__ Taps tap_offsets(const Bilin& b, int npx, int npy) {
 }
 
 // rgb / weight / label side of one valid voxel, done by lane `gl` of the group of `G` lanes.
+// UNDO: the frame's sample leaves the voxel (a = 1 / new_weight, 0 when the voxel empties; the caller has w0 >= 1).
+template <bool UNDO = false>
 __device__ __forceinline__ void fuse_scalars(const KVol& v, const KFrame& f, const Cam& cam, uint32_t n, float gx,
                                              float gy, int w0, float a, float b, int gl, int G,
                                              unsigned long long* stats) {
@@ -157,18 +167,21 @@ __device__ __forceinline__ void fuse_scalars(const KVol& v, const KFrame& f, con
         s = pix >= 0 ? f.rgb[(int64_t)pix * 3 + ch] : 0.f;
       }
       float* dst = v.rgb + (int64_t)n * 3 + ch;
-      *dst = blend(s, *dst, a, b, sum);
+      *dst = UNDO ? unblend(s, *dst, a, b) : blend(s, *dst, a, b, sum);
     }
     if (gl == 0) {
-      v.weight[n] = w0 + 1;  // clipfusion.py:715, :721
+      v.weight[n] = UNDO ? w0 - 1 : w0 + 1;  // clipfusion.py:715, :721
       if (v.labels && f.label_map) {
         // labels = grid_sample(pano_seg.float(), nearest); one_hot(labels.long())  clip_seem_fusion.py:786-822
         const float lf = pix >= 0 ? f.label_map[pix] : 0.f;
         const long long l = (long long)lf;
         if (l >= 0 && l < v.n_classes) {
           int* c = v.labels + (int64_t)n * v.n_classes + l;
-          *c = *c + 1;
-        } else if (stats) {
+          if (!UNDO)
+            *c = *c + 1;
+          else if (*c > 0)  // (a count never goes below 0)
+            *c = *c - 1;
+        } else if (stats && !UNDO) {
           atomicAdd(&stats[3], 1ull);
         }
       }
@@ -223,7 +236,8 @@ __device__ __forceinline__ int sample_rgb_lane(const KFrame& f, const Cam& cam, 
 }
 // labels = grid_sample(pano_seg.float(), nearest); one_hot(labels.long())          clip_seem_fusion.py:786-822
 // ATOMIC: several hits of one voxel may be counted by different lanes at the same time (integer adds commute).
-template <bool ATOMIC>
+// UNDO (never with ATOMIC): the frame's vote is taken back -- a count never goes below 0, a label that was dropped forward is skipped.
+template <bool ATOMIC, bool UNDO = false>
 __device__ __forceinline__ void count_label_lane(const KVol& v, const KFrame& f, uint32_t n, int pix,
                                                  unsigned long long* stats) {
   if (v.labels && f.label_map) {
@@ -232,15 +246,19 @@ __device__ __forceinline__ void count_label_lane(const KVol& v, const KFrame& f,
     const long long l = (long long)lf;
     if (l >= 0 && l < v.n_classes) {
       int* c = v.labels + (int64_t)n * v.n_classes + l;
-      if (ATOMIC)
+      if (UNDO) {
+        if (*c > 0) *c = *c - 1;
+      } else if (ATOMIC) {
         atomicAdd(c, 1);
-      else
+      } else {
         *c = *c + 1;
-    } else if (stats) {
+      }
+    } else if (stats && !UNDO) {
       atomicAdd(&stats[3], 1ull);
     }
   }
 }
+template <bool UNDO = false>
 __device__ __forceinline__ void fuse_scalars_lane(const KVol& v, const KFrame& f, const Cam& cam, uint32_t n,
                                                   float gx, float gy, int w0, float a, float b,
                                                   unsigned long long* stats) {
@@ -249,11 +267,11 @@ __device__ __forceinline__ void fuse_scalars_lane(const KVol& v, const KFrame& f
   const int pix = sample_rgb_lane(f, cam, gx, gy, s0, s1, s2);
   float* dst = v.rgb + (int64_t)n * 3;
   const float o0 = dst[0], o1 = dst[1], o2 = dst[2];
-  dst[0] = blend(s0, o0, a, b, sum);
-  dst[1] = blend(s1, o1, a, b, sum);
-  dst[2] = blend(s2, o2, a, b, sum);
-  v.weight[n] = w0 + 1;  // clipfusion.py:715, :721
-  count_label_lane<false>(v, f, n, pix, stats);
+  dst[0] = UNDO ? unblend(s0, o0, a, b) : blend(s0, o0, a, b, sum);
+  dst[1] = UNDO ? unblend(s1, o1, a, b) : blend(s1, o1, a, b, sum);
+  dst[2] = UNDO ? unblend(s2, o2, a, b) : blend(s2, o2, a, b, sum);
+  v.weight[n] = UNDO ? w0 - 1 : w0 + 1;  // clipfusion.py:715, :721
+  count_label_lane<false, UNDO>(v, f, n, pix, stats);
 }
 
 int make_kframe(const saf_frame* fr, KFrame* kf) {
