@@ -227,11 +227,7 @@ __device__ __forceinline__ void walk_issue(const BrickLds<CPL>& L, const WalkCtx
   for (int u = 0; u <= kP; ++u) b.hl[u] = __builtin_amdgcn_readlane(hs, u);
 #pragma unroll
   for (int u = 0; u < kP; ++u) {
-#ifdef SAF_BRICK_NOTAPS  // ablation: every tap outside the buffer (no L2 -> L1 traffic, same instruction stream)
-    const uint4 o = L.walk.grp_off[cx.G];
-#else
     const uint4 o = L.walk.grp_off[min(g0 + u, cx.G)];  // entry G: four offsets beyond the buffer (no such group: nothing moves)
-#endif
     tp[u][0] = tap_load<CPL>(cx.maps, o.x + cx.lane_off);
     tp[u][1] = tap_load<CPL>(cx.maps, o.y + cx.lane_off);
     tp[u][2] = tap_load<CPL>(cx.maps, o.z + cx.lane_off);
@@ -265,11 +261,7 @@ __device__ __forceinline__ void walk_process(BrickLds<CPL>& L, const WalkCtx& cx
 #pragma unroll
     for (int u = 0; u < kP; ++u) {
       const int l0 = max(b.hl[u], c0), l1 = min(b.hl[u + 1], c1);
-#ifdef SAF_BRICK_NOHITS  // ablation: no per-hit work at all
-      for (int l = l0; l < l0; ++l) {
-#else
       for (int l = l0; l < l1; ++l) {
-#endif
         const int li = l - c0;
         const float wnw = rl_f(w_nw, li), wne = rl_f(w_ne, li), wsw = rl_f(w_sw, li), wse = rl_f(w_se, li);
         const int idx = __builtin_amdgcn_readlane(rowbase, li) - li + cx.lane;  // the hit's row, this lane
@@ -299,13 +291,7 @@ __device__ __forceinline__ void walk_process(BrickLds<CPL>& L, const WalkCtx& cx
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
           const float s = sv[c];
-#ifdef SAF_BRICK_NOATOM  // ablation: a plain LDS store instead of the atomic add (wrong sums, same instruction count)
-          if (true) {
-            L.acc[idx + c * 64] = cvt_rpi(s);
-          } else if (FX) {
-#else
           if (FX) {
-#endif
             __hip_atomic_fetch_add(&L.acc[idx + c * 64], cvt_rpi(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           } else {
             __hip_atomic_fetch_add(reinterpret_cast<float*>(&L.acc[idx + c * 64]), s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -539,11 +525,7 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
                 o.x = old[i].x * b + sm[0]; o.y = old[i].y * b + sm[1];
                 o.z = old[i].z * b + sm[2]; o.w = old[i].w * b + sm[3];
               }
-#ifndef SAF_BRICK_NOROWS  // ablation: no row stores (and no row loads below)
               st_stream(gp, o);
-#else
-              asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-#endif
             }
           }
           // (a loop of its own: behind each store, a load would make the wait-count pass drain the queue in every
@@ -552,10 +534,8 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
 #pragma unroll
             for (int i = 0; i < kMI; ++i) {
               const int mr = (i * kRPI + m_sub) * kMovers + (wave - kWalkers);
-#ifndef SAF_BRICK_NOROWS
               if (i * kRPI * kMovers < R && mr < R && !L.rows[cur].rowfresh[mr])
                 old[i] = ld_stream(feat + (int64_t)L.rows[cur].rown[mr] * row_vecs + (int64_t)(p + 1) * kPPR + m_pc);
-#endif
             }
           }
           BT(7);

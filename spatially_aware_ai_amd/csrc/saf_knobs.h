@@ -43,7 +43,6 @@ struct Knobs {
   bool q_split;       // SAF_Q_SPLIT: set and atoi() == 0 = the exact-fp32 MFMA scan for every shape (A-B)
   bool q_split16;     // SAF_Q_SPLIT16: set and atoi() == 0 = 16-bit volumes through the split scan's fp32 form (A-B)
   int q_threads;      // SAF_Q_THREADS: atoi() == 512 = 512 threads per workgroup, any other value = 256; unset = 0, by the tiles' size (development)
-  int wide_rows;      // SAF_WIDE_ROWS: atoi(); 64 / 33 pick geometries that only -DSAF_W2_NF2 / -DSAF_W2_TWO_WGS builds have (development)
   bool wide_mfma32;   // SAF_WIDE_MFMA: atoi() == 32 = the wide scan's 32x32x16 form, query_wide2_kernel (A-B, tests)
   bool w2_safe_wait;  // SAF_W2_SAFE_WAIT: first character '1' = the wide scan's draining wait (development)
 };
@@ -85,7 +84,6 @@ inline Knobs read_knobs() {
   k.q_split16 = nonzero("SAF_Q_SPLIT16");
   const char* th = getenv("SAF_Q_THREADS");
   k.q_threads = th ? (atoi(th) == 512 ? 512 : 256) : 0;
-  k.wide_rows = num("SAF_WIDE_ROWS", 0);
   k.wide_mfma32 = num("SAF_WIDE_MFMA", 0) == 32;
   k.w2_safe_wait = is1("SAF_W2_SAFE_WAIT");
   return k;

@@ -187,28 +187,8 @@ __device__ __forceinline__ float4 load_feat4(const void* __restrict__ base, int6
 #ifndef SAF_QM_SLOTS
 #define SAF_QM_SLOTS 2  // register groups of the row ring (one is multiplied, the others are in flight)
 #endif
-#ifndef SAF_QM_NT
-#define SAF_QM_NT 0     // 1: the rows as non-temporal loads (they are read once)
-#endif
-#ifndef SAF_QM_ABL
-#define SAF_QM_ABL 0    // development (WRONG results): 1 = no row loads (constants), 2 = no MFMAs
-#endif
 constexpr int kQGroup = SAF_QM_GROUP;  // K chunks (of 8 floats) per prefetch group: 64 floats of every row
 constexpr int kQSlots = SAF_QM_SLOTS;
-
-template <int FT>
-__device__ __forceinline__ float4 load_row4(const void* __restrict__ base, int64_t i) {  // the scan's row stream (knobs above)
-#if SAF_QM_ABL & 1
-  return make_float4((float)(i & 7), 1.0f, 0.5f, 0.25f);
-#else
-  if (SAF_QM_NT && FT == SAF_F32) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(static_cast<const float*>(base) + i));
-    return make_float4(v.x, v.y, v.z, v.w);
-  }
-  return load_feat4<FT>(base, i);
-#endif
-}
 
 // Reductions over the 32 lanes of a half without the LDS (round 6; rounds 1-5: five ds_bpermute steps each, 16 to 32 chains per
 // tile): quads, eights and sixteens by DPP inside the adds, the two 16-lane rows of the half by one v_permlane16_swap -- swapping a
@@ -499,7 +479,7 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
     for (int sl = 0; sl + 1 < kQSlots; ++sl) {
       if (sl < n_groups) {
 #pragma unroll
-        for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_row4<FT>(feats, base + 8 * (sl * kQGroup + q));
+        for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_feat4<FT>(feats, base + 8 * (sl * kQGroup + q));
       }
     }
     for (int g0 = 0; g0 < n_groups; g0 += kQSlots) {
@@ -510,7 +490,7 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
         if (g + kQSlots - 1 < n_groups) {
 #pragma unroll
           for (int q = 0; q < kQGroup; ++q)
-            ring[(sl + kQSlots - 1) % kQSlots][q] = load_row4<FT>(feats, base + 8 * ((g + kQSlots - 1) * kQGroup + q));
+            ring[(sl + kQSlots - 1) % kQSlots][q] = load_feat4<FT>(feats, base + 8 * ((g + kQSlots - 1) * kQGroup + q));
         }
 #pragma unroll
         for (int q = 0; q < kQGroup; ++q) {
@@ -520,7 +500,6 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
           ss = __builtin_fmaf(a.y, a.y, ss);
           ss = __builtin_fmaf(a.z, a.z, ss);
           ss = __builtin_fmaf(a.w, a.w, ss);
-#if !(SAF_QM_ABL & 2)
 #pragma unroll
           for (int t = 0; t < TILES; ++t) {
             const float4 b = *reinterpret_cast<const float4*>(tb + t * 32 * tstr + k0);
@@ -529,7 +508,6 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[t], 0, 0, 0);
           }
-#endif
         }
       }
     }
@@ -574,15 +552,6 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
 // Same loads, same register ring, same epilogue as the fp32 MFMA scan above (SAF_Q_SPLIT=0 selects that one).  Measured at
 // 256^3 x 512 fp32 (profiles/r06/split_scan_ab.txt): L = 63 surgery 10.95 -> 7.6 ms (round 5: 12.2), L = 5 softmax 6.9 -> 5.9 (reductions without the LDS).
 // ------------------------------------------------------------------------------------------
-#ifndef SAF_QS_ABL
-#define SAF_QS_ABL 0
-#endif
-#ifndef SAF_QS_STAGE
-#define SAF_QS_STAGE 1  // 0: the score matrix stored a row's 32 columns at a time (A/B)
-#endif
-#ifndef SAF_QS_CHAIN
-#define SAF_QS_CHAIN 1  // 0: a fresh ring per tile, the next group's loads behind a condition (rounds 1-6: every wait a vmcnt(0..7))
-#endif
 typedef _Float16 h8x __attribute__((ext_vector_type(8)));
 typedef _Float16 h2x __attribute__((ext_vector_type(2)));
 
@@ -645,7 +614,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
   // why three slots, or four, never changed anything).  Where a row is a whole number of PAIRS of groups (feat_dim a multiple of
   // 128) the two slots are loaded by unconditional code -- behind a tile's last group comes the wave's NEXT tile's first (behind
   // the last tile: a row nobody uses) -- and the waits count 8 younger loads: vmcnt(15) .. vmcnt(8).
-  const bool chain = SAF_QS_CHAIN && kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
+  const bool chain = kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
   const int64_t tile0 = (int64_t)blockIdx.x * (TH / 64) + wave, tile_step = (int64_t)gridDim.x * (TH / 64);
   auto row_base = [&](int64_t tile) {
     int64_t row = tile * 32 + m;
@@ -658,7 +627,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
 #pragma unroll
     for (int sl = 0; sl + 1 < kQSlots; ++sl)
 #pragma unroll
-      for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_row4<FT>(feats, base + 8 * (sl * kQGroup + q));
+      for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_feat4<FT>(feats, base + 8 * (sl * kQGroup + q));
   }
   for (int64_t tile = tile0; tile < n_tiles; tile += tile_step) {
     const int64_t base = row_base(tile);
@@ -699,30 +668,19 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
       ss = __builtin_fmaf(a1.z, a1.z, ss);
       ss = __builtin_fmaf(a1.w, a1.w, ss);
       uint4 hi, lo;
-#if SAF_QS_ABL & 2  // (development, WRONG results: the features' bits as they are)
-      hi = make_uint4(__builtin_bit_cast(uint32_t, a0.x), __builtin_bit_cast(uint32_t, a0.y), __builtin_bit_cast(uint32_t, a0.z), __builtin_bit_cast(uint32_t, a0.w));
-      lo = make_uint4(__builtin_bit_cast(uint32_t, a1.x), __builtin_bit_cast(uint32_t, a1.y), __builtin_bit_cast(uint32_t, a1.z), __builtin_bit_cast(uint32_t, a1.w));
-#else
       split2(ldexpf(a0.x, re), ldexpf(a0.y, re), hi.x, lo.x);
       split2(ldexpf(a0.z, re), ldexpf(a0.w, re), hi.y, lo.y);
       split2(ldexpf(a1.x, re), ldexpf(a1.y, re), hi.z, lo.z);
       split2(ldexpf(a1.z, re), ldexpf(a1.w, re), hi.w, lo.w);
-#endif
       const h8x ah = __builtin_bit_cast(h8x, hi), al = __builtin_bit_cast(h8x, lo);
 #pragma unroll
       for (int t = 0; t < TILES; ++t) {
         const uint4* bp = reinterpret_cast<const uint4*>(tb + (size_t)t * 32 * rs_bytes + p * 64);
         const uint4 bc[2] = {bp[0], bp[1]};
         const h8x bh = __builtin_bit_cast(h8x, bc[0]), bl = __builtin_bit_cast(h8x, bc[1]);
-#if SAF_QS_ABL & 1  // (development, WRONG results: no MFMAs, the pieces kept alive by four integer operations)
-        acc[t][0] += __builtin_bit_cast(float, (hi.x ^ lo.y ^ bc[0].x) & 0x3fffffffu);
-        acc[t][1] += __builtin_bit_cast(float, (hi.z ^ lo.w ^ bc[1].x) & 0x3fffffffu);
-        acc[t][2] += __builtin_bit_cast(float, (hi.y ^ lo.x ^ hi.w ^ lo.z) & 0x3fffffffu);
-#else
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
-#endif
       }
     };
     auto multiply = [&](const float4 (&grp)[kQGroup], int g) {  // one group of a row: its scale, then its k-steps
@@ -739,11 +697,11 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
     if (chain) {
       for (int g = 0; g < n_groups; g += 2) {
 #pragma unroll
-        for (int q = 0; q < kQGroup; ++q) ring[1 % kQSlots][q] = load_row4<FT>(feats, base + 8 * ((g + 1) * kQGroup + q));
+        for (int q = 0; q < kQGroup; ++q) ring[1 % kQSlots][q] = load_feat4<FT>(feats, base + 8 * ((g + 1) * kQGroup + q));
         multiply(ring[0], g);
         const int64_t from = g + 2 < n_groups ? base + 8 * ((g + 2) * kQGroup) : base_next;
 #pragma unroll
-        for (int q = 0; q < kQGroup; ++q) ring[0][q] = load_row4<FT>(feats, from + 8 * q);
+        for (int q = 0; q < kQGroup; ++q) ring[0][q] = load_feat4<FT>(feats, from + 8 * q);
         multiply(ring[1 % kQSlots], g + 1);
       }
     } else {
@@ -751,7 +709,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
       for (int sl = 0; sl + 1 < kQSlots; ++sl) {
         if (sl < n_groups) {
 #pragma unroll
-          for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_row4<FT>(feats, base + 8 * (sl * kQGroup + q));
+          for (int q = 0; q < kQGroup; ++q) ring[sl][q] = load_feat4<FT>(feats, base + 8 * (sl * kQGroup + q));
         }
       }
       for (int g0 = 0; g0 < n_groups; g0 += kQSlots) {
@@ -762,7 +720,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
           const int gl = g + kQSlots - 1;
           if (gl < n_groups) {
 #pragma unroll
-            for (int q = 0; q < kQGroup; ++q) ring[(sl + kQSlots - 1) % kQSlots][q] = load_row4<FT>(feats, base + 8 * (gl * kQGroup + q));
+            for (int q = 0; q < kQGroup; ++q) ring[(sl + kQSlots - 1) % kQSlots][q] = load_feat4<FT>(feats, base + 8 * (gl * kQGroup + q));
           }
           multiply(ring[sl], g);
         }
@@ -833,7 +791,7 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
   const unsigned char* tb = s_split + (size_t)m * rs_bytes + h * 32;
   const uint16_t* f16 = static_cast<const uint16_t*>(feats);
   typedef unsigned int q16_u4 __attribute__((ext_vector_type(4)));
-  const bool chain = SAF_QS_CHAIN && kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
+  const bool chain = kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
   const int64_t tile0 = (int64_t)blockIdx.x * (TH / 64) + wave, tile_step = (int64_t)gridDim.x * (TH / 64);
   q16_u4 ring[kQSlots][kQGroup16];
   if (chain && tile0 < n_tiles) {
@@ -996,7 +954,7 @@ int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, co
   if (blocks < 1) blocks = 1;
   // the split scan's staged stores: a whole [N, L] matrix on a 16-byte boundary, and 8 x 32 TILES floats of LDS per wave to spare
   const size_t stage_bytes = (size_t)kWavesTh * TILES * 256 * sizeof(float);
-  const bool stage = SPLIT && SAF_QS_STAGE && out && (out_stride <= 0 || out_stride == L) && out_col0 == 0 && ((uintptr_t)out & 15) == 0 &&
+  const bool stage = SPLIT && out && (out_stride <= 0 || out_stride == L) && out_col0 == 0 && ((uintptr_t)out & 15) == 0 &&
                      shmem + stage_bytes <= 159 * 1024 && (160 * 1024) / (shmem + stage_bytes + 256) >= (size_t)(per_cu < 1 ? 1 : per_cu);
   if (stage) shmem += stage_bytes;
   if (shmem > 64 * 1024) {

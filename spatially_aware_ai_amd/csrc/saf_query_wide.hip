@@ -267,9 +267,6 @@ __device__ __forceinline__ uint4 ld_stream_u4(const uint16_t* p) {  // the volum
 // whole L2 latency of the next tile at the start of every step: the "3.3 ms of LDS-DMA" of DESIGN 4.4).  The ordering is
 // this file's own: a counted `s_waitcnt vmcnt` ahead of the barrier behind which the tile is read (w2_wait_vm).  An
 // operation the compiler's counter does not know about only makes its own waits longer, never shorter.
-#ifndef SAF_W2_ASMDMA
-#define SAF_W2_ASMDMA 1
-#endif
 // K consecutive text rows (1 KiB each: D = 512) from sbase (wave-uniform: SGPRs) + the lane's 16 bytes into K consecutive padded
 // LDS rows (ROWB bytes apart) from the wave-uniform byte address lds_addr.  One statement: M0 and the lane offset step from
 // piece to piece (a VALU instruction sits between every write of M0 and the transfer that reads it).
@@ -277,7 +274,6 @@ __device__ __forceinline__ uint4 ld_stream_u4(const uint16_t* p) {  // the volum
 template <int K, int ROWB>
 __device__ __forceinline__ void w2_dma_rows(const uint16_t* sbase, uint32_t lane16, uint32_t lds_addr) {
   static_assert(K == 4 || K == 8, "pieces per wave and tile");
-#if SAF_W2_ASMDMA
   uint32_t m0_saved, voff;  // (M0 is the compiler's: handed back as found)
   if (K == 4)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\tv_mov_b32 %1, %2\n\tglobal_load_lds_dwordx4 %1, %3\n\t" SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT
@@ -287,12 +283,6 @@ __device__ __forceinline__ void w2_dma_rows(const uint16_t* sbase, uint32_t lane
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\tv_mov_b32 %1, %2\n\tglobal_load_lds_dwordx4 %1, %3\n\t" SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT
                  SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT SAF_W2_DMA_NEXT "s_nop 0\n\ts_mov_b32 m0, %0"
                  : "=&s"(m0_saved), "=&v"(voff) : "v"(lane16), "s"(sbase), "s"(lds_addr), "n"(ROWB) : "memory", "scc");
-#else
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(sbase) + lane16 + k * 1024),
-                                     (__attribute__((address_space(3))) void*)(uintptr_t)(lds_addr + k * ROWB), 16, 0, 0);
-#endif
 }
 // One piece with a per-lane byte offset from a wave-uniform base (the next row block's rows: see query_wide3_kernel).
 __device__ __forceinline__ void w3_dma_piece(const uint16_t* sbase, uint32_t lane_off, uint32_t lds_addr) {
@@ -330,15 +320,6 @@ __device__ __forceinline__ uint2 pack4_16(float v0, float v1, float v2, float v3
   a.x = (_Float16)v0; a.y = (_Float16)v1; b.x = (_Float16)v2; b.y = (_Float16)v3;
   return make_uint2(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b));
 }
-
-// Development (-DSAF_W2_STAMP): s_memtime stamps around the segments of a step, summed per wave of workgroup 0 and read
-// back by saf_debug_w2_stamps (tools/w2_stamps.py).  Costs about a tenth of the kernel's time.
-#ifdef SAF_W2_STAMP
-__device__ unsigned long long g_w2_stamp[8 * 8];
-#define W2_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); seg[k] += t_ - t_last; t_last = t_; } while (0)
-#else
-#define W2_STAMP(k) do { } while (0)
-#endif
 
 struct Wide2Args {
   const uint16_t* feats;
@@ -624,14 +605,9 @@ query_wide2_kernel(Wide2Args wa) {
   // depend on what follows) -> the MFMAs, each group consuming one fragment and requesting the one AHEAD steps ahead.
   int qt_run = 0;
   int64_t blk_run = blockIdx.x;
-#ifdef SAF_W2_STAMP
-  unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t_last = __builtin_amdgcn_s_memtime();
-#endif
   auto step_body = [&](int64_t step, f32x16_t (&c)[NF], const f32x16_t (&pc)[NF]) {
-    const int qt = qt_run;  // step % n_qt, kept incrementally (the 64-bit division cost ~250 cycles of every step: tools/w2_stamps.py)
+    const int qt = qt_run;  // step % n_qt, kept incrementally (the 64-bit division cost ~250 cycles of every step: profiles/r04/wide_scan_step_stamps.txt)
     qt_run = qt + 1 < n_qt ? qt + 1 : 0;
-    W2_STAMP(0);  // the tail of the step before: last epilogue pieces, loop control
     if (qt == 0) {
       // A new row block: its rows per wave, register resident for every query tile.  A 32-row fragment per wave-load
       // touches 32 rows x 32 bytes (each lane holds 16 bytes of its OWN row: the MFMA operand layout), and nothing runs
@@ -688,22 +664,15 @@ query_wide2_kernel(Wide2Args wa) {
       cur.bad = kReduce && __any(bad);
     }
     cur.qt = qt;
-    if (qt == 0) W2_STAMP(1);  // a new block's rows: issue, norms (the waits for the data are in the first tile's MFMAs)
     const unsigned char* curb = s_tiles + (size_t)(step & 1) * kWTile * ROWB;
     unsigned char* nxt = s_tiles + (size_t)((step + 1) & 1) * kWTile * ROWB;
     // This tile's text is in LDS (its transfer was issued a step ago) and every wave is done reading the other buffer.
     // The wait is COUNTED: the wave's `tail_ops` youngest vector-memory operations are the previous tile's last stores (or
     // its atomic), issued behind the transfer -- they need not have landed (vmcnt retires in issue order).
-#if SAF_W2_ASMDMA
     // (the count is this file's claim about what the compiler emits behind the transfer: SAF_W2_SAFE_WAIT=1 drains instead,
     //  and tests/test_gpu_parity.py::test_wide_scan_counted_wait_equals_the_draining_wait compares the two bit for bit)
     w2_wait_vm(kDma && !wa.safe_wait ? tail_ops : 0);
-#else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    W2_STAMP(7);  // the wait for this wave's pieces of the tile
     __syncthreads();
-    W2_STAMP(2);  // the barrier  // the wait for the tile and the barrier
     const bool more = step + 1 < n_steps;
     const int qt_next = qt + 1 < n_qt ? qt + 1 : 0;
     typedef unsigned int w2_u4 __attribute__((ext_vector_type(4)));  // (a native vector: HIP's uint4 -- a struct around a union -- stayed in scratch memory here)
@@ -731,7 +700,6 @@ query_wide2_kernel(Wide2Args wa) {
         }
       }
     }
-    W2_STAMP(3);  // the issue of the next tile's transfer
 #ifndef SAF_W2_AHEAD
 #define SAF_W2_AHEAD 6  // text fragments requested ahead of the MFMA that consumes them.  8 spilled 5-18 registers in the NF = 1, D = 512 instantiations (scratch traffic inside the tile loop: VERDICT round 3); 6: none
 #endif
@@ -752,9 +720,6 @@ query_wide2_kernel(Wide2Args wa) {
     if (EPI == SAF_QW_ROW_ARGMAX) fast = fast && prev.qt > 0 && prev.qt < n_qt - 1;  // first / last tile: reset / write-out
     if (EPI == SAF_QW_QUERY_MAX) fast = fast && (prev.qt + 1) * kWTile <= wa.Q;
     if (kReduce) fast = fast && !prev.bad;
-#ifdef SAF_W2_NO_FAST
-    fast = false;
-#endif
     const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     constexpr bool kSwap = EPI == SAF_QW_QUERY_MAX;
     if (!fast) {
@@ -858,7 +823,6 @@ query_wide2_kernel(Wide2Args wa) {
       for (int f = 0; f < NF; ++f)
         if (h == 0) s_inv[32 * f + r] = cur.inv[f];  // (read back by this wave only: the LDS keeps a wave's accesses in order)
     }
-    if (qt == 0) W2_STAMP(4); else W2_STAMP(5);  // the tile: LDS reads, MFMAs, the previous tile's epilogue (4: first tile of a block, waits for its rows)
     if (more && !kDma) {
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {
@@ -883,12 +847,6 @@ query_wide2_kernel(Wide2Args wa) {
   } else {
     w2_epilogue<OT, EPI, NF>(wa, acc[1], prev, st, r, h, n_qt, vec_ok);
   }
-#ifdef SAF_W2_STAMP
-  if (blockIdx.x == 0 && lane == 0 && wave < 8) {
-    seg[6] = (unsigned long long)n_steps;
-    for (int k = 0; k < 8; ++k) g_w2_stamp[wave * 8 + k] = seg[k];
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -918,9 +876,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
                        // 2 (round 6, later): the low half held in four registers for one tile, the two halves stored back to back (heat maps and raw
                        // scores; no LDS, no extra instruction).  The counters say pairing removes the amplification (34.2 GB written); the clock
                        // says nobody was waiting for it: 21.0-21.2 -> 21.6 ms, raw scores 19.3 -> 19.7-19.9 (same file).  Not kept either.
-#endif
-#ifndef SAF_W3_PREFETCH
-#define SAF_W3_PREFETCH 1  // the next row block's first pieces through the LDS (query_wide3_kernel, kPref); 0: every row from HBM at the block change
 #endif
 
 template <int FT>
@@ -1275,16 +1230,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int qt_run = 0;
   int64_t blk_run = blockIdx.x;
   // The block change is the scan's largest idle stretch: every wave replaces its 32 KiB of rows at once, a CU pulls HBM at 20-25 GB/s
-  // (profiles/r05/gather_probe_movers.log), nothing computes meanwhile -- 2.9 of 15.4 ms (SAF_W3_NO_RELOAD).  The registers have no
+  // (profiles/r05/gather_probe_movers.log), nothing computes meanwhile -- 2.9 of 15.4 ms (a build that loaded only the first block's rows).  The registers have no
   // room for a second set, but the LDS has 93 KiB beside the two text tiles: kPref of a wave's 32 one-KiB pieces (piece p = row block
   // p / S, k-step p % S: exactly register a[p / S][p % S] of every lane, lane-linear) of the NEXT block travel there by LDS-DMA while
   // this block computes -- one piece per step, issued last in the step so that it is the step's youngest vector-memory operation and
   // the counted wait in front of the next barrier lets it fly -- and the block change reads them back with ds_read_b128.
   // Measured, one box, ms with / without (profiles/r05/wide_scan_prefetch_ab.txt): best voxel per query 16.9 / 17.45, raw scores
-  // 20.05 / 20.65 -- a third of the pieces, a sixth of what SAF_W3_NO_RELOAD suggests the block change costs (that ablation also feeds
+  // 20.05 / 20.65 -- a third of the pieces, a sixth of what that build suggests the block change costs (that ablation also feeds
   // the matrix pipes constant operands, which raises the clock) --; row argmax 15.8 / 15.85 (its block change already overlaps the
   // last tile's write-out), heat maps 21.8 / 21.7: those two keep loading every row at the block change.
-  constexpr int kPref = (kDma && SAF_W3_PREFETCH && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 11 : 0;
+  constexpr int kPref = (kDma && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 11 : 0;
   constexpr uint32_t kPrefOff = 2 * kWTile * ROWB + 1024;  // behind the tiles and QUERY_MAX's 1 KiB of 1/norms
   int pref_cnt = 0;       // pieces of the next block issued so far (wave-uniform)
   bool pref_ok = false;   // the next block exists and all 32 rows of this wave's part of it do
@@ -1295,17 +1250,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto step_body = [&](int64_t step, f32x4_t (&cacc)[2][2], const f32x4_t (&pacc)[2][2]) __attribute__((always_inline)) {
     const int qt = qt_run;
     qt_run = qt + 1 < n_qt ? qt + 1 : 0;
-#ifdef SAF_W3_NO_RELOAD  // (development: only the first block's rows are loaded -- wrong results, the scan without its block-change bubble)
-    if (qt == 0 && step > 0) {
-      const int64_t blk = blk_run;
-      blk_run += gridDim.x;
-      const int64_t row0 = (blk * kWaves + wave) * kRows;
-      cur.row[0] = row0 + c; cur.row[1] = row0 + 16 + c;
-    }
-    if (qt == 0 && step == 0) {
-#else
     if (qt == 0) {  // a new row block: its rows per wave, register resident for every query tile
-#endif
       const int64_t blk = blk_run;
       blk_run += gridDim.x;
       const int64_t row0 = (blk * kWaves + wave) * kRows;
@@ -1371,11 +1316,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     cur.qt = qt;
     const unsigned char* curb = s_tiles + (size_t)(step & 1) * kWTile * ROWB;
     unsigned char* nxt = s_tiles + (size_t)((step + 1) & 1) * kWTile * ROWB;
-#if SAF_W2_ASMDMA
     w2_wait_vm(kDma && !wa.safe_wait ? tail_ops : 0);
-#else
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     __syncthreads();  // this tile's text is in LDS, every wave is done reading the other buffer
     const bool more = step + 1 < n_steps;
     const int qt_next = qt + 1 < n_qt ? qt + 1 : 0;
@@ -1414,9 +1355,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (EPI == SAF_QW_ROW_ARGMAX) fast = fast && prev.qt > 0 && prev.qt < n_qt - 1;  // first / last tile: reset / write-out
     if (EPI == SAF_QW_QUERY_MAX) fast = fast && (prev.qt + 1) * kWTile <= wa.Q;
     if (kReduce) fast = fast && !prev.bad;
-#ifdef SAF_W3_NO_FAST
-    fast = false;
-#endif
     if (kPair) {
       // low half (an even output tile): staged only -- if the NEXT tile's epilogue takes this path too (same block, a whole tile,
       // and not the workgroup's very last one, whose epilogue runs behind the loop); high half: completes what was staged
@@ -1430,9 +1368,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
     if (!fast) {
-#ifndef SAF_W3_NO_EPI  // (development: the scan without its epilogues -- wrong results, the matrix core's time)
       if (step > 0) w3_epilogue<OT, EPI>(wa, pacc, prev, st, c, g, n_qt, vec_ok);
-#endif
 #pragma unroll
       for (int m = 0; m < KS; ++m) {
         const int s = m >> 1, qb = m & 1;
@@ -1451,21 +1387,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int rb = 0; rb < 2; ++rb)
           cacc[rb][qb] = kSwap ? mfma32<FT>(a[rb][s], t[m], s == 0 ? zero4 : cacc[rb][qb]) : mfma32<FT>(t[m], a[rb][s], s == 0 ? zero4 : cacc[rb][qb]);
         if (m + AHEAD < KS) t[m + AHEAD] = *reinterpret_cast<const uint4*>(trow + SAF_W3_TOFF(m + AHEAD));
-#ifndef SAF_W3_NO_EPI
 #pragma unroll
         for (int k = (m * 16) / KS; k < ((m + 1) * 16) / KS; ++k) w3_piece<OT, EPI>(k, wa, pacc, prev, st, fs, c, g);
-#endif
         __builtin_amdgcn_sched_barrier(0);  // keep the pieces where they are: between the MFMAs
       }
       // what this step issued behind its transfer, at the very least: a store per row block (two for fp32) or the tile's atomic
       // -- every one of them by all lanes of a group that always exists
-#ifndef SAF_W3_NO_EPI
       tail_ops = EPI == SAF_QW_ROW_ARGMAX ? 0 : EPI == SAF_QW_QUERY_MAX ? 1 : (OT == SAF_F32 ? 4 : 2);
       if (kPair && st.pair == 1) tail_ops = 0;  // (staged: no store this step; a completed pair: four)
       if (kPair && st.pair == 2) tail_ops = 4;
-#else
-      tail_ops = 0;
-#endif
     }
     if (kPref && pref_ok && qt >= 1 && pref_cnt < kPref) {
       // one piece of the next block's rows, the step's youngest operation (see kPref)
@@ -1578,7 +1508,7 @@ template <int FT, int OT, int KS, int EPI>
 int launch_wide3(const Wide2Args& wa, hipStream_t s) {
   // two text tiles, 1 KiB of 1/norms (QUERY_MAX), and at D = 512 eleven 1 KiB pieces per wave of the next block's rows (kPref)
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16) + 1024 +
-                           ((KS == 32 && SAF_W3_PREFETCH && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 8 * 11 * 1024 : 0) +
+                           ((KS == 32 && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 8 * 11 * 1024 : 0) +
                            ((SAF_W3_PAIR == 1 && EPI == SAF_QW_VS_BACKGROUND && OT != SAF_F32) ? 8 * 4096 : 0);
   auto fn = query_wide3_kernel<FT, OT, KS, EPI>;
   if (shmem > 64 * 1024) {
@@ -1593,25 +1523,14 @@ int launch_wide3(const Wide2Args& wa, hipStream_t s) {
   return check_launch("query_wide3_kernel");
 }
 
-// The shipped geometry is 32 rows per wave, 8 waves per workgroup.  Development builds: -DSAF_W2_NF2 adds the 64-row instantiations
-// (SAF_WIDE_ROWS=64 in the environment picks them; the fp32-out heat maps among them spill ten registers), -DSAF_W2_TWO_WGS two
-// workgroups of four waves per CU (SAF_WIDE_ROWS=33).
 template <int FT, int OT, int KS, int EPI>
 int launch_wide2(const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
-  const int rows_env = kn.wide_rows;  // (SAF_WIDE_ROWS)
-  (void)rows_env;
   // The scan runs on v_mfma_f32_16x16x32 (query_wide3_kernel: 4-9 % faster than the 32x32x16 form at the same tile per wave, the
   // chip holds a higher clock on it); SAF_WIDE_MFMA=32 selects query_wide2_kernel.
   if (!kn.wide_mfma32) return launch_wide3<FT, OT, KS, EPI>(wa, s);
-#ifdef SAF_W2_NF2
-  if (rows_env == 64) return launch_wide2_nf<FT, OT, KS, EPI, 2, 256>(wa, s);
-#endif
-#ifdef SAF_W2_TWO_WGS
-  if (rows_env == 33) return launch_wide2_nf<FT, OT, KS, EPI, 1, 256>(wa, s);  // two workgroups of 4 waves per CU
-#endif
-  // measured at config 5 (ms, 32 vs 64 rows per wave): heat maps 27.5 / 31.4, best query per voxel 19.3 / 20.4, raw scores
-  // 25.7 / 27.8 (rounds 2-3: the best voxel per query ran at 64 -- its reduction over the lanes of a wave was per tile; with the
-  // operands swapped there is none)
+  // 32 rows per wave, 8 waves per workgroup.  Measured at config 5 (ms, 32 vs 64 rows per wave): heat maps 27.5 / 31.4, best query
+  // per voxel 19.3 / 20.4, raw scores 25.7 / 27.8 (the fp32-out heat maps at 64 spill ten registers); two workgroups of four waves
+  // per CU were slower too (see query_wide2_kernel's row-block comment)
   return launch_wide2_nf<FT, OT, KS, EPI, 1, 512>(wa, s);
 }
 
@@ -1798,11 +1717,5 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
   }
   return SAF_OK;
 }
-
-#ifdef SAF_W2_STAMP
-int saf_debug_w2_stamps(unsigned long long* host_out) {  // [8 waves][8]: cycles per segment, [6] = steps
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(saf::g_w2_stamp), sizeof(unsigned long long) * 64) == hipSuccess ? SAF_OK : SAF_E_HIP;
-}
-#endif
 
 }  // extern "C"

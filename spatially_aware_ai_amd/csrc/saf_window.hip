@@ -58,9 +58,9 @@ struct ClsArgs {
   int n, H, W;  // frames of this launch (<= kClsFrames), image size
   int slot;     // index of the launch's first frame within the window (0, 32, 64, 96)
   int count;    // 1: this launch counts its frames in stats[2] (a window classified slab by slab counts them once)
-  float guard_x, guard_y;  // SAF_CLS_GUARD: W * 2^-20, H * 2^-20 (2: always the reference's chain -- images wider than 8192)
+  float guard_x, guard_y;  // the guarded pixel path's band: W * 2^-20, H * 2^-20 (2: always the reference's chain -- images wider than 8192)
   float mid_x, mid_y;      // (W - 1) / 2, (H - 1) / 2
-  unsigned long long* verify;  // SAF_CLS_GUARD = 2 (development): disagreements of the two paths are counted here
+  unsigned long long* verify;  // SAF_CLS_VERIFY=1: disagreements of the two pixel paths are counted here
   int tiles_x8;     // TILED instantiations: tiles per image row of the frames' tiled depth copies
   int depth_bytes;  // bytes of one depth image as the launch reads it (the padded tiled copy, or H * W * 4)
   const float* depth[kClsFrames];
@@ -127,47 +127,18 @@ __device__ unsigned long long g_win_t[16];
 #define WT_FLUSH
 #endif
 
-#ifndef SAF_WIN_MAPS16_BUILD
-#define SAF_WIN_MAPS16_BUILD 1  // bf16 volumes, order-free form: bf16 map images (0: f32 images, the A/B)
-#endif
 #ifndef SAF_WIN_P2
 #define SAF_WIN_P2 2  // tap groups in flight: 2 -> 133 VGPRs, so that two row-kernel waves leave room for classification waves on a SIMD (alone, 2 / 3 / 4 / 6 time the same)
 #endif
 #ifndef SAF_CLS_WPE
 #define SAF_CLS_WPE 5  // classify_bricks_kernel: waves per SIMD the register budget is set for (78 VGPRs, no spills)
 #endif
-#ifndef SAF_CLS_OCCL
-#define SAF_CLS_OCCL 1  // the occlusion cull of the classification (depth tile maxima); 0: the frame-wide largest depth only
-#endif
-#ifndef SAF_CLS_BUFLD
-#define SAF_CLS_BUFLD 1  // depth gathers through a buffer descriptor of the frame's image (0: 64-bit addresses)
-#endif
-#ifndef SAF_CLS_GUARD
-#define SAF_CLS_GUARD 1  // the voxel's pixel from the quotients themselves wherever no lane is near a rounding boundary (0: always the reference's chain; 2: both, disagreements counted)
+#ifndef SAF_CLS_FU
+#define SAF_CLS_FU 1   // frames classified together: with the frame cull, occupancy hides the depth gathers better than batching does (1: 1.13 ms, 2: 1.17, 4: 1.29, 8: 2.08 per launch)
 #endif
 #ifndef SAF_CLS_GUARD_EPS
 #define SAF_CLS_GUARD_EPS 0x1p-20f  // the guard band per pixel of image width / height (the chain's error bound is 11.1 * 2^-24 = 0.69 of it)
 #endif
-#ifndef SAF_CLS_BOX
-#define SAF_CLS_BOX 1  // the brick's frame cull tests the box's extents (0: its bounding sphere, rounds 2-3)
-#endif
-#ifndef SAF_CLS_SKIPDEAD
-#define SAF_CLS_SKIPDEAD 0  // 1: depth gathers of voxel slots without a single pixel in the wave are not issued.  Measured SLOWER (round 6, same box,
-                            // profiles/r06/classification_skipdead_ab.txt: job 75.26 -> 75.7 ms, config 3 69.5 -> 70.0): the ballot and branch per slot cost
-                            // the vector-bound kernel more than the skipped requests save the texture-address path
-#endif
-#ifndef SAF_CLS_FU
-#define SAF_CLS_FU 1   // frames classified together: with the frame cull, occupancy hides the depth gathers better than batching does (1: 1.13 ms, 2: 1.17, 4: 1.29, 8: 2.08 per launch)
-#endif
-#ifndef SAF_CLS_CUBE
-#define SAF_CLS_CUBE 0  // 1: voxel j of a lane lies in the brick's j-th 4 x 4 x 4 cube (z = 4 j + lane / 16), so that the 64 depth gathers of one
-                        // instruction land in a cube's pixel footprint instead of the whole 16-voxel column's.  Measured (round 5,
-                        // profiles/r05/classification_variants.txt): no difference, 76.4 vs 76.6 ms per job -- a lane keeps 4 consecutive z
-#endif
-#ifndef SAF_CLS_ABL
-#define SAF_CLS_ABL 0  // development (same results): 1 = every depth gather issued twice (the second one's pixel mirrored in its row):
-#endif                 // doubles the classification's load on the texture-address unit and nothing else; 2 = the projection's vector
-                       // arithmetic twice, no memory request (profiles/r05/classification_variants.txt)
 #ifndef SAF_WIN_SPLIT_LOG2
 #define SAF_WIN_SPLIT_LOG2 2  // a piece is handed out in 2^k parts (quarters measured best: halves 6967, quarters 7165, eighths 6049 frames/s on the coherent scene)
 #endif
@@ -185,12 +156,6 @@ __device__ unsigned long long g_win_t[16];
 #ifndef SAF_WIN_OF_P2
 #define SAF_WIN_OF_P2 2
 #endif
-#ifndef SAF_WIN_LABEL_RUNS
-#define SAF_WIN_LABEL_RUNS 1  // label histogram: one add per run of equal classes of a voxel's hits (0: one atomic per hit, rounds 1-4)
-#endif
-#ifndef SAF_WIN_ABL
-#define SAF_WIN_ABL 0  // development: ablations of the order-free kernel (WRONG results): 1 taps "outside" (instructions issue, no
-#endif                 // request), 2 no tap instructions, 4 no row loads, 8 no row stores, 16 no multiply-adds
 #ifndef SAF_WIN_OF_LDPOL
 #define SAF_WIN_OF_LDPOL 2  // cache policy of the order-free kernel's row loads / stores (aux bits of the buffer instructions: 2 = nt)
 #endif
@@ -265,8 +230,7 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
                                                 unsigned long long& tsdf_rows_done) {
   float told[4];
   int tw[4];
-  constexpr uint32_t kZS = SAF_CLS_CUBE ? 4u : 1u;  // flat-index distance of a lane's voxels j and j + 1
-  const bool vec = kZS == 1u && tsdf_aligned && inb[3] && (nb & 3u) == 0u;
+  const bool vec = tsdf_aligned && inb[3] && (nb & 3u) == 0u;
   if (vec) {
     const float4 t4 = *reinterpret_cast<const float4*>(v.tsdf + nb);
     const int4 w4 = *reinterpret_cast<const int4*>(v.tsdf_w + nb);
@@ -275,8 +239,8 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      told[j] = inb[j] ? v.tsdf[nb + kZS * j] : 0.0f;
-      tw[j] = inb[j] ? v.tsdf_w[nb + kZS * j] : 0;
+      told[j] = inb[j] ? v.tsdf[nb + j] : 0.0f;
+      tw[j] = inb[j] ? v.tsdf_w[nb + j] : 0;
     }
   }
   uint32_t touched = 0;  // bit j: voxel j's TSDF changed
@@ -298,7 +262,6 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
       const Cam cam = s_cam[on ? fr[u] : 0];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-#if SAF_CLS_GUARD
         // The voxel's pixel without the normalise / un-normalise round trip (clipfusion.py:654-661 and grid_sample's own
         // arithmetic: +0.5, /W, *2, -1, +1, *W/2, -0.5, round): that chain returns the quotient qu = u / z to within
         // W * 11.1 * 2^-24 (every rounding of it at its largest, |qu| <= 2 W; beyond that the voxel is out of view by a margin no
@@ -307,19 +270,6 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
         // the image.  If ANY lane of the wave is closer than that (14 % of the voxel slots at 640 x 480) the whole wave takes
         // the reference's chain for this voxel ...
         const Uvz hq = project_uvz(cam, xw[j], yw[j], zw[j]);
-#if SAF_CLS_ABL & 2  // the guarded path's arithmetic a second time on a shifted point, result kept alive: twice the vector work, no memory request
-        {
-          const Uvz h2 = project_uvz(cam, xw[j] + 0.25f, yw[j] - 0.25f, zw[j] + 0.125f);
-          const float r2 = __builtin_amdgcn_rcpf(h2.z);
-          const float a2 = h2.u * r2, b2 = h2.v * r2;
-          const float c2 = __builtin_rintf(a2), d2 = __builtin_rintf(b2);
-          const bool n2 = fabsf(a2 - c2) > 0.5f - __builtin_fmaf(fabsf(a2), 0x1p-21f, wa.guard_x) ||
-                          fabsf(b2 - d2) > 0.5f - __builtin_fmaf(fabsf(b2), 0x1p-21f, wa.guard_y);
-          const bool v2 = fabsf(a2 - wa.mid_x) < cam.sfx && fabsf(b2 - wa.mid_y) < cam.sfy && (h2.z > 0.0f);
-          const int p2 = (v2 && !n2) ? (int)d2 * wa.W + (int)c2 : -2;
-          asm volatile("" ::"v"(p2));
-        }
-#endif
         // ... and, on the guarded path, without the two IEEE divisions either: au = u * rcp(z) is within |qu| * 0.75 * 2^-22 of
         // the quotient (v_rcp_f32: 1 ulp; one rounding of the product), so the band is widened by |au| * 2^-21.  (z below
         // 2^-100 -- the camera inside the voxel -- takes the reference's path: rcp overflows there.)
@@ -339,7 +289,7 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
           const bool in_view = on && inb[j] && fabsf(au - wa.mid_x) < cam.sfx && fabsf(av - wa.mid_y) < cam.sfy && (hq.z > 0.0f);
           pixel = in_view ? depth_offset<TILED>((int)ru, (int)rv, wa.W, wa.tiles_x8) : -2;
         }
-        if constexpr (VERIFY || SAF_CLS_GUARD > 1) {  // the self-check (SAF_CLS_VERIFY=1 at run time): both paths, disagreements counted in stats[7]
+        if constexpr (VERIFY) {  // the self-check (SAF_CLS_VERIFY=1 at run time): both paths, disagreements counted in stats[7]
           const Proj p = finish_from_uv(cam, hq.u / hq.z, hq.v / hq.z, hq.z);
           const bool in_view = on && inb[j] && (fabsf(p.gx) <= 1.0f) && (fabsf(p.gy) <= 1.0f) && (p.z > 0.0f);
           const int px = nearest_offset<TILED>(p.gx, p.gy, cam, wa.W, wa.tiles_x8);
@@ -348,13 +298,6 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
         }
         pix[u][j] = pixel;
         pz[u][j] = hq.z;
-        continue;
-#endif
-        const Proj p = project(cam, xw[j], yw[j], zw[j]);
-        const bool in_view = on && inb[j] && (fabsf(p.gx) <= 1.0f) && (fabsf(p.gy) <= 1.0f) && (p.z > 0.0f);
-        const int px = nearest_offset<TILED>(p.gx, p.gy, cam, wa.W, wa.tiles_x8);
-        pix[u][j] = in_view ? (px >= 0 ? px : -1) : -2;
-        pz[u][j] = p.z;
       }
     }
     float depth[kFU][4];
@@ -362,34 +305,13 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
     for (int u = 0; u < kFU; ++u) {
       // through a buffer descriptor of the frame's depth image (the frame is wave-uniform): a 32-bit offset per lane instead of
       // a 64-bit address, and "no pixel" (pix < 0: an offset beyond the image) reads 0 by the range check -- zeros padding
-#if SAF_CLS_BUFLD
       const __amdgpu_buffer_rsrc_t dimg = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<float*>(wa.depth[fr[u] >= 0 ? fr[u] : 0]), 0, wa.depth_bytes, 0x00020000);
+      // (not issuing the gathers of voxel slots without a single pixel in the wave was measured slower: the ballot and branch per
+      //  slot cost the vector-bound kernel more than the skipped requests save, profiles/r06/classification_skipdead_ab.txt)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-#if SAF_CLS_SKIPDEAD
-        // a voxel slot no lane of the wave has a pixel for (a brick at the edge of the view, z <= 0) issues no gather: an
-        // instruction whose 64 offsets all lie beyond the image makes no memory request but still takes its turn in the
-        // texture-address unit, the path the classification shares with the row kernel beside it
-        depth[u][j] = 0.0f;
-        if (__builtin_amdgcn_ballot_w64(pix[u][j] >= 0) != 0ull)
-#endif
+      for (int j = 0; j < 4; ++j)
         depth[u][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dimg, pix[u][j] * 4, 0, 0));
-      }
-#if SAF_CLS_ABL & 1
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = pix[u][j] / wa.W, col = pix[u][j] - row * wa.W;
-        const int twin = pix[u][j] >= 0 && !TILED ? row * wa.W + (wa.W - 1 - col) : pix[u][j];
-        const float d2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dimg, twin * 4, 0, 0));
-        asm volatile("" ::"v"(d2));
-      }
-#endif
-#else
-      const float* __restrict__ dimg = wa.depth[fr[u] >= 0 ? fr[u] : 0];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) depth[u][j] = pix[u][j] >= 0 ? dimg[pix[u][j]] : 0.0f;
-#endif
     }
 #pragma unroll
     for (int u = 0; u < kFU; ++u) {
@@ -424,8 +346,8 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (touched & (1u << j)) {
-          v.tsdf[nb + kZS * j] = told[j];
-          v.tsdf_w[nb + kZS * j] = tw[j];
+          v.tsdf[nb + j] = told[j];
+          v.tsdf_w[nb + j] = tw[j];
         }
       }
     }
@@ -581,9 +503,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
   const uint32_t bx = (tt / tiles_y) * 8u + r / 8u, by = (tt % tiles_y) * 8u + r % 8u;
   const bool on = bx < nbx && by < nby;  // (no early return: the workgroup meets again in cls_accumulate)
   const int ix = (int)bx * kBrickX + (lane & 3), iy = (int)by * kBrickY + ((lane >> 2) & 3);
-  // a lane's four voxels: z = iz0 + kZS j (SAF_CLS_CUBE: one per 4 x 4 x 4 cube of the brick; else four consecutive ones)
-  constexpr int kZS = SAF_CLS_CUBE ? 4 : 1;
-  const int iz0 = (int)bz * kBrickZ + (SAF_CLS_CUBE ? (lane >> 4) : (lane >> 4) * 4);
+  // a lane's four voxels: z = iz0 + j, four consecutive ones (one per 4 x 4 x 4 cube of the brick instead, so that an instruction's 64
+  // depth gathers land in a cube's pixel footprint, made no difference: 76.4 vs 76.6 ms per job, profiles/r05/classification_variants.txt)
+  const int iz0 = (int)bz * kBrickZ + (lane >> 4) * 4;
   const bool col_in = on && ix < v.nx && iy < v.ny;
   const int ixc = min(ix, v.nx - 1), iyc = min(iy, v.ny - 1);
   const uint32_t nb = ((uint32_t)ixc * (uint32_t)v.ny + (uint32_t)iyc) * (uint32_t)v.nz + (uint32_t)min(iz0, v.nz - 1);
@@ -594,8 +516,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
   for (int j = 0; j < 4; ++j) {
     xw[j] = x_l;
     yw[j] = y_l;
-    zw[j] = v.az[min(iz0 + kZS * j, v.nz - 1)];
-    inb[j] = col_in && iz0 + kZS * j < v.nz;
+    zw[j] = v.az[min(iz0 + j, v.nz - 1)];
+    inb[j] = col_in && iz0 + j < v.nz;
   }
   // ---- which frames can touch this brick at all?  lane k tests frame k
   uint32_t live;
@@ -608,7 +530,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
     const float z0 = v.az[bz0], z1 = v.az[min(bz0 + kBrickZ - 1, v.nz - 1)];
     const float cxw = 0.5f * (x0 + x1), cyw = 0.5f * (y0 + y1), czw = 0.5f * (z0 + z1);
     const float hx = 0.5f * (x1 - x0), hy = 0.5f * (y1 - y0), hz = 0.5f * (z1 - z0);
-    const float rho = sqrtf(hx * hx + hy * hy + hz * hz) * 1.02f + 1e-4f;  // voxel CENTRES are what is tested
     bool dead = false;
     int why = 0;  // what dropped the frame: 1 behind the camera, 2 beyond the frame's largest depth + trunc, 3 outside the frustum, 4 occluded
     if (lane < n_f) {
@@ -628,13 +549,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
       const bool rigid = fabsf(n0 - 1.0f) < 1e-3f && fabsf(n1 - 1.0f) < 1e-3f && fabsf(n2 - 1.0f) < 1e-3f &&
                          fabsf(d01) < 1e-3f && fabsf(d02) < 1e-3f && fabsf(d12) < 1e-3f;
       const bool z_is_depth = c.k20 == 0.0f && c.k21 == 0.0f && c.k22 == 1.0f;
-      // (SAF_CLS_BOX, round 4: the brick is 4 x 4 x 16 voxels -- its bounding sphere is four times as wide as the brick is
+      // (voxel CENTRES are what is tested.  Round 4: the brick is 4 x 4 x 16 voxels -- its bounding sphere is four times as wide as the brick is
       //  across -- so the tests use the BOX's extent along each direction instead: for a direction n in camera space the
       //  box reaches |n . ex| hx + |n . ey| hy + |n . ez| hz from its centre, ex / ey / ez = the world axes in camera space)
       const float mg = 1.02f, me = 1e-4f;
-      const float ext_x = SAF_CLS_BOX ? (fabsf(c.r00) * hx + fabsf(c.r10) * hy + fabsf(c.r20) * hz) * mg + me : rho;
-      const float ext_y = SAF_CLS_BOX ? (fabsf(c.r01) * hx + fabsf(c.r11) * hy + fabsf(c.r21) * hz) * mg + me : rho;
-      const float ext_z = SAF_CLS_BOX ? (fabsf(c.r02) * hx + fabsf(c.r12) * hy + fabsf(c.r22) * hz) * mg + me : rho;
+      const float ext_x = (fabsf(c.r00) * hx + fabsf(c.r10) * hy + fabsf(c.r20) * hz) * mg + me;
+      const float ext_y = (fabsf(c.r01) * hx + fabsf(c.r11) * hy + fabsf(c.r21) * hz) * mg + me;
+      const float ext_z = (fabsf(c.r02) * hx + fabsf(c.r12) * hy + fabsf(c.r22) * hz) * mg + me;
       dead = rigid && z_is_depth && (zc + ext_z <= 0.0f || zc - ext_z > far_z);
       why = dead ? (zc + ext_z <= 0.0f ? 1 : 2) : 0;
       if (pinhole && rigid) {
@@ -649,17 +570,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
         const float m1 = sqrtf(c.k11 * c.k11 + b1 * b1), m2 = sqrtf(c.k11 * c.k11 + b2 * b2);
         const float d1 = (c.k00 * xc + a1 * zc) / n1, d2 = (c.k00 * xc + a2 * zc) / n2;
         const float e1 = (c.k11 * yc + b1 * zc) / m1, e2 = (c.k11 * yc + b2 * zc) / m2;
-        const float rd1 = SAF_CLS_BOX ? reach(c.k00, 0.0f, a1) / n1 + me : rho, rd2 = SAF_CLS_BOX ? reach(c.k00, 0.0f, a2) / n2 + me : rho;
-        const float re1 = SAF_CLS_BOX ? reach(0.0f, c.k11, b1) / m1 + me : rho, re2 = SAF_CLS_BOX ? reach(0.0f, c.k11, b2) / m2 + me : rho;
+        const float rd1 = reach(c.k00, 0.0f, a1) / n1 + me, rd2 = reach(c.k00, 0.0f, a2) / n2 + me;
+        const float re1 = reach(0.0f, c.k11, b1) / m1 + me, re2 = reach(0.0f, c.k11, b2) / m2 + me;
         const bool fx_pos = c.k00 > 0.0f, fy_pos = c.k11 > 0.0f;  // the usual orientation; otherwise no frustum cull
         dead = dead || (fx_pos && (d1 < -rd1 || d2 > rd2)) || (fy_pos && (e1 < -re1 || e2 > re2));
         why = dead && !why ? 3 : why;
-        // ---- occlusion: the largest depth over the pixels the brick can project onto (SAF_CLS_OCCL=0 at build time: off).
+        // ---- occlusion: the largest depth over the pixels the brick can project onto.
         // A voxel's pixel is round(u), u = k00 x / z + k02 (clipfusion.py:651-661 undone: grid_sample's un-normalisation gives
-        // back the pixel coordinate); over the sphere's bounding box x in [xc - rho, xc + rho], z in [zc - rho, zc + rho] (z > 0)
+        // back the pixel coordinate); over the box's extents x in [xc - ext_x, xc + ext_x], z in [zc - ext_z, zc + ext_z] (z > 0)
         // u is monotone in x and in 1 / z: a conservative pixel rectangle, widened by a pixel, at most 16 tiles of it.
         const float zn = zc - ext_z, zf = zc + ext_z;
-        if (SAF_CLS_OCCL && !dead && z_is_depth && fx_pos && fy_pos && zn > 1e-3f && zn > dmax[kWin + lane] + v.trunc * 1.01f + 1e-4f) {
+        if (!dead && z_is_depth && fx_pos && fy_pos && zn > 1e-3f && zn > dmax[kWin + lane] + v.trunc * 1.01f + 1e-4f) {
           const float rn = 1.0f / zn, rf = 1.0f / zf;
           const float xl = xc - ext_x, xh = xc + ext_x, yl = yc - ext_y, yh = yc + ext_y;
           const float ul = c.k00 * (xl >= 0.0f ? xl * rf : xl * rn) + c.k02, uh = c.k00 * (xh >= 0.0f ? xh * rn : xh * rf) + c.k02;
@@ -699,12 +620,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
     classify_voxels<SAF_CLS_FU, SUM, VERIFY, TILED>(v, wa, s_cam, nb, xw, yw, zw, inb, rtrunc, tsdf_aligned, live, mk4, nt_done, tsdf_rows_done);
   // every voxel of the grid gets its mask word (the row kernel reads them all); 16 bytes at once where the four lie in the grid
   // and the run is aligned (always, when nz is a multiple of 4)
-  if (kZS == 1 && inb[3] && (nb & 3u) == 0u) {
+  if (inb[3] && (nb & 3u) == 0u) {
     *reinterpret_cast<uint4*>(hitmask + nb) = make_uint4(mk4[0], mk4[1], mk4[2], mk4[3]);
-  } else {  // (cube order: the four lanes of a column write 16 consecutive bytes per instruction)
+  } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (inb[j]) hitmask[nb + kZS * j] = mk4[j];
+      if (inb[j]) hitmask[nb + j] = mk4[j];
   }
   cls_accumulate(nt_done, tsdf_rows_done, cull, lane, wave, s_acc, s_cull, stats ? cls_acc : nullptr);
 }
@@ -863,7 +784,7 @@ template <int NB, int CPL, bool SUM, bool BF16, int SR, bool F16>
 __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&hl)[NB + 1], int nb, const WinGroupOffs& go,
                                              const WinHit& rec, const unsigned long long (&rm)[SR],
                                              win_v2f (&acc)[SR][2 * CPL]) {
-  if constexpr (BF16 && SAF_WIN_MAPS16_BUILD) {  // bf16 map images: one 16-byte load per tap and unit of 8 channels, widened in the FMA operands
+  if constexpr (BF16) {  // bf16 map images: one 16-byte load per tap and unit of 8 channels, widened in the FMA operands
     constexpr int UPL = CPL / 2;
     uint4 tq[NB][4][UPL];
 #pragma unroll
@@ -914,7 +835,7 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
   float4 tp[NB][4][CPL];
 #pragma unroll
   for (int u = 0; u < NB; ++u) {
-    const bool real = u < nb && !(SAF_WIN_ABL & 1);  // (hl[u] = 64 for an empty group when the pass is full: no such lane to read)
+    const bool real = u < nb;  // (hl[u] = 64 for an empty group when the pass is full: no such lane to read)
     const int hu = real ? hl[u] : 0;
     // (distinct offsets for an empty group's taps: identical loads would be merged into one)
     const int o_nw = real ? __builtin_amdgcn_readlane(go.nw, hu) : (int)(kTapOutside + 0x10000u * (4 * u));
@@ -925,11 +846,6 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       const uint32_t off = lane_off + (uint32_t)win_chunk_off<BF16>(c) * 16u;
-      if (SAF_WIN_ABL & 2) {
-        const float f = __builtin_bit_cast(float, (uint32_t)o_nw + off);
-        tp[u][0][c] = tp[u][1][c] = tp[u][2][c] = tp[u][3][c] = make_float4(f, f, f, f);
-        continue;
-      }
       tp[u][0][c] = win_tap_load(cx.maps, (uint32_t)o_nw + off);
       tp[u][1][c] = win_tap_load(cx.maps, (uint32_t)o_ne + off);
       tp[u][2][c] = win_tap_load(cx.maps, (uint32_t)o_sw + off);
@@ -951,14 +867,7 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
         const float ne = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rec.ne), l));
         const float sw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rec.sw), l));
         const float se = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rec.se), l));
-        if (SAF_WIN_ABL & 16) {
-#pragma unroll
-          for (int c = 0; c < CPL; ++c)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(tp[u][t][c].x), "v"(tp[u][t][c].y), "v"(tp[u][t][c].z), "v"(tp[u][t][c].w), "s"(nw), "s"(ne), "s"(sw), "s"(se));
-        } else {
-          of_add_row<CPL>(acc[R], tp[u], nw, ne, sw, se);
-        }
+        of_add_row<CPL>(acc[R], tp[u], nw, ne, sw, se);
       }
     }
   }
@@ -978,15 +887,9 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
   constexpr int SR = Cfg::SR;
   // (s_setprio 1 / 3 here, ahead of the classification waves that share the SIMDs, changes nothing: 105.4 / 105.7 / 105.8 ms)
   // a bf16 sub-chunk also holds its raw rows in registers until they are widened: one tap group fewer in flight
-#ifndef SAF_WIN_OF_P16
-#define SAF_WIN_OF_P16 0  // tap groups in flight with bf16 map images at D = 512 (0: as for f32 images; their registers are half as many)
-#endif
-  constexpr int P = OF ? ((BF16 && SAF_WIN_MAPS16_BUILD && CPL == 2 && SAF_WIN_OF_P16 > 0) ? SAF_WIN_OF_P16 : Cfg::P)
+  constexpr int P = OF ? Cfg::P
                        : (BF16 && Cfg::P > 2 ? Cfg::P - 1 : (BF16 && CPL == 4 ? 1 : Cfg::P));  // (bf16, D = 1024: two groups of 64 tap registers in flight spilled)
   extern __shared__ __align__(16) unsigned char s_dyn[];
-#ifdef SAF_WIN_PRIO
-  __builtin_amdgcn_s_setprio(SAF_WIN_PRIO);
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float4* rows = reinterpret_cast<float4*>(s_dyn + Cfg::rows_off) + (size_t)wave * SR * CPL * 64;
   uint32_t* stage = reinterpret_cast<uint32_t*>(s_dyn + Cfg::stage_off) + (size_t)wave * 6 * kHitCap;
@@ -1022,7 +925,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
   }
   __syncthreads();
   const int DV = v.D >> 2;
-  const int DVM = (BF16 && OF && SAF_WIN_MAPS16_BUILD) ? v.D >> 3 : v.D >> 2;  // 16-byte vectors of a MAP row (bf16 map images in the order-free form of a bf16 volume)
+  const int DVM = (BF16 && OF) ? v.D >> 3 : v.D >> 2;  // 16-byte vectors of a MAP row (bf16 map images in the order-free form of a bf16 volume)
   const float half_px = (float)wa.npx / 2.0f, half_py = (float)wa.npy / 2.0f;
   const int zero_row = wa.npx * wa.npy;
   int chs[CPL];
@@ -1189,11 +1092,8 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
           s_ha[j] = s0;
           s_hb[j] = s1;
           s_hs2[j] = s2;
-#if !SAF_WIN_LABEL_RUNS
-          count_label_lane<true>(v, kf, n, pix, stats);
-#endif
           // the hit's class (clip_seem_fusion.py:786-791: nearest sample of the panoptic map, .long())
-          if (SAF_WIN_LABEL_RUNS && v.labels && kf.label_map) {
+          if (v.labels && kf.label_map) {
             const float lraw = wa.rgbl ? lpk : kf.label_map[pix >= 0 ? pix : 0];
             const long long l = (long long)(pix >= 0 ? lraw : 0.f);
             const bool ok = l >= 0 && l < v.n_classes;
@@ -1201,7 +1101,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             if (!ok && stats) atomicAdd(&stats[3], 1ull);
           }
         }
-        if (SAF_WIN_LABEL_RUNS && v.labels && s_lab[0]) {
+        if (v.labels && s_lab[0]) {
           // Label histogram (clip_seem_fusion.py:820-822), one add per RUN: a voxel's hits lie in consecutive lanes in frame
           // order, and what a panoptic model says about a static scene is the same frame after frame -- the first lane of a
           // run of equal classes of one voxel adds the run's length (integer adds: bit for bit the per-hit histogram; a run
@@ -1346,7 +1246,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
               low[w] = (uint32_t)w < fwd ? 0xffffffffu : ((uint32_t)w == fwd ? (1u << fbit) - 1u : 0u);
 #pragma unroll
             for (int r = 0; r < SR; ++r) {
-              if (r < nrows && (__builtin_amdgcn_readlane(w0, i0 + r) == 0 || (OF && (SAF_WIN_ABL & 4)))) {
+              if (r < nrows && __builtin_amdgcn_readlane(w0, i0 + r) == 0) {
                 fresh |= 1u << r;
                 if (!BF16 && !OF) {
 #pragma unroll
@@ -1525,9 +1425,8 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                   q.z = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.z), f, a2.x) * fac, __builtin_fmaf(h16_hi<F16>(w.z), f, a2.y) * fac);
                   q.w = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.w), f, a3.x) * fac, __builtin_fmaf(h16_hi<F16>(w.w), f, a3.y) * fac);
                   raw.u[r * UPL + k] = q;
-                  if (!(SAF_WIN_ABL & 8))
-                    st_stream(featb + (row / 2) + lane + k * 64, make_float4(__builtin_bit_cast(float, q.x), __builtin_bit_cast(float, q.y),
-                                                                             __builtin_bit_cast(float, q.z), __builtin_bit_cast(float, q.w)));
+                  st_stream(featb + (row / 2) + lane + k * 64, make_float4(__builtin_bit_cast(float, q.x), __builtin_bit_cast(float, q.y),
+                                                                           __builtin_bit_cast(float, q.z), __builtin_bit_cast(float, q.w)));
                 }
               } else {
                 const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(feat + row, 0, v.D * 4, 0x00020000);
@@ -1538,10 +1437,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                     acc[r][2 * c + 1] = acc[r][2 * c + 1] * (win_v2f){fac, fac};
                   }
                   const float4 o = make_float4(acc[r][2 * c].x, acc[r][2 * c].y, acc[r][2 * c + 1].x, acc[r][2 * c + 1].y);
-                  if (SAF_WIN_ABL & 8)
-                    asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-                  else
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(win_v4u, o), rr, lane * 16 + c * 1024, 0, SAF_WIN_OF_STPOL);
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(win_v4u, o), rr, lane * 16 + c * 1024, 0, SAF_WIN_OF_STPOL);
                 }
               }
             } else if (BF16) {
@@ -1581,9 +1477,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
 // classification waves of 80 beside them, two of 177 (= 184) for one.  The order-free D = 512 kernels -- the benchmark's -- are
 // therefore capped at 176 (amdgpu_num_vgpr takes no template-dependent value: hence two wrappers around one body); the bf16 one
 // had crept to 177 in round 5, and config 3's classification beside it lost its second wave per SIMD.
-#ifndef SAF_WIN_OF_VGPRS
-#define SAF_WIN_OF_VGPRS 176
-#endif
+constexpr int kWinOfVgprs = 176;
 template <int CPL, bool SUM, bool BF16, bool OF>
 __global__ __launch_bounds__(kWinThreads)
 __attribute__((amdgpu_waves_per_eu(OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE, OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE))) void
@@ -1594,7 +1488,7 @@ fuse_window_kernel(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const f
   fuse_window_body<CPL, SUM, BF16, OF>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
 }
 template <int CPL, bool SUM, bool BF16>
-__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(SAF_WIN_OF_VGPRS))) void
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
 fuse_window_kernel_of176(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
                          unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
                          const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
@@ -1613,7 +1507,7 @@ fuse_window_kernel_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, con
                        int xcd_order) {
   fuse_window_body<CPL, false, true, OF, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
 }
-__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(SAF_WIN_OF_VGPRS))) void
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
 fuse_window_kernel_of176_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
                              unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
                              const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
@@ -1655,10 +1549,10 @@ WinFn pick_win(bool sum, int e16) {
   if (e16 == kE16Half) {
     if (CPL % 2 != 0 || sum) return nullptr;
     constexpr int C2 = CPL % 2 == 0 ? CPL : 2;
-    if (OF && CPL == 2 && SAF_WIN_OF_VGPRS > 0) return fuse_window_kernel_of176_f16;
+    if (OF && CPL == 2) return fuse_window_kernel_of176_f16;
     return fuse_window_kernel_f16<C2, OF>;
   }
-  if (OF && CPL == 2 && SAF_WIN_OF_VGPRS > 0) {  // the benchmark's kernels: within 176 registers (see fuse_window_kernel_of176)
+  if (OF && CPL == 2) {  // the benchmark's kernels: within 176 registers (see fuse_window_kernel_of176)
     if (rows16) return sum ? fuse_window_kernel_of176<2, true, true> : fuse_window_kernel_of176<2, false, true>;
     return sum ? fuse_window_kernel_of176<2, true, false> : fuse_window_kernel_of176<2, false, false>;
   }
@@ -1809,7 +1703,7 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Kn
   }
   // bf16 / fp16 volume in the order-free form: the window's map images are kept in the volume's type (what the kernel's BF16 && OF
   // instantiations read)
-  pl->maps16 = !pl->brick_form && pl->of && kv.e16 != 0 && SAF_WIN_MAPS16_BUILD;
+  pl->maps16 = !pl->brick_form && pl->of && kv.e16 != 0;
   pl->img_bytes16 = ((size_t)kv.D * (P + 1) * 2 + 255) & ~(size_t)255;
   if (pl->maps16) pl->img_vecs = (int)(pl->img_bytes16 / sizeof(float4));
   // the depth tiles of the classification's occlusion cull: 16 x 16 pixels, doubled until a frame has at most kMaxDepthTiles
