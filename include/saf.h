@@ -501,11 +501,15 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
 /*
  * After the cross-rank SUM of SAF_SUM-mode volumes: clip_feat <- F/w,
  * rgb <- C/w, tsdf <- T/wt over voxels [first, first+count); rows with zero weight stay zero.
+ * More exactly: a row with w <= 0 (wt <= 0 for the tsdf) is not touched -- it keeps its bytes, whatever they are -- and every
+ * scaled value is one IEEE fp32 division by (float)w.  Voxels outside the range are not touched.  SAF_F32 volumes only.
  */
 int saf_merge_finalize(const saf_volume* vol, int64_t first_voxel, int64_t n_voxels, void* stream);
 
 /* Inverse of the above for a volume that was fused in SAF_RUNNING_MEAN mode: mean -> sum
- * (x*w), so that it can enter the reduction. */
+ * (x*w), so that it can enter the reduction.  The product is taken in EVERY row of the range, one fp32 multiplication by
+ * (float)w: a row with w == 0 becomes x * 0 -- zero where it held finite data (by the volume's contract it held zeros), NaN where
+ * it held NaN or inf.  The round trip mean -> sum -> mean moves a value by at most one unit in the last place where w > 0. */
 int saf_mean_to_sum(const saf_volume* vol, int64_t first_voxel, int64_t n_voxels, void* stream);
 
 /*
