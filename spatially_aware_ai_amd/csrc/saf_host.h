@@ -37,4 +37,28 @@ inline int device_cus() {
   return cus;
 }
 
+// Workgroups of a grid-stride launch: one per `per_wg` items, no more than `per_cu` for each compute unit, at least one.
+inline unsigned grid_1d(int64_t items, int per_cu, int per_wg = 256) {
+  int64_t blocks = (items + per_wg - 1) / per_wg;
+  const int64_t cap = (int64_t)device_cus() * per_cu;
+  if (blocks > cap) blocks = cap;
+  return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// A volume that the field readers (saf_field_dev.h) can use: two voxels per axis for a cell, int32 voxel indices, and the tsdf,
+// its weights and the axis tables.  `also` is whatever else the entry `what` needs of the volume.
+inline int check_field_volume(const char* what, const saf_volume* vol, bool also = true) {
+  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || n_voxels(vol) > 0x7fffffff || !vol->tsdf || !vol->tsdf_weight || !vol->axis_x ||
+      !vol->axis_y || !vol->axis_z || !also)
+    return fail(SAF_E_INVALID, "%s: bad volume (%d x %d x %d voxels; at least 2 per axis, fewer than 2^31 in all)", what, (int)vol->nx,
+                (int)vol->ny, (int)vol->nz);
+  return SAF_OK;
+}
+
+// int32 pixel indices
+inline int check_pixel_count(const char* what, int height, int width) {
+  if ((int64_t)height * width > 0x7fffffff) return fail(SAF_E_INVALID, "%s: too many pixels", what);
+  return SAF_OK;
+}
+
 }  // namespace saf

@@ -115,12 +115,6 @@ size_t scan_tmp_bytes(int64_t n_rows) {
   return (b + 255) & ~(size_t)255;
 }
 
-int grid_for(int64_t n_rows) {
-  const int64_t want = (n_rows + 255) / 256;  // 64 rows per wave and step, 4 waves per workgroup
-  const int64_t cap = (int64_t)device_cus() * 16;
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
-
 }  // namespace
 }  // namespace saf
 
@@ -162,7 +156,8 @@ int saf_merge_pack_rows(const void* src, int64_t row_bytes, const int32_t* weigh
     return fail(SAF_E_INVALID, "merge_pack_rows: bad arguments");
   if (n_rows == 0) return SAF_OK;
   const int vec = row_bytes % 16 == 0 && (((uintptr_t)src | (uintptr_t)packed) & 15) == 0;
-  hipLaunchKernelGGL(pack_rows_kernel, dim3(grid_for(n_rows)), dim3(256), 0, static_cast<hipStream_t>(stream),
+  // (64 rows per wave and step, 4 waves per workgroup)
+  hipLaunchKernelGGL(pack_rows_kernel,dim3(grid_1d(n_rows, 16)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned char*>(src), row_bytes, weight, pos, first, n_rows, static_cast<unsigned char*>(packed), vec);
   return check_launch("pack_rows_kernel");
 }
@@ -175,10 +170,10 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
   const int vec = row_bytes % 16 == 0 && (((uintptr_t)dst | (uintptr_t)recv) & 15) == 0 && (mine * row_bytes) % 16 == 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (is_float)
-    hipLaunchKernelGGL((add_packed_kernel<f32x4, float>), dim3(grid_for(n_rows)), dim3(256), 0, s, static_cast<unsigned char*>(dst), row_bytes,
+    hipLaunchKernelGGL((add_packed_kernel<f32x4, float>), dim3(grid_1d(n_rows, 16)), dim3(256), 0, s, static_cast<unsigned char*>(dst), row_bytes,
                        weight, pos, first, n_rows, static_cast<const unsigned char*>(recv), mine, (int)world, vec);
   else
-    hipLaunchKernelGGL((add_packed_kernel<i32x4, int32_t>), dim3(grid_for(n_rows)), dim3(256), 0, s, static_cast<unsigned char*>(dst), row_bytes,
+    hipLaunchKernelGGL((add_packed_kernel<i32x4, int32_t>), dim3(grid_1d(n_rows, 16)), dim3(256), 0, s, static_cast<unsigned char*>(dst), row_bytes,
                        weight, pos, first, n_rows, static_cast<const unsigned char*>(recv), mine, (int)world, vec);
   return check_launch("add_packed_kernel");
 }

@@ -89,23 +89,16 @@ int scale_volume(const saf_volume* vol, int64_t first, int64_t count, hipStream_
   if (first < 0 || count < 0 || first + count > N) return fail(SAF_E_INVALID, "merge: bad voxel range");
   if (count == 0) return SAF_OK;
   const int D = vol->feat_dim;
-  const int cap = device_cus() * 8;
   float* feat = static_cast<float*>(vol->clip_feat);
-  if (D % 4 == 0 && ((uintptr_t)feat & 15) == 0) {
-    const int64_t total = count * (D / 4);
-    const int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
-    hipLaunchKernelGGL((scale_rows_kernel<TO_MEAN, 4>), dim3(blocks), dim3(256), 0, s, feat, vol->weight, first, count,
-                       D / 4);
-  } else {
-    const int64_t total = count * D;
-    const int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
-    hipLaunchKernelGGL((scale_rows_kernel<TO_MEAN, 1>), dim3(blocks), dim3(256), 0, s, feat, vol->weight, first, count,
-                       D);
-  }
+  if (D % 4 == 0 && ((uintptr_t)feat & 15) == 0)
+    hipLaunchKernelGGL((scale_rows_kernel<TO_MEAN, 4>), dim3(grid_1d(count * (D / 4), 8)), dim3(256), 0, s, feat, vol->weight, first,
+                       count, D / 4);
+  else
+    hipLaunchKernelGGL((scale_rows_kernel<TO_MEAN, 1>), dim3(grid_1d(count * D, 8)), dim3(256), 0, s, feat, vol->weight, first,
+                       count, D);
   int rc = check_launch("scale_rows_kernel");
   if (rc) return rc;
-  const int blocks = (int)((count + 255) / 256 < cap ? (count + 255) / 256 : cap);
-  hipLaunchKernelGGL(scale_scalars_kernel<TO_MEAN>, dim3(blocks), dim3(256), 0, s, vol->rgb, vol->tsdf, vol->weight,
+  hipLaunchKernelGGL(scale_scalars_kernel<TO_MEAN>, dim3(grid_1d(count, 8)), dim3(256), 0, s, vol->rgb, vol->tsdf, vol->weight,
                      vol->tsdf_weight, first, count);
   return check_launch("scale_scalars_kernel");
 }
@@ -327,14 +320,12 @@ int clear_rows(void* feat, const int* weight, int64_t first, int64_t n_rows, int
   // clear into the call is worth 0.2-0.4 ms of 42.7 there and nothing on depth A; 8 per CU was the best of 2 / 4 / 8 / 16.
   const int per_cu = kn.clear_wgs > 0 ? kn.clear_wgs : (masks ? 8 : 16);  // (SAF_CLEAR_WGS)
   if ((uintptr_t)feat & 15) return fail(SAF_E_INVALID, "clear_unwritten_rows: clip_feat must be 16-byte aligned");
-  int64_t blocks = (n_rows + 255) / 256;
-  const int64_t cap = (int64_t)device_cus() * per_cu;
-  if (blocks > cap) blocks = cap;
+  const unsigned blocks = grid_1d(n_rows, per_cu);
   if (esz == 4)
-    hipLaunchKernelGGL(clear_unwritten_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, feat, weight, first, n_rows, row_bytes, masks,
+    hipLaunchKernelGGL(clear_unwritten_kernel<4>, dim3(blocks), dim3(256), 0, s, feat, weight, first, n_rows, row_bytes, masks,
                        mask_plane, n_planes);
   else
-    hipLaunchKernelGGL(clear_unwritten_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, feat, weight, first, n_rows, row_bytes, masks,
+    hipLaunchKernelGGL(clear_unwritten_kernel<2>, dim3(blocks), dim3(256), 0, s, feat, weight, first, n_rows, row_bytes, masks,
                        mask_plane, n_planes);
   return check_launch("clear_unwritten_kernel");
 }
@@ -422,20 +413,18 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
   if (vol->feat_dtype != SAF_F32 && vol->feat_dtype != SAF_BF16 && vol->feat_dtype != SAF_F16)
     return fail(SAF_E_UNSUPPORTED, "sample_vertices: feature dtype %d", vol->feat_dtype);
   if (n_verts == 0) return SAF_OK;
-  int64_t blocks = (n_verts + 3) / 4;
-  const int64_t cap = (int64_t)device_cus() * 8;
-  if (blocks > cap) blocks = cap;
+  const unsigned blocks = grid_1d(n_verts, 8, 4);  // one wave per vertex
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (vol->feat_dtype == SAF_BF16)
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_BF16>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_BF16>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
   else if (vol->feat_dtype == SAF_F16)
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F16>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F16>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
   else
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F32>, dim3((unsigned)blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F32>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
   return check_launch("sample_vertices_kernel");
@@ -444,10 +433,7 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
 int saf_label_argmax(const int32_t* labels_one_hot, int64_t n_vox, int32_t n_classes, int32_t* out, void* stream) {
   if (!labels_one_hot || !out || n_vox < 0 || n_classes <= 0) return fail(SAF_E_INVALID, "label_argmax: bad arguments");
   if (n_vox == 0) return SAF_OK;
-  int64_t blocks = (n_vox + 3) / 4;
-  const int64_t cap = (int64_t)device_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(label_argmax_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(label_argmax_kernel, dim3(grid_1d(n_vox, 8, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      labels_one_hot, n_vox, n_classes, out);
   return check_launch("label_argmax_kernel");
 }

@@ -347,13 +347,6 @@ inline NnLayout nn_layout(int64_t n_ref) {
   return l;
 }
 
-inline unsigned grid_for(int64_t items, int per_cu) {
-  int64_t b = (items + kNnThreads - 1) / kNnThreads;
-  const int64_t cap = (int64_t)device_cus() * per_cu;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 }  // namespace saf
 
@@ -385,16 +378,16 @@ int saf_nearest_points(const float* ref, int64_t n_ref, const float* query, int6
   const size_t count_bytes = (size_t)(l.cap + 1) * sizeof(int);
   if (hipMemsetAsync(count, 0, count_bytes, s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(cell counts)");
   hipLaunchKernelGGL(nn_init_kernel, dim3(1), dim3(64), 0, s, g);
-  hipLaunchKernelGGL(nn_bbox_kernel, dim3(grid_for(n_ref, 4)), dim3(kNnThreads), 0, s, ref, n_ref, g);
+  hipLaunchKernelGGL(nn_bbox_kernel, dim3(grid_1d(n_ref, 4, kNnThreads)), dim3(kNnThreads), 0, s, ref, n_ref, g);
   hipLaunchKernelGGL(nn_grid_kernel, dim3(1), dim3(64), 0, s, g, l.cap);
-  hipLaunchKernelGGL(nn_count_kernel, dim3(grid_for(n_ref, 8)), dim3(kNnThreads), 0, s, ref, n_ref, g, count, pcell);
+  hipLaunchKernelGGL(nn_count_kernel, dim3(grid_1d(n_ref, 8, kNnThreads)), dim3(kNnThreads), 0, s, ref, n_ref, g, count, pcell);
   // start[0, cap + 1): cells past the grid's own count are empty, so start[cells] = n_ref whatever the grid turned out to be
   hipLaunchKernelGGL(nn_chunk_sums_kernel, dim3((unsigned)l.n_chunks), dim3(kNnThreads), 0, s, count, l.cap + 1, sums);
   hipLaunchKernelGGL(nn_scan_sums_kernel, dim3(1), dim3(kNnThreads), 0, s, sums, l.n_chunks);
   hipLaunchKernelGGL(nn_chunk_scan_kernel, dim3((unsigned)l.n_chunks), dim3(kNnThreads), 0, s, count, l.cap + 1, sums, start);
   if (hipMemsetAsync(count, 0, count_bytes, s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(cell cursors)");
-  hipLaunchKernelGGL(nn_scatter_kernel, dim3(grid_for(n_ref, 8)), dim3(kNnThreads), 0, s, ref, n_ref, pcell, start, count, sorted);
-  hipLaunchKernelGGL(nn_query_kernel, dim3(grid_for(n_query, 16)), dim3(kNnThreads), 0, s, query, n_query, g, start, sorted, out_index,
+  hipLaunchKernelGGL(nn_scatter_kernel, dim3(grid_1d(n_ref, 8, kNnThreads)), dim3(kNnThreads), 0, s, ref, n_ref, pcell, start, count, sorted);
+  hipLaunchKernelGGL(nn_query_kernel, dim3(grid_1d(n_query, 16, kNnThreads)), dim3(kNnThreads), 0, s, query, n_query, g, start, sorted, out_index,
                      out_dist2);
   return check_launch("nearest points");
 }
@@ -416,16 +409,13 @@ int saf_segmentation_counts(const int32_t* gt, const int32_t* pred, int64_t n, i
   if (n == 0) return SAF_OK;
   const bool full = n_classes <= kCountFullMax;
   const size_t shmem = (size_t)(3 * n_classes + (full ? n_classes * n_classes : 0)) * sizeof(int);
-  int64_t blocks = (n + kCountThreads * 16 - 1) / (kCountThreads * 16);
-  const int64_t cap = (int64_t)device_cus() * 2;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  const unsigned blocks = grid_1d(n, 2, kCountThreads * 16);
   auto fn = full ? seg_counts_kernel<true> : seg_counts_kernel<false>;
   if (shmem > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kCountThreads), shmem, s, gt, pred, n, (int)pred_stride, (int)topk, (int)n_classes,
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(kCountThreads), shmem, s, gt, pred, n, (int)pred_stride, (int)topk, (int)n_classes,
                      reinterpret_cast<unsigned long long*>(cmat), reinterpret_cast<unsigned long long*>(ncorrect_top1),
                      reinterpret_cast<unsigned long long*>(ncorrect_topk), reinterpret_cast<unsigned long long*>(ntotal));
   return check_launch("seg_counts_kernel");

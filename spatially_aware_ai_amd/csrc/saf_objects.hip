@@ -372,12 +372,9 @@ int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objec
   a.normalize = normalize;
   a.want_rgb = rgb_mean ? 1 : 0;
 
-  const int cus = device_cus();
   {
     const int64_t words = feat_mean ? n_words : 9 * (int64_t)K;
-    int64_t blocks = (words + 255) / 256;
-    if (blocks > (int64_t)cus * 8) blocks = (int64_t)cus * 8;
-    hipLaunchKernelGGL(object_init_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, words, a.s_bbox, K, a.nx, a.ny, a.nz);
+    hipLaunchKernelGGL(object_init_kernel, dim3(grid_1d(words, 8)), dim3(256), 0, s, w, words, a.s_bbox, K, a.nx, a.ny, a.nz);
     int rc = check_launch("object_init_kernel");
     if (rc) return rc;
   }
@@ -385,9 +382,7 @@ int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objec
     const int es = vol->feat_dtype == SAF_BF16 ? 2 : 4;
     const bool vec = ((int64_t)D * es) % 16 == 0 && ((uintptr_t)vol->clip_feat & 15) == 0;
     const int64_t n_chunks = (N + kObjChunk - 1) / kObjChunk;
-    int64_t blocks = (n_chunks + kObjThreads / 64 - 1) / (kObjThreads / 64);
-    if (blocks > (int64_t)cus * 8) blocks = (int64_t)cus * 8;
-    const dim3 grid((unsigned)blocks, feat_mean ? (unsigned)((D + kObjTile - 1) / kObjTile) : 1u);
+    const dim3 grid(grid_1d(n_chunks, 8, kObjThreads / 64), feat_mean ? (unsigned)((D + kObjTile - 1) / kObjTile) : 1u);
     if (!feat_mean)
       launch_stats<OBJ_ROWS_NONE>(a, grid, s);
     else if (es == 4)
@@ -406,9 +401,8 @@ int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objec
     o.coord_sum = coord_sum;
     o.rgb_mean = rgb_mean;
     o.feat_mean = feat_mean;
-    int64_t blocks = ((feat_mean ? (int64_t)K * D : (int64_t)K) + 255) / 256;
-    if (blocks > (int64_t)cus * 8) blocks = (int64_t)cus * 8;
-    hipLaunchKernelGGL(object_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, o);
+    const int64_t items = feat_mean ? (int64_t)K * D : (int64_t)K;
+    hipLaunchKernelGGL(object_finish_kernel, dim3(grid_1d(items, 8)), dim3(256), 0, s, a, o);
     return check_launch("object_finish_kernel");
   }
 }

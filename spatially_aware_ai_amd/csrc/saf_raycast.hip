@@ -5,13 +5,13 @@
 //   * gather_rows_kernel : dst[p, :] = src[index[p], :] (zeros for index < 0) in 16-byte lane accesses: the hit voxels' feature
 //                          rows for the existing text-query scans.
 //
-// Numerics contract of the ray cast (include/saf.h, saf_raycast; tests/raycast_reference.py restates it in NumPy): every fp32
-// operation below is written on its own, in the order stated there; the translation unit is compiled with -ffp-contract=off and
-// divisions are IEEE.
+// Numerics contract of the ray cast (include/saf.h, saf_raycast; tests/raycast_reference.py restates it in NumPy): its reading of
+// the TSDF as a field (the grid frame, the pixel's ray, the trilinear sample) has its one C statement in saf_field_dev.h; the
+// rest -- the box clip, the march and the hit -- is below, every fp32 operation written on its own, in the order stated there;
+// the translation unit is compiled with -ffp-contract=off and divisions are IEEE.
 #include <math.h>
 
-#include "saf_common.h"
-#include "saf_host.h"
+#include "saf_field_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -23,75 +23,19 @@ constexpr int kRayBlock = 16;
 constexpr int kRayMaxSamples = 65536;  // per ray (a bound on the loop whatever the arguments are)
 constexpr int kXcds = 8;
 
-// two values that are consecutive along z: one 8-byte request (4-byte aligned) instead of two
-struct __attribute__((packed, aligned(4))) PairF {
-  float a, b;
-};
-struct __attribute__((packed, aligned(4))) PairI {
-  int a, b;
-};
-
 struct RayArgs {
-  const float* tsdf;
-  const int* tsdf_weight;
+  FieldArgs field;
   const int* weight;
   const float* rgb;
-  const float* axis_x;
-  const float* axis_y;
-  const float* axis_z;
   const float* pose;
   const float* K;
   float* out_depth;
   int* out_voxel;
   float* out_rgb;
-  int nx, ny, nz;
   int height, width;
   int tiles_x;
   float step_vox, z_near, z_far;
 };
-
-// floor(g) clamped to [0, n - 2] (any g, NaN included, gives a cell inside the grid) and the offset from it
-__device__ __forceinline__ int cell_of(float g, int n, float& frac) {
-  int i = (int)__builtin_floorf(g);
-  i = i < 0 ? 0 : i;
-  i = i > n - 2 ? n - 2 : i;
-  frac = g - (float)i;
-  return i;
-}
-
-__device__ __forceinline__ float lerp(float a, float b, float f) {
-  const float d = b - a;
-  const float m = f * d;
-  return a + m;
-}
-
-// trilinear tsdf at grid coordinates (gx, gy, gz); returns whether all 8 corners have been observed
-__device__ __forceinline__ bool sample_tsdf(const RayArgs& A, float gx, float gy, float gz, float& f) {
-  float fx, fy, fz;
-  const int ix = cell_of(gx, A.nx, fx);
-  const int iy = cell_of(gy, A.ny, fy);
-  const int iz = cell_of(gz, A.nz, fz);
-  const int p00 = (ix * A.ny + iy) * A.nz + iz;  // < nx ny nz < 2^31 (checked on the host)
-  const int p01 = p00 + A.nz;
-  const int p10 = p00 + A.ny * A.nz;
-  const int p11 = p10 + A.nz;
-  const PairF t00 = *reinterpret_cast<const PairF*>(A.tsdf + p00);
-  const PairF t01 = *reinterpret_cast<const PairF*>(A.tsdf + p01);
-  const PairF t10 = *reinterpret_cast<const PairF*>(A.tsdf + p10);
-  const PairF t11 = *reinterpret_cast<const PairF*>(A.tsdf + p11);
-  const PairI w00 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p00);
-  const PairI w01 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p01);
-  const PairI w10 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p10);
-  const PairI w11 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p11);
-  const float c00 = lerp(t00.a, t00.b, fz);
-  const float c01 = lerp(t01.a, t01.b, fz);
-  const float c10 = lerp(t10.a, t10.b, fz);
-  const float c11 = lerp(t11.a, t11.b, fz);
-  const float c0 = lerp(c00, c01, fy);
-  const float c1 = lerp(c10, c11, fy);
-  f = lerp(c0, c1, fx);
-  return w00.a > 0 && w00.b > 0 && w01.a > 0 && w01.b > 0 && w10.a > 0 && w10.b > 0 && w11.a > 0 && w11.b > 0;
-}
 
 // one slab of the box clip: g(t) = og + t gd within [0, hi]
 __device__ __forceinline__ bool clip_axis(float og, float gd, float hi, float& tmin, float& tmax) {
@@ -122,28 +66,26 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(const RayArgs A) {
   const int v = (blk / A.tiles_x) * kRayBlock + (wave >> 1) * 8 + (lane >> 3);
   if (u >= A.width || v >= A.height) return;
 
-  // the grid: voxel centre i of an axis at axis[i]; voxel size from the x table's ends
-  const float ox = A.axis_x[0], oy = A.axis_y[0], oz = A.axis_z[0];
-  const float vs = (A.axis_x[A.nx - 1] - ox) / (float)(A.nx - 1);
+  const FieldArgs& F = A.field;
+  const GridFrame G = grid_frame(F);
+  const float vs = G.vs;
   // the ray in camera z: p(t) = o + t d, d = R (dcx, dcy, 1)
-  const float dcx = ((float)u - A.K[2]) / A.K[0];
-  const float dcy = ((float)v - A.K[5]) / A.K[4];
+  float dcx, dcy;
+  pixel_ray(A.K, u, v, dcx, dcy);
   const float* P = A.pose;
   const float dx = (P[0] * dcx + P[1] * dcy) + P[2];
   const float dy = (P[4] * dcx + P[5] * dcy) + P[6];
   const float dz = (P[8] * dcx + P[9] * dcy) + P[10];
   // in grid coordinates: g(t) = og + t gd
-  const float ogx = (P[3] - ox) / vs, ogy = (P[7] - oy) / vs, ogz = (P[11] - oz) / vs;
+  const float ogx = (P[3] - G.ox) / vs, ogy = (P[7] - G.oy) / vs, ogz = (P[11] - G.oz) / vs;
   const float gdx = dx / vs, gdy = dy / vs, gdz = dz / vs;
 
   float tmin = A.z_near, tmax = A.z_far;
-  bool ok = clip_axis(ogx, gdx, (float)(A.nx - 1), tmin, tmax);
-  ok = clip_axis(ogy, gdy, (float)(A.ny - 1), tmin, tmax) && ok;
-  ok = clip_axis(ogz, gdz, (float)(A.nz - 1), tmin, tmax) && ok;
+  bool ok = clip_axis(ogx, gdx, (float)(F.nx - 1), tmin, tmax);
+  ok = clip_axis(ogy, gdy, (float)(F.ny - 1), tmin, tmax) && ok;
+  ok = clip_axis(ogz, gdz, (float)(F.nz - 1), tmin, tmax) && ok;
   ok = ok && tmin <= tmax;
-  // unsupported intrinsics (skew, a third row other than 0 0 1) cannot be refused on the host without reading device memory:
-  // every pixel is a miss
-  ok = ok && A.K[1] == 0.0f && A.K[3] == 0.0f && A.K[6] == 0.0f && A.K[7] == 0.0f && A.K[8] == 1.0f;
+  ok = ok && is_pinhole(A.K);  // otherwise every pixel is a miss
 
   const float dmax = fmaxf(fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)), __builtin_fabsf(dz));
   const float s = (A.step_vox * vs) / dmax;
@@ -156,16 +98,17 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(const RayArgs A) {
     for (int k = 0; k < kRayMaxSamples; ++k) {
       const float t = tmin + (float)k * s;
       if (!(t <= tmax)) break;
-      float f;
-      const bool obs = sample_tsdf(A, ogx + t * gdx, ogy + t * gdy, ogz + t * gdz, f);
+      const FieldSample smp = sample_field(F, ogx + t * gdx, ogy + t * gdy, ogz + t * gdz);
+      const float f = smp.value;
+      const bool obs = smp.observed;
       if (prev_obs && obs && prev_f > 0.0f && f <= 0.0f) {
         const float t0 = tmin + (float)(k - 1) * s;
         const float ts = t0 + s * (prev_f / (prev_f - f));
-        const int vx = nearest_voxel(ogx + ts * gdx, A.nx);
-        const int vy = nearest_voxel(ogy + ts * gdy, A.ny);
-        const int vz = nearest_voxel(ogz + ts * gdz, A.nz);
+        const int vx = nearest_voxel(ogx + ts * gdx, F.nx);
+        const int vy = nearest_voxel(ogy + ts * gdy, F.ny);
+        const int vz = nearest_voxel(ogz + ts * gdz, F.nz);
         depth = ts;
-        voxel = (vx * A.ny + vy) * A.nz + vz;
+        voxel = (vx * F.ny + vy) * F.nz + vz;
         break;
       }
       prev_f = f;
@@ -213,27 +156,17 @@ int saf_raycast(const saf_volume* vol, const float* pose, const float* K, int32_
   if (!vol || !pose || !K || !out_depth || !out_voxel || height <= 0 || width <= 0 || !(step_vox > 0.0f) || !(z_far > z_near))
     return fail(SAF_E_INVALID, "raycast: bad arguments (%d x %d pixels, step_vox = %g, z in [%g, %g])", (int)height, (int)width,
                 (double)step_vox, (double)z_near, (double)z_far);
-  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || n_voxels(vol) > 0x7fffffff || !vol->tsdf || !vol->tsdf_weight || !vol->axis_x ||
-      !vol->axis_y || !vol->axis_z || (out_rgb && (!vol->rgb || !vol->weight)))
-    return fail(SAF_E_INVALID, "raycast: bad volume (%d x %d x %d voxels; at least 2 per axis, fewer than 2^31 in all)", (int)vol->nx,
-                (int)vol->ny, (int)vol->nz);
-  if ((int64_t)height * width > 0x7fffffff) return fail(SAF_E_INVALID, "raycast: too many pixels");
+  if (int rc = check_field_volume("raycast", vol, !out_rgb || (vol->rgb && vol->weight))) return rc;
+  if (int rc = check_pixel_count("raycast", height, width)) return rc;
   RayArgs a;
-  a.tsdf = vol->tsdf;
-  a.tsdf_weight = vol->tsdf_weight;
+  a.field = field_args(vol);
   a.weight = vol->weight;
   a.rgb = vol->rgb;
-  a.axis_x = vol->axis_x;
-  a.axis_y = vol->axis_y;
-  a.axis_z = vol->axis_z;
   a.pose = pose;
   a.K = K;
   a.out_depth = out_depth;
   a.out_voxel = out_voxel;
   a.out_rgb = out_rgb;
-  a.nx = vol->nx;
-  a.ny = vol->ny;
-  a.nz = vol->nz;
   a.height = height;
   a.width = width;
   a.tiles_x = (width + kRayBlock - 1) / kRayBlock;
@@ -252,10 +185,7 @@ int saf_gather_rows(const void* src, int64_t n_src_rows, int64_t row_bytes, cons
     return fail(SAF_E_INVALID, "gather rows: bad arguments (%lld source rows of %lld bytes, %lld indices; rows are multiples of 16 "
                 "bytes on 16-byte boundaries)", (long long)n_src_rows, (long long)row_bytes, (long long)n_index);
   const int64_t row_vecs = row_bytes / 16;
-  int64_t blocks = (n_index * row_vecs + 255) / 256;
-  const int64_t cap = (int64_t)device_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_1d(n_index * row_vecs, 16)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const uint4*>(src), n_src_rows, row_vecs, index, n_index, static_cast<uint4*>(dst));
   return check_launch("gather_rows_kernel");
 }

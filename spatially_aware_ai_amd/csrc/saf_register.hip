@@ -13,8 +13,7 @@
 // are IEEE.  Every index is tested on the float before it is converted, so any input (NaN, inf, 1e30, any T) stays in bounds.
 #include <math.h>
 
-#include "saf_common.h"
-#include "saf_host.h"
+#include "saf_field_dev.h"  // lerp
 
 #pragma clang fp contract(off)
 
@@ -112,7 +111,7 @@ __device__ __forceinline__ bool nearest_index(float us, float vs, int w, int h, 
 }
 
 // the bilinear cell of one axis: i0 = floor(s) in [-1, n - 1] (outside that range every tap is outside: false), f = s - i0
-__device__ __forceinline__ bool cell_of(float s, int n, int& i0, float& f) {
+__device__ __forceinline__ bool image_cell(float s, int n, int& i0, float& f) {
   const float fl = __builtin_floorf(s);
   if (!(fl >= -1.0f && fl <= (float)(n - 1))) return false;
   i0 = (int)fl;
@@ -123,12 +122,6 @@ __device__ __forceinline__ bool cell_of(float s, int n, int& i0, float& f) {
 __device__ __forceinline__ float tap(const float* __restrict__ img, int w, int h, int ch, int c, int iu, int iv) {
   if (iu < 0 || iu >= w || iv < 0 || iv >= h) return 0.0f;
   return img[((int64_t)iv * w + iu) * ch + c];
-}
-
-__device__ __forceinline__ float lerp(float a, float b, float f) {
-  const float d = b - a;
-  const float m = f * d;
-  return a + m;
 }
 
 // bilinear along u then v, taps outside the image contribute 0
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(kRegThreads) void undistort_kernel(const float* __r
   } else {
     int i0, j0;
     float fu, fv;
-    const bool in = cell_of(us, cs.w, i0, fu) && cell_of(vs, cs.h, j0, fv);  // (a non-finite coordinate has no cell)
+    const bool in = image_cell(us, cs.w, i0, fu) && image_cell(vs, cs.h, j0, fv);  // (a non-finite coordinate has no cell)
     for (int c = 0; c < ch; ++c) out[c] = in ? bilinear(img, cs.w, cs.h, ch, c, i0, j0, fu, fv) : 0.0f;
   }
 }
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(kRegThreads) void color_to_depth_kernel(const Gathe
   int i0 = 0, j0 = 0;
   float fu = 0.0f, fv = 0.0f;
   // VALID needs the whole cell inside the colour image: 0 <= floor <= n - 2 on both axes
-  valid = valid && cell_of(uc, A.cc.w, i0, fu) && cell_of(vc, A.cc.h, j0, fv) && i0 >= 0 && i0 <= A.cc.w - 2 && j0 >= 0 &&
+  valid = valid && image_cell(uc, A.cc.w, i0, fu) && image_cell(vc, A.cc.h, j0, fv) && i0 >= 0 && i0 <= A.cc.w - 2 && j0 >= 0 &&
           j0 <= A.cc.h - 2;
   if (valid && A.zbuf) {
     int zu, zv;
@@ -320,12 +313,6 @@ dim3 tile_grid(const saf_camera* c, int batch) {
 // (image rows of 16-pixel blocks are the grid's second dimension)
 bool good_grid(const saf_camera* c) { return (c->height + kRegBlock - 1) / kRegBlock <= 65535; }
 
-unsigned linear_blocks(int64_t n) {
-  int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)device_cus() * 16;
-  return (unsigned)(blocks > cap ? cap : blocks);
-}
-
 }  // namespace
 }  // namespace saf
 
@@ -362,10 +349,10 @@ int saf_depth_to_color(const float* depth, const saf_camera* cam_depth, const fl
   hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned* zbuf = reinterpret_cast<unsigned*>(out_depth);
   const int64_t n = (int64_t)batch * cam_color->height * cam_color->width;
-  hipLaunchKernelGGL(fill_kernel, dim3(linear_blocks(n)), dim3(256), 0, s, zbuf, n);
+  hipLaunchKernelGGL(fill_kernel, dim3(grid_1d(n, 16)), dim3(256), 0, s, zbuf, n);
   hipLaunchKernelGGL(splat_kernel, tile_grid(cam_depth, batch), dim3(kRegThreads), 0, s, depth, device_camera(cam_depth, false),
                      T_d2c, device_camera(cam_color, true), 0.5f * (float)max_footprint, zbuf);
-  hipLaunchKernelGGL(finish_kernel, dim3(linear_blocks(n)), dim3(256), 0, s, zbuf, n);
+  hipLaunchKernelGGL(finish_kernel, dim3(grid_1d(n, 16)), dim3(256), 0, s, zbuf, n);
   return check_launch("splat_kernel");
 }
 

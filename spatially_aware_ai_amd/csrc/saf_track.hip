@@ -7,13 +7,14 @@
 //   * pose_init_kernel / pose_solve_kernel : the Gauss-Newton loop of saf_pose_refine -- the same sum, a damped 6 x 6 Cholesky solve
 //                             in fp64, the pose update and the stopping rules, all decided on the device.
 //
-// Numerics contract (include/saf.h, saf_pose_linearize; tests/pose_reference.py restates it in NumPy): every fp32 operation of
-// the per-pixel chain is written on its own, in the order stated there; the translation unit is compiled with -ffp-contract=off
-// and divisions are IEEE.  No floating-point atomics anywhere: the same inputs give the same bytes whatever the scheduling.
+// Numerics contract (include/saf.h, saf_pose_linearize; tests/pose_reference.py restates it in NumPy): the residual is the ray
+// cast's reading of the TSDF as a field, whose one C statement is saf_field_dev.h (the grid frame, the pixel's ray, the trilinear
+// sample and its intermediates); the rest of the per-pixel chain is below, every fp32 operation written on its own, in the order
+// stated there; the translation unit is compiled with -ffp-contract=off and divisions are IEEE.  No floating-point atomics
+// anywhere: the same inputs give the same bytes whatever the scheduling.
 #include <math.h>
 
-#include "saf_common.h"
-#include "saf_host.h"
+#include "saf_field_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -25,14 +26,6 @@ constexpr int kSysSlots = 32;     // doubles per partial: H (21), b (6), cost, n
 constexpr int kSysUsed = 29;
 constexpr int kSumThreads = 256;  // 8 groups of 32 slots
 constexpr size_t kStateBytes = 512;
-
-// two values that are consecutive along z: one 8-byte request (4-byte aligned) instead of two
-struct __attribute__((packed, aligned(4))) PairF {
-  float a, b;
-};
-struct __attribute__((packed, aligned(4))) PairI {
-  int a, b;
-};
 
 // What the iterations of one saf_pose_refine call share (the head of its workspace).
 struct PoseState {
@@ -46,11 +39,7 @@ struct PoseState {
 static_assert(sizeof(PoseState) <= kStateBytes, "PoseState outgrew its slot");
 
 struct LinArgs {
-  const float* tsdf;
-  const int* tsdf_weight;
-  const float* axis_x;
-  const float* axis_y;
-  const float* axis_z;
+  FieldArgs field;
   const float* depth;
   const float* pose;
   const float* K;
@@ -58,27 +47,11 @@ struct LinArgs {
   double* partials;
   float* out_residual;
   float* out_jacobian;
-  int nx, ny, nz;
   int height, width;
   int stride, lat_w, lat_h, tiles_x, tiles_y;
   int level;
   float huber, r_max;
 };
-
-// floor(g) clamped to [0, n - 2] and the offset from it (g is finite and inside the grid here)
-__device__ __forceinline__ int cell_of(float g, int n, float& frac) {
-  int i = (int)__builtin_floorf(g);
-  i = i < 0 ? 0 : i;
-  i = i > n - 2 ? n - 2 : i;
-  frac = g - (float)i;
-  return i;
-}
-
-__device__ __forceinline__ float lerp(float a, float b, float f) {
-  const float d = b - a;
-  const float m = f * d;
-  return a + m;
-}
 
 __device__ __forceinline__ double wave_sum(double x) {
   // fixed pattern: lane i ends with the sum over all 64 lanes, added in the order of a butterfly over lane distance 32, 16, ..., 1
@@ -98,61 +71,39 @@ __global__ __launch_bounds__(kLinThreads) void pose_linearize_kernel(const LinAr
   const int u = on_lattice ? i * A.stride : 0, v = on_lattice ? j * A.stride : 0;  // < width, < height
   const int64_t pix = (int64_t)v * A.width + u;
 
-  // the grid: voxel centre i of an axis at axis[i]; voxel size from the x table's ends
-  const float ox = A.axis_x[0], oy = A.axis_y[0], oz = A.axis_z[0];
-  const float vs = (A.axis_x[A.nx - 1] - ox) / (float)(A.nx - 1);
+  const FieldArgs& F = A.field;
+  const GridFrame G = grid_frame(F);
+  const float vs = G.vs;
   const float* P = A.pose;
-  const float* K = A.K;
 
   const float z = A.depth[pix];
   bool ok = on_lattice && z > 0.0f && z <= 3.402823466e38f;  // (NaN fails both)
-  ok = ok && K[1] == 0.0f && K[3] == 0.0f && K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f;
+  ok = ok && is_pinhole(A.K);
   // the point: q = z d_cam, lever l = R q, p = l + t
-  const float dcx = ((float)u - K[2]) / K[0];
-  const float dcy = ((float)v - K[5]) / K[4];
+  float dcx, dcy;
+  pixel_ray(A.K, u, v, dcx, dcy);
   const float q0 = z * dcx, q1 = z * dcy, q2 = z;
   const float l0 = (P[0] * q0 + P[1] * q1) + P[2] * q2;
   const float l1 = (P[4] * q0 + P[5] * q1) + P[6] * q2;
   const float l2 = (P[8] * q0 + P[9] * q1) + P[10] * q2;
   const float p0 = l0 + P[3], p1 = l1 + P[7], p2 = l2 + P[11];
-  const float gx = (p0 - ox) / vs, gy = (p1 - oy) / vs, gz = (p2 - oz) / vs;
-  ok = ok && gx >= 0.0f && gx <= (float)(A.nx - 1) && gy >= 0.0f && gy <= (float)(A.ny - 1) && gz >= 0.0f &&
-       gz <= (float)(A.nz - 1);
+  const float gx = (p0 - G.ox) / vs, gy = (p1 - G.oy) / vs, gz = (p2 - G.oz) / vs;
+  ok = ok && gx >= 0.0f && gx <= (float)(F.nx - 1) && gy >= 0.0f && gy <= (float)(F.ny - 1) && gz >= 0.0f &&
+       gz <= (float)(F.nz - 1);
 
   float r = 0.0f, w = 0.0f;
   float J0 = 0.0f, J1 = 0.0f, J2 = 0.0f, J3 = 0.0f, J4 = 0.0f, J5 = 0.0f;
   if (ok) {  // (only then are the grid coordinates known to be finite and inside the grid)
-    float fx, fy, fz;
-    const int ix = cell_of(gx, A.nx, fx);
-    const int iy = cell_of(gy, A.ny, fy);
-    const int iz = cell_of(gz, A.nz, fz);
-    const int p00 = (ix * A.ny + iy) * A.nz + iz;  // < nx ny nz < 2^31 (checked on the host)
-    const int p01 = p00 + A.nz;
-    const int p10 = p00 + A.ny * A.nz;
-    const int p11 = p10 + A.nz;
-    const PairI w00 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p00);
-    const PairI w01 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p01);
-    const PairI w10 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p10);
-    const PairI w11 = *reinterpret_cast<const PairI*>(A.tsdf_weight + p11);
-    const PairF t00 = *reinterpret_cast<const PairF*>(A.tsdf + p00);
-    const PairF t01 = *reinterpret_cast<const PairF*>(A.tsdf + p01);
-    const PairF t10 = *reinterpret_cast<const PairF*>(A.tsdf + p10);
-    const PairF t11 = *reinterpret_cast<const PairF*>(A.tsdf + p11);
-    ok = w00.a > 0 && w00.b > 0 && w01.a > 0 && w01.b > 0 && w10.a > 0 && w10.b > 0 && w11.a > 0 && w11.b > 0;
     // the residual: trilinear, z then y then x
-    const float c00 = lerp(t00.a, t00.b, fz);
-    const float c01 = lerp(t01.a, t01.b, fz);
-    const float c10 = lerp(t10.a, t10.b, fz);
-    const float c11 = lerp(t11.a, t11.b, fz);
-    const float c0 = lerp(c00, c01, fy);
-    const float c1 = lerp(c10, c11, fy);
-    r = lerp(c0, c1, fx);
+    const FieldSample f = sample_field(F, gx, gy, gz);
+    ok = f.observed;
+    r = f.value;
     // its gradient in voxel units, from the same intermediates
-    const float ddx = c1 - c0;
-    const float ddy = lerp(c01 - c00, c11 - c10, fx);
-    const float dz0 = lerp(t00.b - t00.a, t01.b - t01.a, fy);
-    const float dz1 = lerp(t10.b - t10.a, t11.b - t11.a, fy);
-    const float ddz = lerp(dz0, dz1, fx);
+    const float ddx = f.c1 - f.c0;
+    const float ddy = lerp(f.c01 - f.c00, f.c11 - f.c10, f.fx);
+    const float dz0 = lerp(f.t00.b - f.t00.a, f.t01.b - f.t01.a, f.fy);
+    const float dz1 = lerp(f.t10.b - f.t10.a, f.t11.b - f.t11.a, f.fy);
+    const float ddz = lerp(dz0, dz1, f.fx);
     const float n0 = ddx / vs, n1 = ddy / vs, n2 = ddz / vs;
     const float ar = __builtin_fabsf(r);
     ok = ok && ar < A.r_max;
@@ -317,9 +268,7 @@ __global__ __launch_bounds__(kSumThreads) void pose_solve_kernel(const SolveArgs
   const double mean_cost = n_valid > 0.0 ? total[27] / n_valid : 0.0;
   int status = 1;
   double step_t = 0.0, step_r = 0.0;
-  const float* K = A.K;
-  const bool k_ok = K[1] == 0.0f && K[3] == 0.0f && K[6] == 0.0f && K[7] == 0.0f && K[8] == 1.0f;
-  if (!k_ok) {
+  if (!is_pinhole(A.K)) {
     status = 4;
   } else if (n_valid < (double)prm.min_valid) {
     status = 2;
@@ -451,21 +400,13 @@ inline int64_t tiles_of(int height, int width, int stride) {
 int check_common(const char* what, const saf_volume* vol, const float* depth, int height, int width, const float* pose, const float* K) {
   if (!vol || !depth || !pose || !K || height <= 0 || width <= 0)
     return fail(SAF_E_INVALID, "%s: bad arguments (%d x %d pixels; vol, depth, pose and K must not be NULL)", what, (int)height, (int)width);
-  if (vol->nx < 2 || vol->ny < 2 || vol->nz < 2 || n_voxels(vol) > 0x7fffffff || !vol->tsdf || !vol->tsdf_weight || !vol->axis_x ||
-      !vol->axis_y || !vol->axis_z)
-    return fail(SAF_E_INVALID, "%s: bad volume (%d x %d x %d voxels; at least 2 per axis, fewer than 2^31 in all)", what, (int)vol->nx,
-                (int)vol->ny, (int)vol->nz);
-  if ((int64_t)height * width > 0x7fffffff) return fail(SAF_E_INVALID, "%s: too many pixels", what);
-  return SAF_OK;
+  if (int rc = check_field_volume(what, vol)) return rc;
+  return check_pixel_count(what, height, width);
 }
 
 void fill_lin_args(LinArgs& a, const saf_volume* vol, const float* depth, int height, int width, const float* pose, const float* K,
                    int stride, float huber, float r_max, void* workspace) {
-  a.tsdf = vol->tsdf;
-  a.tsdf_weight = vol->tsdf_weight;
-  a.axis_x = vol->axis_x;
-  a.axis_y = vol->axis_y;
-  a.axis_z = vol->axis_z;
+  a.field = field_args(vol);
   a.depth = depth;
   a.pose = pose;
   a.K = K;
@@ -473,9 +414,6 @@ void fill_lin_args(LinArgs& a, const saf_volume* vol, const float* depth, int he
   a.partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + kStateBytes);
   a.out_residual = nullptr;
   a.out_jacobian = nullptr;
-  a.nx = vol->nx;
-  a.ny = vol->ny;
-  a.nz = vol->nz;
   a.height = height;
   a.width = width;
   a.stride = stride;
@@ -518,15 +456,8 @@ int saf_pose_linearize(const saf_volume* vol, const float* depth, int32_t height
   a.out_residual = out_residual;
   a.out_jacobian = out_jacobian;
   const int64_t npix = (int64_t)height * width;
-  const int64_t cap = (int64_t)device_cus() * 16;
-  if (out_residual) {
-    const int64_t blocks = (npix + 255) / 256;
-    hipLaunchKernelGGL(pose_fill_nan_kernel, dim3((unsigned)(blocks > cap ? cap : blocks)), dim3(256), 0, s, out_residual, npix);
-  }
-  if (out_jacobian) {
-    const int64_t blocks = (6 * npix + 255) / 256;
-    hipLaunchKernelGGL(pose_fill_nan_kernel, dim3((unsigned)(blocks > cap ? cap : blocks)), dim3(256), 0, s, out_jacobian, 6 * npix);
-  }
+  if (out_residual) hipLaunchKernelGGL(pose_fill_nan_kernel, dim3(grid_1d(npix, 16)), dim3(256), 0, s, out_residual, npix);
+  if (out_jacobian) hipLaunchKernelGGL(pose_fill_nan_kernel, dim3(grid_1d(6 * npix, 16)), dim3(256), 0, s, out_jacobian, 6 * npix);
   hipLaunchKernelGGL(pose_linearize_kernel, dim3(lin_blocks(a)), dim3(kLinThreads), 0, s, a);
   hipLaunchKernelGGL(pose_sum_kernel, dim3(1), dim3(kSumThreads), 0, s, a.partials, a.tiles_x * a.tiles_y, out_system);
   return check_launch("pose_linearize_kernel");

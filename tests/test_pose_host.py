@@ -15,19 +15,12 @@ import pytest
 
 import pose_reference as pr
 import raycast_reference as rr
+from host_stubs import fake_volume as _fake_volume
 from spatially_aware_ai_amd import _abi, _lib
 from spatially_aware_ai_amd import synthetic as syn
 
 FRAGILE_CAP = 0.01
 VALID_MIN = 0.30
-
-
-def _fake_volume(n=8):
-    v = _abi.SafVolume()
-    v.nx = v.ny = v.nz = n
-    for f in ("axis_x", "axis_y", "axis_z", "tsdf", "tsdf_weight", "weight", "rgb", "clip_feat"):
-        setattr(v, f, 4096)  # non-NULL, aligned: the descriptor is only inspected
-    return v
 
 
 def _big_volume():

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import raycast_reference as rr
+from host_stubs import fake_volume as _fake_volume
 from spatially_aware_ai_amd import _abi, _lib
 from spatially_aware_ai_amd import synthetic as syn
 
@@ -108,14 +109,6 @@ def test_unsupported_intrinsics_are_all_misses(fused):
         bad[i, j] = val
         r = rr.raycast(vol.tsdf.numpy(), vol.tsdf_weight.numpy(), axes, pose.numpy(), bad.numpy(), h, w, dtype=np.float32)
         assert not r["hit"].any() and (r["depth"] == 0).all() and (r["voxel"] == -1).all()
-
-
-def _fake_volume(n=8):
-    v = _abi.SafVolume()
-    v.nx = v.ny = v.nz = n
-    for f in ("axis_x", "axis_y", "axis_z", "tsdf", "tsdf_weight", "weight", "rgb", "clip_feat"):
-        setattr(v, f, 4096)  # non-NULL, aligned: the descriptor is only inspected
-    return v
 
 
 def test_raycast_rejects_bad_arguments_on_the_host():

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import small_pass_reference as sp
+from host_stubs import P, fake_volume  # P: every call of the host-side tests below returns before it would be used
 from spatially_aware_ai_amd import _abi, _lib
 
 CUS = 256  # an MI355X; the GPU tests read the device's count
@@ -206,18 +207,8 @@ def test_clear_inputs_are_not_hollow():
 
 
 # ---------------------------------------------------------------------------------------------- the host side of the entry points
-P = 4096  # a non-NULL, 16-byte aligned stand-in for a device pointer; every call below returns before it would be used
-
-
-def _fake_volume(n=4, dim=8, dtype=_abi.SAF_F32, **fields):
-    v = _abi.SafVolume()
-    v.nx = v.ny = v.nz = n
-    v.feat_dim, v.feat_dtype = dim, dtype
-    for f in ("axis_x", "axis_y", "axis_z", "tsdf", "tsdf_weight", "weight", "rgb", "clip_feat"):
-        setattr(v, f, P)
-    for f, val in fields.items():
-        setattr(v, f, val)
-    return C.byref(v)
+def _fake_volume(**fields):
+    return C.byref(fake_volume(n=4, dim=8, **fields))
 
 
 @pytest.mark.parametrize("fn", ["saf_merge_finalize", "saf_mean_to_sum"])
