@@ -795,11 +795,7 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
     fn = (cpl == 1) ? pick_lds<1, 1, 4>(lds, undo) : pick_lds<1, 0, 1>(lds, undo);
   }
   const size_t shmem = lds ? lds_map_bytes(D, P) : 0;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", shmem, hipGetErrorString(e));
-  }
+  if (int rc = allow_lds(fn, shmem)) return rc;
   // 512-thread workgroups (8 waves at <= 128 VGPRs = half of each SIMD's register file, one LDS
   // image of the map).  Alone on the chip two of them share a CU; in the saf_fuse_frames pipeline
   // ONE per CU is launched so that the other half of the registers, ~80 KB of LDS and 16 wave slots

@@ -45,6 +45,15 @@ inline unsigned grid_1d(int64_t items, int per_cu, int per_wg = 256) {
   return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
+// Before a launch with `bytes` of dynamic LDS: above the 64 KB every kernel may ask for, the kernel's own limit is raised to them.
+template <typename K>
+inline int allow_lds(K* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return SAF_OK;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", bytes, hipGetErrorString(e));
+  return SAF_OK;
+}
+
 // A volume that the field readers (saf_field_dev.h) can use: two voxels per axis for a cell, int32 voxel indices, and the tsdf,
 // its weights and the axis tables.  `also` is whatever else the entry `what` needs of the volume.
 inline int check_field_volume(const char* what, const saf_volume* vol, bool also = true) {

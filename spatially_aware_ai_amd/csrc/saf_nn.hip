@@ -411,10 +411,7 @@ int saf_segmentation_counts(const int32_t* gt, const int32_t* pred, int64_t n, i
   const size_t shmem = (size_t)(3 * n_classes + (full ? n_classes * n_classes : 0)) * sizeof(int);
   const unsigned blocks = grid_1d(n, 2, kCountThreads * 16);
   auto fn = full ? seg_counts_kernel<true> : seg_counts_kernel<false>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
+  if (int rc = allow_lds(fn, shmem)) return rc;
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(kCountThreads), shmem, s, gt, pred, n, (int)pred_stride, (int)topk, (int)n_classes,
                      reinterpret_cast<unsigned long long*>(cmat), reinterpret_cast<unsigned long long*>(ncorrect_top1),
                      reinterpret_cast<unsigned long long*>(ncorrect_topk), reinterpret_cast<unsigned long long*>(ntotal));

@@ -11,6 +11,8 @@
 // the reference's L <= ~64; the Q=1000 MFMA formulation is listed as next work in DESIGN.md.
 #include <math.h>
 
+#include <type_traits>
+
 #include "saf_common.h"
 #include "saf_host.h"
 
@@ -40,6 +42,39 @@ __device__ __forceinline__ float load_feat(const void* __restrict__ base, int64_
   return static_cast<const float*>(base)[i];
 }
 
+// One wave's row: into LDS (row[]), normalised there, then its dot product with every label into sc[] (SCALED: times `scale`).
+template <int FT, bool SCALED>
+__device__ __forceinline__ void row_scores(const void* feats, int64_t r, int64_t fstride, int D, const float* text, int L, int64_t tstride,
+                                           float scale, int normalize, float* row, float* sc, int lane) {
+  float ss = 0.f;
+  for (int c = lane; c < D; c += 64) {
+    const float x = load_feat<FT>(feats, r * fstride + c);
+    row[c] = x;
+    ss += x * x;
+  }
+  if (normalize) {
+    // clip_feat /= clip_feat.norm(dim=-1, keepdim=True); nan_to_num   clip_seem_fusion.py:508-511
+    float norm = sqrtf(wave_sum(ss));
+    // SAF_NORM_L2_CLAMP: feat_norm.clamp_min_(0.1)   eval_scannet_segmentation.py:549-551, hypersim_eval.py:50-51
+    if (normalize == SAF_NORM_L2_CLAMP) norm = norm < 0.1f ? 0.1f : norm;
+    for (int c = lane; c < D; c += 64) {
+      float q = row[c] / norm;
+      if (normalize == SAF_NORM_L2) {
+        if (q != q) q = 0.f;
+        if (__builtin_isinf(q)) q = q > 0.f ? 3.4028234663852886e38f : -3.4028234663852886e38f;
+      }
+      row[c] = q;
+    }
+  }
+  for (int l = 0; l < L; ++l) {
+    const float* t = text + (int64_t)l * tstride;
+    float acc = 0.f;
+    for (int c = lane; c < D; c += 64) acc = __builtin_fmaf(row[c], t[c], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) sc[l] = SCALED ? scale * acc : acc;
+  }
+}
+
 template <int EPI, int FT>
 __global__ __launch_bounds__(kQThreads) void query_kernel(const void* __restrict__ feats, int64_t n_rows,
                                                            int64_t fstride, int D, const float* __restrict__ text,
@@ -55,35 +90,7 @@ __global__ __launch_bounds__(kQThreads) void query_kernel(const void* __restrict
   for (int64_t r0 = (int64_t)blockIdx.x * kQWaves; r0 < n_rows; r0 += (int64_t)gridDim.x * kQWaves) {
     const int64_t r = r0 + wave;
     const bool active = r < n_rows;
-    if (active) {
-      float ss = 0.f;
-      for (int c = lane; c < D; c += 64) {
-        const float x = load_feat<FT>(feats, r * fstride + c);
-        row[c] = x;
-        ss += x * x;
-      }
-      if (normalize) {
-        // clip_feat /= clip_feat.norm(dim=-1, keepdim=True); nan_to_num   clip_seem_fusion.py:508-511
-        float norm = sqrtf(wave_sum(ss));
-        // SAF_NORM_L2_CLAMP: feat_norm.clamp_min_(0.1)   eval_scannet_segmentation.py:549-551, hypersim_eval.py:50-51
-        if (normalize == SAF_NORM_L2_CLAMP) norm = norm < 0.1f ? 0.1f : norm;
-        for (int c = lane; c < D; c += 64) {
-          float q = row[c] / norm;
-          if (normalize == SAF_NORM_L2) {
-            if (q != q) q = 0.f;
-            if (__builtin_isinf(q)) q = q > 0.f ? 3.4028234663852886e38f : -3.4028234663852886e38f;
-          }
-          row[c] = q;
-        }
-      }
-      for (int l = 0; l < L; ++l) {
-        const float* t = text + (int64_t)l * tstride;
-        float acc = 0.f;
-        for (int c = lane; c < D; c += 64) acc = __builtin_fmaf(row[c], t[c], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) sc[l] = acc;
-      }
-    }
+    if (active) row_scores<FT, false>(feats, r, fstride, D, text, L, tstride, scale, normalize, row, sc, lane);
     __syncthreads();  // sc[] written by lane 0, read by all lanes below
     if (active) {
       if (EPI == SAF_Q_SCORES) {
@@ -133,26 +140,6 @@ __global__ __launch_bounds__(kQThreads) void query_kernel(const void* __restrict
   }
 }
 
-template <int EPI, int FT>
-int launch_t(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-           float scale, int normalize, float* wts, float* out, float* out_last, hipStream_t s) {
-  const size_t shmem = (size_t)kQWaves * (((D + 3) & ~3) + ((L + 3) & ~3)) * sizeof(float);
-  if (shmem > 150 * 1024) return fail(SAF_E_UNSUPPORTED, "feat_dim + n_text too large for the v1 scan (%zu B LDS)", shmem);
-  auto fn = query_kernel<EPI, FT>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  int64_t blocks = (n_rows + kQWaves - 1) / kQWaves;
-  const int64_t cap = (int64_t)device_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kQThreads), shmem, s, feats, n_rows, fstride, D, text, L,
-                     tstride, scale, normalize, wts, out, out_last);
-  return check_launch("query_kernel");
-}
-
 // ------------------------------------------------------------------------------------------
 // MFMA scan (feat_dim % 8 == 0, n_text <= 64): exact-fp32 matrix cores.
 //
@@ -181,14 +168,11 @@ __device__ __forceinline__ float4 load_feat4(const void* __restrict__ base, int6
   return make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
 }
 
-#ifndef SAF_QM_GROUP
-#define SAF_QM_GROUP 8
-#endif
-#ifndef SAF_QM_SLOTS
-#define SAF_QM_SLOTS 2  // register groups of the row ring (one is multiplied, the others are in flight)
-#endif
-constexpr int kQGroup = SAF_QM_GROUP;  // K chunks (of 8 floats) per prefetch group: 64 floats of every row
-constexpr int kQSlots = SAF_QM_SLOTS;
+constexpr int kQGroup = 8;  // K chunks (of 8 floats) per prefetch group: 64 floats of every row
+// register groups of the row ring: one is multiplied, the other is in flight.  (A plain constant since the build-time variants went;
+// the kernels keep their loops over the slots as they were -- spelling the two slots out moved instructions in 79 of the 128 matrix
+// kernels, and one function template for the ring cost query_mfma_kernel occupancy: profiles/r09.)
+constexpr int kQSlots = 2;
 
 // Reductions over the 32 lanes of a half without the LDS (round 6; rounds 1-5: five ds_bpermute steps each, 16 to 32 chains per
 // tile): quads, eights and sixteens by DPP inside the adds, the two 16-lane rows of the half by one v_permlane16_swap -- swapping a
@@ -568,6 +552,26 @@ __device__ __forceinline__ void split2(float y0, float y1, uint32_t& hi, uint32_
   lo = __builtin_bit_cast(uint32_t, lv);
 }
 
+// A row's scale 2^re follows its running maximum: a group's largest magnitude `gm` (this half's part) against the scale, before
+// the group is cut.  Where the scale changes, the row's accumulators are multiplied by the same power of two (exact).
+template <int TILES>
+__device__ __forceinline__ void fit_row_scale(float gm, int& re, bool& seen, f32x16 (&acc)[TILES], int h) {
+  gm = other_half_max(gm);
+  const bool need = ldexpf(gm, re) >= 32768.0f || (!seen && gm > 0.0f);
+  if (__builtin_amdgcn_ballot_w64(need)) {
+    const int ne = need ? (gm < INFINITY ? split_exponent(gm) : 0) : re;
+    const float fac = need && seen ? ldexpf(1.0f, ne - re) : 1.0f;  // (0 once the row has grown by more than fp32's range)
+    re = ne;
+    seen = seen || gm > 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float f = __shfl(fac, (i & 3) + 8 * (i >> 2) + 4 * h);
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) acc[t][i] *= f;
+    }
+  }
+}
+
 template <int EPI, int FT, int TILES, int TH>
 __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restrict__ feats, int64_t n_rows, int64_t fstride, int D,
                                                          const float* __restrict__ text, int L, int64_t tstride, float scale,
@@ -614,7 +618,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
   // why three slots, or four, never changed anything).  Where a row is a whole number of PAIRS of groups (feat_dim a multiple of
   // 128) the two slots are loaded by unconditional code -- behind a tile's last group comes the wave's NEXT tile's first (behind
   // the last tile: a row nobody uses) -- and the waits count 8 younger loads: vmcnt(15) .. vmcnt(8).
-  const bool chain = kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
+  const bool chain = n_groups >= 2 && n_groups % 2 == 0;
   const int64_t tile0 = (int64_t)blockIdx.x * (TH / 64) + wave, tile_step = (int64_t)gridDim.x * (TH / 64);
   auto row_base = [&](int64_t tile) {
     int64_t row = tile * 32 + m;
@@ -640,23 +644,7 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
     float ss = 0.0f;
     int re = 0;         // the row's scale is 2^re (applied by v_ldexp_f32: any exponent, denormal features included)
     bool seen = false;  // a feature of the row was not zero
-    // a group's largest magnitude `gm` (this half's part) against the row's scale, before the group is cut
-    auto fit = [&](float gm) {
-      gm = other_half_max(gm);
-      const bool need = ldexpf(gm, re) >= 32768.0f || (!seen && gm > 0.0f);
-      if (__builtin_amdgcn_ballot_w64(need)) {
-        const int ne = need ? (gm < INFINITY ? split_exponent(gm) : 0) : re;
-        const float fac = need && seen ? ldexpf(1.0f, ne - re) : 1.0f;  // (0 once the row has grown by more than fp32's range)
-        re = ne;
-        seen = seen || gm > 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float f = __shfl(fac, (i & 3) + 8 * (i >> 2) + 4 * h);
-#pragma unroll
-          for (int t = 0; t < TILES; ++t) acc[t][i] *= f;
-        }
-      }
-    };
+    auto fit = [&](float gm) { fit_row_scale(gm, re, seen, acc, h); };
     // one k-step: chunks 2p and 2p + 1 of the lane's row (k = 16p + 8u + 4h + j)
     auto step = [&](const float4& a0, const float4& a1, int p) {
       ss = __builtin_fmaf(a0.x, a0.x, ss);
@@ -697,12 +685,12 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
     if (chain) {
       for (int g = 0; g < n_groups; g += 2) {
 #pragma unroll
-        for (int q = 0; q < kQGroup; ++q) ring[1 % kQSlots][q] = load_feat4<FT>(feats, base + 8 * ((g + 1) * kQGroup + q));
+        for (int q = 0; q < kQGroup; ++q) ring[1][q] = load_feat4<FT>(feats, base + 8 * ((g + 1) * kQGroup + q));
         multiply(ring[0], g);
         const int64_t from = g + 2 < n_groups ? base + 8 * ((g + 2) * kQGroup) : base_next;
 #pragma unroll
         for (int q = 0; q < kQGroup; ++q) ring[0][q] = load_feat4<FT>(feats, from + 8 * q);
-        multiply(ring[1 % kQSlots], g + 1);
+        multiply(ring[1], g + 1);
       }
     } else {
 #pragma unroll
@@ -791,7 +779,7 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
   const unsigned char* tb = s_split + (size_t)m * rs_bytes + h * 32;
   const uint16_t* f16 = static_cast<const uint16_t*>(feats);
   typedef unsigned int q16_u4 __attribute__((ext_vector_type(4)));
-  const bool chain = kQSlots == 2 && n_groups >= 2 && n_groups % 2 == 0;
+  const bool chain = n_groups >= 2 && n_groups % 2 == 0;
   const int64_t tile0 = (int64_t)blockIdx.x * (TH / 64) + wave, tile_step = (int64_t)gridDim.x * (TH / 64);
   q16_u4 ring[kQSlots][kQGroup16];
   if (chain && tile0 < n_tiles) {
@@ -812,22 +800,7 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
     float ss = 0.0f;
     int re = 0;         // bf16: the row's scale is 2^re, following its running maximum (query_split_kernel); fp16: none
     bool seen = false;
-    auto fit = [&](float gm) {
-      gm = other_half_max(gm);
-      const bool need = ldexpf(gm, re) >= 32768.0f || (!seen && gm > 0.0f);
-      if (__builtin_amdgcn_ballot_w64(need)) {
-        const int ne = need ? (gm < INFINITY ? split_exponent(gm) : 0) : re;
-        const float fac = need && seen ? ldexpf(1.0f, ne - re) : 1.0f;
-        re = ne;
-        seen = seen || gm > 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float f = __shfl(fac, (i & 3) + 8 * (i >> 2) + 4 * h);
-#pragma unroll
-          for (int t = 0; t < TILES; ++t) acc[t][i] *= f;
-        }
-      }
-    };
+    auto fit = [&](float gm) { fit_row_scale(gm, re, seen, acc, h); };
     auto widen = [](uint32_t w, float& x0, float& x1) {  // two bf16 -> fp32
       x0 = __builtin_bit_cast(float, w << 16);
       x1 = __builtin_bit_cast(float, w & 0xffff0000u);
@@ -900,12 +873,12 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
       const uint16_t* rpn = f16 + nrow * fstride + 8 * h;
       for (int g = 0; g < n_groups; g += 2) {
 #pragma unroll
-        for (int q = 0; q < kQGroup16; ++q) ring[1 % kQSlots][q] = *reinterpret_cast<const q16_u4*>(rp + 16 * ((g + 1) * kQGroup16 + q));
+        for (int q = 0; q < kQGroup16; ++q) ring[1][q] = *reinterpret_cast<const q16_u4*>(rp + 16 * ((g + 1) * kQGroup16 + q));
         multiply(ring[0], g);
         const uint16_t* from = g + 2 < n_groups ? rp + 16 * ((g + 2) * kQGroup16) : rpn;
 #pragma unroll
         for (int q = 0; q < kQGroup16; ++q) ring[0][q] = *reinterpret_cast<const q16_u4*>(from + 16 * q);
-        multiply(ring[1 % kQSlots], g + 1);
+        multiply(ring[1], g + 1);
       }
     } else {
 #pragma unroll
@@ -941,29 +914,69 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Host side.  What a scan launch needs travels in one struct, filled once by saf_query_scan / saf_query_topk; the kernels keep
+// their parameter lists (their pointers are __restrict__, which a struct's members would not carry to the optimiser), so the
+// struct is unpacked at the one launch of each kernel.
+// ------------------------------------------------------------------------------------------
+struct ScanArgs {
+  int ft = SAF_F32;  // saf_dtype of the feature rows
+  const void* feats = nullptr;
+  int64_t n_rows = 0, fstride = 0;
+  int D = 0;
+  const float* text = nullptr;
+  int L = 0;
+  int64_t tstride = 0;
+  float scale = 1.0f;
+  int normalize = 0;
+  float* wts = nullptr;  // surgery: the labels' weights (written by the EPI_WEIGHTS pass, read by the scans)
+  float* out = nullptr;
+  float* out_last = nullptr;
+  int64_t out_stride = 0;  // where this launch's L columns lie in the output row: 0 and 0 = the row is these L columns, or
+  int out_col0 = 0;        // (row length, first column) for one block of a wider row
+  TopkArgs tk;
+  hipStream_t s = nullptr;
+};
+
+// f(std::integral_constant<int, FT>{}) for the feature dtype (checked by the entry points)
+template <typename F>
+int dispatch_ft(int ft, F&& f) {
+  switch (ft) {
+    case SAF_BF16: return f(std::integral_constant<int, SAF_BF16>{});
+    case SAF_F16: return f(std::integral_constant<int, SAF_F16>{});
+    default: return f(std::integral_constant<int, SAF_F32>{});
+  }
+}
+
+// one wave per row (query_kernel): any shape
+template <int EPI>
+int launch(const ScanArgs& a) {
+  return dispatch_ft(a.ft, [&](auto ft) {
+    const size_t shmem = (size_t)kQWaves * (((a.D + 3) & ~3) + ((a.L + 3) & ~3)) * sizeof(float);
+    if (shmem > 150 * 1024) return fail(SAF_E_UNSUPPORTED, "feat_dim + n_text too large for the v1 scan (%zu B LDS)", shmem);
+    auto fn = query_kernel<EPI, decltype(ft)::value>;
+    if (int rc = allow_lds(fn, shmem)) return rc;
+    hipLaunchKernelGGL(fn, dim3(grid_1d(a.n_rows, 8, kQWaves)), dim3(kQThreads), shmem, a.s, a.feats, a.n_rows, a.fstride, a.D, a.text,
+                       a.L, a.tstride, a.scale, a.normalize, a.wts, a.out, a.out_last);
+    return check_launch("query_kernel");
+  });
+}
+
 template <int EPI, int FT, int TILES, int TH, int SPLIT>  // SPLIT: 0 the exact-fp32 scan, 1 the split scan, 2 its 16-bit-volume form
-int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                   float scale, int normalize, const float* wts, float* out, float* out_last, int per_cu, size_t shmem, hipStream_t s,
-                   int64_t out_stride, int out_col0, const TopkArgs& tk) {
+int launch_mfma_th(const ScanArgs& a, int per_cu, size_t shmem) {
   auto fn = SPLIT == 2 ? query_split16_kernel<EPI, (FT == SAF_F32 ? SAF_F16 : FT), TILES, TH>
             : SPLIT ? query_split_kernel<EPI, FT, TILES, TH> : query_mfma_kernel<EPI, FT, TILES, TH>;
   constexpr int kWavesTh = TH / 64;
-  int64_t blocks = ((n_rows + 31) / 32 + kWavesTh - 1) / kWavesTh;
-  const int64_t cap = (int64_t)device_cus() * (per_cu < 1 ? 1 : per_cu);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  if (per_cu < 1) per_cu = 1;
   // the split scan's staged stores: a whole [N, L] matrix on a 16-byte boundary, and 8 x 32 TILES floats of LDS per wave to spare
   const size_t stage_bytes = (size_t)kWavesTh * TILES * 256 * sizeof(float);
-  const bool stage = SPLIT && out && (out_stride <= 0 || out_stride == L) && out_col0 == 0 && ((uintptr_t)out & 15) == 0 &&
-                     shmem + stage_bytes <= 159 * 1024 && (160 * 1024) / (shmem + stage_bytes + 256) >= (size_t)(per_cu < 1 ? 1 : per_cu);
+  const bool stage = SPLIT && a.out && (a.out_stride <= 0 || a.out_stride == a.L) && a.out_col0 == 0 && ((uintptr_t)a.out & 15) == 0 &&
+                     shmem + stage_bytes <= 159 * 1024 && (160 * 1024) / (shmem + stage_bytes + 256) >= (size_t)per_cu;
   if (stage) shmem += stage_bytes;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(TH), shmem, s, feats, n_rows, fstride, D, text, L,
-                     tstride, scale, normalize, wts, out, out_last, out_stride > 0 ? out_stride : (int64_t)L, out_col0, stage ? 1 : 0, tk);
+  if (int rc = allow_lds(fn, shmem)) return rc;
+  hipLaunchKernelGGL(fn, dim3(grid_1d((a.n_rows + 31) / 32, per_cu, kWavesTh)), dim3(TH), shmem, a.s, a.feats, a.n_rows, a.fstride, a.D,
+                     a.text, a.L, a.tstride, a.scale, a.normalize, a.wts, a.out, a.out_last,
+                     a.out_stride > 0 ? a.out_stride : (int64_t)a.L, a.out_col0, stage ? 1 : 0, a.tk);
   return check_launch(SPLIT == 2 ? "query_split16_kernel" : SPLIT ? "query_split_kernel" : "query_mfma_kernel");
 }
 
@@ -971,22 +984,19 @@ int launch_mfma_th(const void* feats, int64_t n_rows, int64_t fstride, int D, co
 inline bool split_wanted(int D, const Knobs& kn) { return D % 16 == 0 && kn.q_split; }
 
 template <int EPI, int FT, int TILES>
-int launch_mfma_t(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int64_t out_stride,
-                  int out_col0, const TopkArgs& tk) {
-  const bool split = split_wanted(D, kn);
+int launch_mfma_t(const ScanArgs& a, const Knobs& kn) {
+  const bool split = split_wanted(a.D, kn);
   // (the split scan's label rows take the bytes of the fp32 rows -- two fp16 pieces per value -- plus a scale per label)
-  const size_t shmem = (size_t)TILES * 32 * (D + 4) * sizeof(float) + (split ? (size_t)TILES * 32 * sizeof(float) : 0);
+  const size_t shmem = (size_t)TILES * 32 * (a.D + 4) * sizeof(float) + (split ? (size_t)TILES * 32 * sizeof(float) : 0);
   const int per_cu = (int)((160 * 1024) / (shmem + 256)) > 2 ? 2 : (int)((160 * 1024) / (shmem + 256));
   // SAF_Q_THREADS: 256 or 512 threads per workgroup whatever the tiles leave room for
   const bool wide = kn.q_threads ? kn.q_threads == 512 : per_cu <= 1;
-#define SAF_Q_GO(TH, SP) launch_mfma_th<EPI, FT, TILES, TH, SP>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, per_cu, shmem, s, out_stride, out_col0, tk)
   // a 16-bit volume whose rows lie on 16-byte boundaries: one load per k-step in the matrix instruction's layout, one piece per feature
   // (SAF_Q_SPLIT16=0: through the fp32 form)
-  if (split && FT != SAF_F32 && fstride % 8 == 0 && kn.q_split16) return wide ? SAF_Q_GO(512, 2) : SAF_Q_GO(256, 2);
-  if (split) return wide ? SAF_Q_GO(512, 1) : SAF_Q_GO(256, 1);
-  return wide ? SAF_Q_GO(512, 0) : SAF_Q_GO(256, 0);
-#undef SAF_Q_GO
+  if (split && FT != SAF_F32 && a.fstride % 8 == 0 && kn.q_split16)
+    return wide ? launch_mfma_th<EPI, FT, TILES, 512, 2>(a, per_cu, shmem) : launch_mfma_th<EPI, FT, TILES, 256, 2>(a, per_cu, shmem);
+  if (split) return wide ? launch_mfma_th<EPI, FT, TILES, 512, 1>(a, per_cu, shmem) : launch_mfma_th<EPI, FT, TILES, 256, 1>(a, per_cu, shmem);
+  return wide ? launch_mfma_th<EPI, FT, TILES, 512, 0>(a, per_cu, shmem) : launch_mfma_th<EPI, FT, TILES, 256, 0>(a, per_cu, shmem);
 }
 
 // true if the MFMA scan can take this shape
@@ -998,28 +1008,13 @@ inline bool mfma_ok(int ft, int64_t fstride, int D, int L, const void* feats) {
   return shmem <= 150 * 1024;
 }
 
-template <int EPI, int FT>
-int launch_mfma_f(const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                  float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int64_t out_stride,
-                  int out_col0, const TopkArgs& tk) {
-  return L > 32 ? launch_mfma_t<EPI, FT, 2>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, kn, out_stride, out_col0, tk)
-                : launch_mfma_t<EPI, FT, 1>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out,
-                                            out_last, s, kn, out_stride, out_col0, tk);
-}
-
+// the matrix scans (mfma_ok): one or two tiles of 32 labels
 template <int EPI>
-int launch_mfma(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L,
-                int64_t tstride, float scale, int normalize, const float* wts, float* out, float* out_last,
-                hipStream_t s, const Knobs& kn, int64_t out_stride = 0, int out_col0 = 0, const TopkArgs& tk = TopkArgs{}) {
-  switch (ft) {
-    case SAF_BF16:
-      return launch_mfma_f<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
-    case SAF_F16:
-      return launch_mfma_f<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
-    default:
-      return launch_mfma_f<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s, kn, out_stride, out_col0, tk);
-  }
+int launch_mfma(const ScanArgs& a, const Knobs& kn) {
+  return dispatch_ft(a.ft, [&](auto ft) {
+    constexpr int FT = decltype(ft)::value;
+    return a.L > 32 ? launch_mfma_t<EPI, FT, 2>(a, kn) : launch_mfma_t<EPI, FT, 1>(a, kn);
+  });
 }
 
 // More than 64 labels (round 6; the reference's control set grows by one label per new query text, clip_seem_fusion.py:496-505):
@@ -1035,10 +1030,10 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(float* __restrict__ ou
     if (EPI == SAF_Q_SOFTMAX) {
       float mx = -INFINITY;
       for (int c = lane; c < L; c += 64) mx = fmaxf(mx, row[c]);
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      mx = wave_max(mx);
       float sum = 0.0f;
       for (int c = lane; c < L; c += 64) sum += expf(row[c] - mx);
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+      sum = wave_sum(sum);
       for (int c = lane; c < L; c += 64) {
         const float v = expf(row[c] - mx) / sum;
         row[c] = v;
@@ -1047,8 +1042,7 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(float* __restrict__ ou
     } else {  // surgery: minus the row's mean over the labels
       float sum = 0.0f;
       for (int c = lane; c < L; c += 64) sum += row[c];
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-      const float mean = sum / (float)L;
+      const float mean = wave_sum(sum) / (float)L;
       for (int c = lane; c < L; c += 64) {
         const float v = row[c] - mean;
         row[c] = v;
@@ -1059,37 +1053,30 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(float* __restrict__ ou
 }
 
 template <int EPI>
-int launch_mfma_blocks(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                       float scale, int normalize, const float* wts, float* out, float* out_last, hipStream_t s, const Knobs& kn, int bw) {
+int launch_mfma_blocks(const ScanArgs& a, const Knobs& kn, int bw) {
   // bw: labels per block -- 64, or 32 where two 32-label tiles of this width do not fit the LDS (feat_dim 768 / 1024: round 6)
-  for (int c0 = 0; c0 < L; c0 += bw) {
-    const int lb = L - c0 < bw ? L - c0 : bw;
+  for (int c0 = 0; c0 < a.L; c0 += bw) {
+    ScanArgs b = a;
+    b.L = a.L - c0 < bw ? a.L - c0 : bw;
+    b.text = a.text + (int64_t)c0 * a.tstride;
+    b.wts = a.wts ? a.wts + c0 : nullptr;
     // (raw scores are final as a block stores them: the launch that holds column L - 1 -- the last column of ITS block -- writes
     //  out_last; softmax and surgery take it from the finishing pass)
-    float* last = EPI == SAF_Q_SCORES && c0 + lb == L ? out_last : nullptr;
-    int rc = launch_mfma<SAF_Q_SCORES>(ft, feats, n_rows, fstride, D, text + (int64_t)c0 * tstride, lb, tstride, scale, normalize,
-                                       wts ? wts + c0 : nullptr, out, last, s, kn, (int64_t)L, c0);
-    if (rc) return rc;
+    b.out_last = EPI == SAF_Q_SCORES && c0 + b.L == a.L ? a.out_last : nullptr;
+    b.out_stride = a.L;
+    b.out_col0 = c0;
+    if (int rc = launch_mfma<SAF_Q_SCORES>(b, kn)) return rc;
   }
   if (EPI == SAF_Q_SCORES) return SAF_OK;
-  int64_t blocks = (n_rows + 3) / 4;
-  const int64_t cap = (int64_t)device_cus() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(finish_rows_kernel<EPI>, dim3((unsigned)blocks), dim3(256), 0, s, out, n_rows, L, out_last);
+  hipLaunchKernelGGL(finish_rows_kernel<EPI>, dim3(grid_1d(a.n_rows, 16, 4)), dim3(256), 0, a.s, a.out, a.n_rows, a.L, a.out_last);
   return check_launch("finish_rows_kernel");
 }
 
+// The route of a scan: blocks of `bw` labels on the matrix scan, the matrix scan once, or one wave per row.
 template <int EPI>
-int launch(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-           float scale, int normalize, float* wts, float* out, float* out_last, hipStream_t s) {
-  switch (ft) {
-    case SAF_BF16:
-      return launch_t<EPI, SAF_BF16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s);
-    case SAF_F16:
-      return launch_t<EPI, SAF_F16>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s);
-    default:
-      return launch_t<EPI, SAF_F32>(feats, n_rows, fstride, D, text, L, tstride, scale, normalize, wts, out, out_last, s);
-  }
+int scan(const ScanArgs& a, const Knobs& kn, bool mfma, int bw) {
+  if (bw) return launch_mfma_blocks<EPI>(a, kn, bw);
+  return mfma ? launch_mfma<EPI>(a, kn) : launch<EPI>(a);
 }
 
 // Top-k for shapes the matrix scans do not take (feat_dim % 8 != 0, unaligned rows): one wave per row as query_kernel, the row's
@@ -1107,33 +1094,7 @@ __global__ __launch_bounds__(kQThreads) void topk_rows_kernel(const void* __rest
   for (int64_t r0 = (int64_t)blockIdx.x * kQWaves; r0 < n_rows; r0 += (int64_t)gridDim.x * kQWaves) {
     const int64_t r = r0 + wave;
     const bool active = r < n_rows;
-    if (active) {
-      float ss = 0.f;
-      for (int c = lane; c < D; c += 64) {
-        const float x = load_feat<FT>(feats, r * fstride + c);
-        row[c] = x;
-        ss += x * x;
-      }
-      if (normalize) {
-        float norm = sqrtf(wave_sum(ss));
-        if (normalize == SAF_NORM_L2_CLAMP) norm = norm < 0.1f ? 0.1f : norm;
-        for (int c = lane; c < D; c += 64) {
-          float q = row[c] / norm;
-          if (normalize == SAF_NORM_L2) {
-            if (q != q) q = 0.f;
-            if (__builtin_isinf(q)) q = q > 0.f ? 3.4028234663852886e38f : -3.4028234663852886e38f;
-          }
-          row[c] = q;
-        }
-      }
-      for (int l = 0; l < L; ++l) {
-        const float* t = text + (int64_t)l * tstride;
-        float acc = 0.f;
-        for (int c = lane; c < D; c += 64) acc = __builtin_fmaf(row[c], t[c], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) sc[l] = scale * acc;
-      }
-    }
+    if (active) row_scores<FT, true>(feats, r, fstride, D, text, L, tstride, scale, normalize, row, sc, lane);
     __syncthreads();  // sc[] written by lane 0, read by all lanes below
     if (active) {
       float mx = -INFINITY;
@@ -1170,21 +1131,13 @@ __global__ __launch_bounds__(kQThreads) void topk_rows_kernel(const void* __rest
   }
 }
 
-int launch_topk_rows(int ft, const void* feats, int64_t n_rows, int64_t fstride, int D, const float* text, int L, int64_t tstride,
-                     float scale, int normalize, int k, int* out_index, float* out_prob, hipStream_t s) {
-  const size_t shmem = (size_t)kQWaves * (((D + 3) & ~3) + ((L + 3) & ~3)) * sizeof(float);
+int launch_topk_rows(const ScanArgs& a) {
+  const size_t shmem = (size_t)kQWaves * (((a.D + 3) & ~3) + ((a.L + 3) & ~3)) * sizeof(float);
   if (shmem > 150 * 1024) return fail(SAF_E_UNSUPPORTED, "query top-k: feat_dim + n_text too large (%zu B LDS)", shmem);
-  auto fn = ft == SAF_BF16 ? topk_rows_kernel<SAF_BF16> : ft == SAF_F16 ? topk_rows_kernel<SAF_F16> : topk_rows_kernel<SAF_F32>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  int64_t blocks = (n_rows + kQWaves - 1) / kQWaves;
-  const int64_t cap = (int64_t)device_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kQThreads), shmem, s, feats, n_rows, fstride, D, text, L, tstride, scale,
-                     normalize, k, out_index, out_prob);
+  auto fn = a.ft == SAF_BF16 ? topk_rows_kernel<SAF_BF16> : a.ft == SAF_F16 ? topk_rows_kernel<SAF_F16> : topk_rows_kernel<SAF_F32>;
+  if (int rc = allow_lds(fn, shmem)) return rc;
+  hipLaunchKernelGGL(fn, dim3(grid_1d(a.n_rows, 8, kQWaves)), dim3(kQThreads), shmem, a.s, a.feats, a.n_rows, a.fstride, a.D, a.text,
+                     a.L, a.tstride, a.scale, a.normalize, a.tk.k, a.tk.out_index, a.tk.out_prob);
   return check_launch("topk_rows_kernel");
 }
 
@@ -1216,8 +1169,20 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
     return fail(SAF_E_INVALID, "query scan: bad arguments");
   if (!out && !out_last) return fail(SAF_E_INVALID, "query scan: no output buffer");
   if (n_rows == 0) return SAF_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const void* f = feats;
+  ScanArgs a;
+  a.ft = feat_dtype;
+  a.feats = feats;
+  a.n_rows = n_rows;
+  a.fstride = feat_stride;
+  a.D = feat_dim;
+  a.text = text;
+  a.L = n_text;
+  a.tstride = text_stride;
+  a.scale = scale;
+  a.normalize = normalize;
+  a.out = out;
+  a.out_last = out_last;
+  a.s = static_cast<hipStream_t>(stream);
   const int ft = feat_dtype;
   const bool mfma = mfma_ok(ft, feat_stride, feat_dim, n_text, feats);
   // more than 64 labels: block by block on the MFMA scan where it takes a 64-label block of this shape and the caller wants the
@@ -1227,43 +1192,21 @@ int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
   const int bw = mfma || out == nullptr ? 0
                  : (n_text > 64 && mfma_ok(ft, feat_stride, feat_dim, 64, feats)) ? 64
                  : (n_text > 32 && mfma_ok(ft, feat_stride, feat_dim, 32, feats)) ? 32 : 0;
-  const bool blocks = bw != 0;
   const Knobs kn = read_knobs();
   switch (epilogue) {
-    case SAF_Q_SCORES:
-      if (blocks)
-        return launch_mfma_blocks<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                                nullptr, out, out_last, s, kn, bw);
-      if (mfma)
-        return launch_mfma<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale,
-                                         normalize, nullptr, out, out_last, s, kn);
-      return launch<SAF_Q_SCORES>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                  nullptr, out, out_last, s);
-    case SAF_Q_SOFTMAX:
-      if (blocks)
-        return launch_mfma_blocks<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                                 nullptr, out, out_last, s, kn, bw);
-      if (mfma)
-        return launch_mfma<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale,
-                                          normalize, nullptr, out, out_last, s, kn);
-      return launch<SAF_Q_SOFTMAX>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize,
-                                   nullptr, out, out_last, s);
+    case SAF_Q_SCORES: return scan<SAF_Q_SCORES>(a, kn, mfma, bw);
+    case SAF_Q_SOFTMAX: return scan<SAF_Q_SOFTMAX>(a, kn, mfma, bw);
     case SAF_Q_SURGERY: {
       if (!workspace || workspace_bytes < saf_query_workspace_bytes(n_text, epilogue))
         return fail(SAF_E_WORKSPACE, "query scan: surgery needs %zu bytes of workspace",
                     saf_query_workspace_bytes(n_text, epilogue));
-      float* wts = static_cast<float*>(workspace);
-      int rc = launch<EPI_WEIGHTS>(ft, f, 1, feat_stride, feat_dim, text, n_text, text_stride, 1.0f, normalize, wts,
-                                   nullptr, nullptr, s);
-      if (rc) return rc;
-      if (blocks)
-        return launch_mfma_blocks<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f, normalize,
-                                                 wts, out, out_last, s, kn, bw);
-      if (mfma)
-        return launch_mfma<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f,
-                                          normalize, wts, out, out_last, s, kn);
-      return launch<SAF_Q_SURGERY>(ft, f, n_rows, feat_stride, feat_dim, text, n_text, text_stride, 1.0f, normalize, wts,
-                                   out, out_last, s);
+      a.wts = static_cast<float*>(workspace);
+      a.scale = 1.0f;
+      ScanArgs first = a;  // the weights: from row 0
+      first.n_rows = 1;
+      first.out = first.out_last = nullptr;
+      if (int rc = launch<EPI_WEIGHTS>(first)) return rc;
+      return scan<SAF_Q_SURGERY>(a, kn, mfma, bw);
     }
     default:
       return fail(SAF_E_INVALID, "query scan: unknown epilogue %d", epilogue);
@@ -1286,16 +1229,25 @@ int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
     return fail(SAF_E_INVALID, "query top-k: bad arguments");
   if (k < 1 || k > kTopkMax || k > n_text) return fail(SAF_E_INVALID, "query top-k: k = %d (1 <= k <= min(8, n_text = %d))", k, n_text);
   if (n_rows == 0) return SAF_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int bw = topk_block(feat_dtype, feat_stride, feat_dim, feats);
-  if (bw == 0)
-    return launch_topk_rows(feat_dtype, feats, n_rows, feat_stride, feat_dim, text, n_text, text_stride, scale, normalize, k,
-                            out_index, out_prob, s);
-  const Knobs kn = read_knobs();
-  TopkArgs tk;
+  ScanArgs a;
+  a.ft = feat_dtype;
+  a.feats = feats;
+  a.n_rows = n_rows;
+  a.fstride = feat_stride;
+  a.D = feat_dim;
+  a.text = text;
+  a.L = n_text;
+  a.tstride = text_stride;
+  a.scale = scale;
+  a.normalize = normalize;
+  a.s = static_cast<hipStream_t>(stream);
+  TopkArgs& tk = a.tk;
   tk.k = k;
   tk.out_index = out_index;
   tk.out_prob = out_prob;
+  const int bw = topk_block(feat_dtype, feat_stride, feat_dim, feats);
+  if (bw == 0) return launch_topk_rows(a);
+  const Knobs kn = read_knobs();
   if (n_text > bw) {
     const size_t need = saf_query_topk_workspace_bytes(n_rows, n_text, k);
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255))
@@ -1310,13 +1262,13 @@ int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_
     tk.st_sum = reinterpret_cast<float*>(w);
   }
   for (int c0 = 0; c0 < n_text; c0 += bw) {
-    const int lb = n_text - c0 < bw ? n_text - c0 : bw;
-    tk.col0 = c0;
-    tk.first = c0 == 0;
-    tk.last = c0 + lb >= n_text;
-    const int rc = launch_mfma<EPI_TOPK>(feat_dtype, feats, n_rows, feat_stride, feat_dim, text + (int64_t)c0 * text_stride, lb,
-                                         text_stride, scale, normalize, nullptr, nullptr, nullptr, s, kn, 0, 0, tk);
-    if (rc) return rc;
+    ScanArgs b = a;
+    b.L = n_text - c0 < bw ? n_text - c0 : bw;
+    b.text = text + (int64_t)c0 * text_stride;
+    b.tk.col0 = c0;
+    b.tk.first = c0 == 0;
+    b.tk.last = c0 + b.L >= n_text;
+    if (int rc = launch_mfma<EPI_TOPK>(b, kn)) return rc;
   }
   return SAF_OK;
 }

@@ -1452,15 +1452,8 @@ int launch_wide(const uint16_t* feats, int64_t n_rows, int64_t fstride, const ui
                 float scale, int normalize, void* out, int64_t ostride, hipStream_t s) {
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16);
   auto fn = query_wide_kernel<FT, OT, KS>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  int64_t blocks = (n_rows + 32 * kWWaves - 1) / (32 * kWWaves);
-  const int64_t cap = device_cus();
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(kWThreads), shmem, s, feats, n_rows, fstride, text16, Q, Qpad,
+  if (int rc = allow_lds(fn, shmem)) return rc;
+  hipLaunchKernelGGL(fn, dim3(grid_1d(n_rows, 1, 32 * kWWaves)), dim3(kWThreads), shmem, s, feats, n_rows, fstride, text16, Q, Qpad,
                      scale, normalize, out, ostride);
   return check_launch("query_wide_kernel");
 }
@@ -1491,16 +1484,9 @@ template <int FT, int OT, int KS, int EPI, int NF, int TH>
 int launch_wide2_nf(const Wide2Args& wa, hipStream_t s) {
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16) + (EPI == SAF_QW_QUERY_MAX ? (TH / 64) * 32 * NF * sizeof(float) : 0);
   auto fn = query_wide2_kernel<FT, OT, KS, EPI, NF, TH>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  const int64_t rows_per_wg = (TH / 64) * 32 * NF;
-  int64_t blocks = (wa.n_rows + rows_per_wg - 1) / rows_per_wg;
-  const int64_t cap = (int64_t)device_cus() * (NF == 1 && TH == 256 ? 2 : 1);  // persistent: one or two workgroups per CU
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(TH), shmem, s, wa);
+  if (int rc = allow_lds(fn, shmem)) return rc;
+  // persistent: one or two workgroups per CU
+  hipLaunchKernelGGL(fn, dim3(grid_1d(wa.n_rows, NF == 1 && TH == 256 ? 2 : 1, (TH / 64) * 32 * NF)), dim3(TH), shmem, s, wa);
   return check_launch("query_wide2_kernel");
 }
 
@@ -1511,15 +1497,8 @@ int launch_wide3(const Wide2Args& wa, hipStream_t s) {
                            ((KS == 32 && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 8 * 11 * 1024 : 0) +
                            ((SAF_W3_PAIR == 1 && EPI == SAF_QW_VS_BACKGROUND && OT != SAF_F32) ? 8 * 4096 : 0);
   auto fn = query_wide3_kernel<FT, OT, KS, EPI>;
-  if (shmem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  const int64_t rows_per_wg = 8 * 32;
-  int64_t blocks = (wa.n_rows + rows_per_wg - 1) / rows_per_wg;
-  const int64_t cap = (int64_t)device_cus();  // persistent: one workgroup per CU
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(512), shmem, s, wa);
+  if (int rc = allow_lds(fn, shmem)) return rc;
+  hipLaunchKernelGGL(fn, dim3(grid_1d(wa.n_rows, 1, 8 * 32)), dim3(512), shmem, s, wa);  // persistent: one workgroup per CU
   return check_launch("query_wide3_kernel");
 }
 

@@ -127,15 +127,28 @@ def test_split_scan_rows_of_any_magnitude():
     assert (np.abs(got - want) <= bound).all(), float((np.abs(got - want) / bound).max())
 
 
-@pytest.mark.parametrize("d", [16, 48, 80, 528, 1024])
+@pytest.mark.parametrize("d", [16, 48, 80, 192, 336, 528, 1024])
 def test_split_scan_other_widths(d):
-    """feat_dim a multiple of 16 but not of 64: the pairs behind the last full group; no full group at all"""
+    """feat_dim a multiple of 16 but not of 64: the pairs behind the last full group; no full group at all; an odd number of
+    64-feature groups (192: three, the conditional ring with a group in flight; 336: five and a trailing pair)"""
     n, nl = 1000, 37
     g = torch.Generator().manual_seed(d)
     feats = torch.randn((n, d), generator=g)
     feats[:, d // 2:] *= 300.0
     text = torch.randn((nl, d), generator=g)
     _check_raw(feats, text, f"D = {d}")
+
+
+@pytest.mark.parametrize("d", [8, 72, 200, 520])
+def test_exact_fp32_scan_other_widths(d):
+    """feat_dim a multiple of 8 but not of 16: the split scan does not take it, the exact-fp32 matrix scan (query_mfma_kernel) does
+    by default -- no 64-feature group at all, one / three / eight groups and a chunk of 8 behind them; both label tiles"""
+    n, nl = 1000, 37
+    g = torch.Generator().manual_seed(d)
+    feats = torch.randn((n, d), generator=g)
+    feats[:, d // 2:] *= 300.0
+    text = torch.randn((nl, d), generator=g)
+    _check_raw(feats, text, f"exact fp32, D = {d}")
 
 
 def test_split_scan_strided_rows_and_non_finite():
@@ -242,10 +255,11 @@ def test_split_scan_16bit_volumes_of_any_magnitude(fdt):
 
 
 @pytest.mark.parametrize("fdt", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("d", [16, 144, 272, 1024])
+@pytest.mark.parametrize("d", [16, 144, 272, 384, 400, 1024])
 def test_split_scan_16bit_other_widths(fdt, d):
     """16-bit volumes whose rows are not a whole number of 128-feature groups (no group at all; one group and a k-step; two groups --
-    the ring with unconditional loads -- and a k-step behind them) and 1024 channels"""
+    the ring with unconditional loads -- and a k-step behind them; three groups -- the conditional ring with a group in flight --
+    alone and with a k-step behind them) and 1024 channels"""
     n, nl = 777, 29
     g = torch.Generator().manual_seed(d)
     feats = (torch.randn((n, d), generator=g) * 3.0).to(fdt)
