@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/saf.h"
 #include "saf_knobs.h"
 
@@ -52,6 +54,33 @@ inline int allow_lds(K* kernel, size_t bytes) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", bytes, hipGetErrorString(e));
   return SAF_OK;
+}
+
+// One template argument from a run-time element type: f(std::integral_constant<int, DT>{}), so that `decltype(dt)::value` names the
+// instantiation.  dispatch_ft: a feature dtype the entry point has checked (anything else counts as SAF_F32); dispatch_ft16: one it
+// has checked to be 16-bit; dispatch_dtype: an unchecked one -- for any other value the caller's refusal `bad()` is the result.
+// (The order of the cases is the order in which a file's kernels are instantiated and so laid out in its code object: a launch
+//  switch whose cases stand in another order -- clip_tiles, dwconv7x7 -- keeps its kernels' order only by staying a switch.)
+template <typename F>
+int dispatch_ft(int ft, F&& f) {
+  switch (ft) {
+    case SAF_BF16: return f(std::integral_constant<int, SAF_BF16>{});
+    case SAF_F16: return f(std::integral_constant<int, SAF_F16>{});
+    default: return f(std::integral_constant<int, SAF_F32>{});
+  }
+}
+template <typename F>
+int dispatch_ft16(int ft, F&& f) {
+  return ft == SAF_BF16 ? f(std::integral_constant<int, SAF_BF16>{}) : f(std::integral_constant<int, SAF_F16>{});
+}
+template <typename F, typename Bad>
+int dispatch_dtype(int dt, F&& f, Bad&& bad) {
+  switch (dt) {
+    case SAF_F32: return f(std::integral_constant<int, SAF_F32>{});
+    case SAF_F16: return f(std::integral_constant<int, SAF_F16>{});
+    case SAF_BF16: return f(std::integral_constant<int, SAF_BF16>{});
+    default: return bad();
+  }
 }
 
 // A volume that the field readers (saf_field_dev.h) can use: two voxels per axis for a cell, int32 voxel indices, and the tsdf,

@@ -415,19 +415,12 @@ int saf_sample_vertices(const saf_volume* vol, const float* verts_index, int64_t
   if (n_verts == 0) return SAF_OK;
   const unsigned blocks = grid_1d(n_verts, 8, 4);  // one wave per vertex
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (vol->feat_dtype == SAF_BF16)
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_BF16>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
+  return dispatch_ft(vol->feat_dtype, [&](auto ft) {
+    hipLaunchKernelGGL(sample_vertices_kernel<decltype(ft)::value>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
                        vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
                        seg_color, out_seg);
-  else if (vol->feat_dtype == SAF_F16)
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F16>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
-                       vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
-                       seg_color, out_seg);
-  else
-    hipLaunchKernelGGL(sample_vertices_kernel<SAF_F32>, dim3(blocks), dim3(256), 0, s, vol->nx, vol->ny, vol->nz,
-                       vol->feat_dim, vol->clip_feat, vol->rgb, verts_index, n_verts, out_feat, out_rgb, obj_idx, out_obj,
-                       seg_color, out_seg);
-  return check_launch("sample_vertices_kernel");
+    return check_launch("sample_vertices_kernel");
+  });
 }
 
 int saf_label_argmax(const int32_t* labels_one_hot, int64_t n_vox, int32_t n_classes, int32_t* out, void* stream) {

@@ -938,16 +938,6 @@ struct ScanArgs {
   hipStream_t s = nullptr;
 };
 
-// f(std::integral_constant<int, FT>{}) for the feature dtype (checked by the entry points)
-template <typename F>
-int dispatch_ft(int ft, F&& f) {
-  switch (ft) {
-    case SAF_BF16: return f(std::integral_constant<int, SAF_BF16>{});
-    case SAF_F16: return f(std::integral_constant<int, SAF_F16>{});
-    default: return f(std::integral_constant<int, SAF_F32>{});
-  }
-}
-
 // one wave per row (query_kernel): any shape
 template <int EPI>
 int launch(const ScanArgs& a) {

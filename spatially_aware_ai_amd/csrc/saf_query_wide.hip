@@ -28,22 +28,6 @@ constexpr int kWThreads = 512;
 constexpr int kWWaves = kWThreads / 64;
 constexpr int kWTile = 32;  // queries per LDS tile
 
-// fp32 text [Q][tstride] -> 16-bit [Qpad][D] (rows >= Q zero)
-template <int FT>
-__global__ void text_to_16_kernel(const float* __restrict__ text, int Q, int64_t tstride, int D, int Qpad,
-                                  uint16_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Qpad * D) return;
-  const int q = i / D, k = i - q * D;
-  const float v = q < Q ? text[(int64_t)q * tstride + k] : 0.0f;
-  if (FT == SAF_BF16) {
-    out[i] = (uint16_t)f32_to_bf16_bits(v);
-  } else {
-    const _Float16 hv = (_Float16)v;
-    out[i] = __builtin_bit_cast(uint16_t, hv);
-  }
-}
-
 template <int FT>
 __device__ __forceinline__ float elem16_to_f32(uint16_t b) {
   if (FT == SAF_BF16) return __builtin_bit_cast(float, (uint32_t)b << 16);
@@ -61,6 +45,12 @@ __device__ __forceinline__ float dot2_self(uint32_t w, float acc) {
   typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
   const h2_t v = __builtin_bit_cast(h2_t, w);
   return __builtin_amdgcn_fdot2(v, v, acc, false);
+}
+
+// scale / row norm from the row's sum of squares.  SAF_NORM_L2_CLAMP: norm.clamp_min(0.1); SAF_NORM_L2 with nan_to_num: an all-zero
+// row scores 0
+__device__ __forceinline__ float row_inv(int normalize, float scale, float ss) {
+  return normalize == SAF_NORM_L2_CLAMP ? scale / fmaxf(sqrtf(ss), 0.1f) : (ss > 0.0f ? scale / sqrtf(ss) : 0.0f);
 }
 
 template <int OT>
@@ -82,20 +72,25 @@ __device__ __forceinline__ f32x16_t mfma16(const uint4& a, const uint4& b, const
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
 }
 
+// Four scores as four 16-bit values of the output dtype (the fused scans exchange two of these between the half-waves: lanes
+// 0-31 then hold queries 8 g .. 8 g + 7 and lanes 32-63 queries 8 g + 8 .. 8 g + 15 of their row, T21)
+template <int OT>
+__device__ __forceinline__ uint2 pack4_16(float v0, float v1, float v2, float v3) {
+  if (OT == SAF_BF16) return make_uint2(pack_bf16(v0, v1), pack_bf16(v2, v3));
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  h2 a, b;
+  a.x = (_Float16)v0; a.y = (_Float16)v1; b.x = (_Float16)v2; b.y = (_Float16)v3;
+  return make_uint2(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b));
+}
+
 // Four consecutive scores of one feature row -> one 8-byte (16-bit out) or 16-byte (fp32 out) store.
 template <int OT>
 __device__ __forceinline__ void store_scores4(void* __restrict__ out, int64_t idx, float v0, float v1, float v2,
                                               float v3) {
   if (OT == SAF_F32) {
     *reinterpret_cast<float4*>(static_cast<float*>(out) + idx) = make_float4(v0, v1, v2, v3);
-  } else if (OT == SAF_BF16) {
-    *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + idx) = make_uint2(pack_bf16(v0, v1), pack_bf16(v2, v3));
   } else {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 a, b;
-    a.x = (_Float16)v0; a.y = (_Float16)v1; b.x = (_Float16)v2; b.y = (_Float16)v3;
-    *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + idx) =
-        make_uint2(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b));
+    *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + idx) = pack4_16<OT>(v0, v1, v2, v3);
   }
 }
 
@@ -146,8 +141,7 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         }
       }
       ss += __shfl_xor(ss, 32);                              // both halves of row r
-      // SAF_NORM_L2: nan_to_num, an all-zero row scores 0; SAF_NORM_L2_CLAMP: norm.clamp_min(0.1)
-      inv = normalize == SAF_NORM_L2_CLAMP ? scale / fmaxf(sqrtf(ss), 0.1f) : (ss > 0.0f ? scale / sqrtf(ss) : 0.0f);
+      inv = row_inv(normalize, scale, ss);
       // SAF_NORM_L2, a row with an inf or a NaN in it (ss is inf or NaN in both of its lanes): nan_to_num gives the all-zero row
       if (normalize == SAF_NORM_L2 && !(ss < INFINITY)) {
 #pragma unroll
@@ -310,18 +304,22 @@ __device__ __forceinline__ float from_ordered_bits(uint32_t o) {
   return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-// 8 consecutive 16-bit scores per lane from the two half-waves' groups g (even) and g + 1: after the exchange
-// lanes 0-31 hold queries 8 g .. 8 g + 7 and lanes 32-63 queries 8 g + 8 .. 8 g + 15 of their row (T21).
-template <int OT>
-__device__ __forceinline__ uint2 pack4_16(float v0, float v1, float v2, float v3) {
-  if (OT == SAF_BF16) return make_uint2(pack_bf16(v0, v1), pack_bf16(v2, v3));
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  h2 a, b;
-  a.x = (_Float16)v0; a.y = (_Float16)v1; b.x = (_Float16)v2; b.y = (_Float16)v3;
-  return make_uint2(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b));
+// softmax([backgrounds..., target])[-1] = 1 / (1 + exp(lse - z)), z = raw * inv, as 1 / (1 + 2^(raw ka + kb)) with the row's
+// ka = -inv log2(e), kb = lse log2(e); query_mesh.py:39's ((p - 0.5) * 2).clamp(0, 1) is clamp(2 p - 1): one FMA whose constants the
+// flag picks (p itself lies in (0, 1]: the clamp is harmless without the rescale).  Six vector instructions per score.  The ONE
+// definition for both kernels' epilogues and pieces: interior and edge tiles of one output agree bit for bit.
+constexpr float kLog2e = 1.4426950408889634f;
+__device__ __forceinline__ float vs_bg_prob(float raw, float ka, float kb, bool rescale) {
+  const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(raw, ka, kb)));
+  return __builtin_amdgcn_fmed3f(__builtin_fmaf(p, rescale ? 2.0f : 1.0f, rescale ? -1.0f : 0.0f), 0.0f, 1.0f);
 }
 
-struct Wide2Args {
+// QUERY_MAX's key of a score and its row (low 32 bits): ordered(score) << 32 | ~row -- the larger score wins, then the smaller row
+__device__ __forceinline__ unsigned long long qmax_key(float best, uint32_t row) {
+  return ((unsigned long long)ordered_bits(best) << 32) | (uint32_t)~row;
+}
+
+struct WideArgs {
   const uint16_t* feats;
   int64_t n_rows, fstride;
   const uint16_t* text16;  // [Qpad][D]; VS_BACKGROUND: tile 0 = backgrounds (zero padded), targets from tile 1
@@ -336,6 +334,43 @@ struct Wide2Args {
   int64_t row_offset;
   int safe_wait;  // SAF_W2_SAFE_WAIT=1 (read per call): vmcnt(0) in front of every tile's barrier instead of the counted wait
 };
+
+// One fragment's rows at a block change: the factor (scale / norm, or scale) of the lane's row from its registers a[0..N), and what
+// becomes of a row with an inf or a NaN in it (its sum of squares is inf or NaN in every lane of the row: two lanes, QUAD: four).
+// SAF_NORM_L2: nan_to_num gives the all-zero row -- the registers are zeroed here, in every epilogue, once per row block instead
+// of a select per score; otherwise its scores are what IEEE gives and `bad` is set: the reductions keep NaN out of their chains
+// (W2Tile::bad).  `sums`: the caller needs the sum of squares (a norm is asked for, or a reduction looks at every row).
+// The squared norm: one v_dot2_f32_{f16,bf16} per pair of elements (exact products, fp32 sums) -- a quarter of the instructions of
+// widening and two FMAs per pair; two chains, added at the end.
+template <int FT, bool QUAD, int N>
+__device__ __forceinline__ float row_block_factor(uint4 (&a)[N], const WideArgs& wa, bool sums, bool& bad) {
+  float inv = wa.scale;
+  if (sums) {
+    float ss = 0.f, ss2 = 0.f;
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      const uint32_t w[4] = {a[s].x, a[s].y, a[s].z, a[s].w};
+#pragma unroll
+      for (int j = 0; j < 4; j += 2) {
+        ss = dot2_self<FT>(w[j], ss);
+        ss2 = dot2_self<FT>(w[j + 1], ss2);
+      }
+    }
+    ss += ss2;
+    if (QUAD) ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    if (wa.normalize) inv = row_inv(wa.normalize, wa.scale, ss);
+    if (!(ss < INFINITY)) {
+      if (wa.normalize == SAF_NORM_L2) {
+#pragma unroll
+        for (int s = 0; s < N; ++s) a[s] = make_uint4(0u, 0u, 0u, 0u);
+      } else {
+        bad = true;
+      }
+    }
+  }
+  return inv;
+}
 
 // What the epilogue of a tile needs to know about the tile (it runs one step later, beside the next tile's MFMAs,
 // possibly after the workgroup has moved on to its next row block).  NF = 32-row fragments per wave.
@@ -360,7 +395,7 @@ struct W2State {
 };
 
 template <int OT, int EPI, int NF>
-__device__ __forceinline__ void w2_epilogue(const Wide2Args& wa, const f32x16_t (&c)[NF], const W2Tile<NF>& t, W2State<NF>& st,
+__device__ __forceinline__ void w2_epilogue(const WideArgs& wa, const f32x16_t (&c)[NF], const W2Tile<NF>& t, W2State<NF>& st,
                                             int r, int h, int n_qt, bool vec_ok) {
   // lane (r, h): feature row t.row[f] in fragment f; register 4 g + i holds query qt*32 + 8 g + 4 h + i
   const int qbase = t.qt * kWTile + 4 * h;
@@ -389,10 +424,7 @@ __device__ __forceinline__ void w2_epilogue(const Wide2Args& wa, const f32x16_t 
           const bool rescale = (wa.flags & 1) != 0;  // query_mesh.py:39: ((r - 0.5) * 2).clamp(0, 1)
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            // (the same arithmetic as w2_fast_piece: interior and edge tiles of one output agree bit for bit)
-            const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(c[f][i], -t.inv[f] * 1.4426950408889634f,
-                                                                                                  st.lse[f] * 1.4426950408889634f)));
-            v[i] = __builtin_amdgcn_fmed3f(__builtin_fmaf(p, rescale ? 2.0f : 1.0f, rescale ? -1.0f : 0.0f), 0.0f, 1.0f);
+            v[i] = vs_bg_prob(c[f][i], -t.inv[f] * kLog2e, st.lse[f] * kLog2e, rescale);
           }
           col0 = qbase - kWTile;
         }
@@ -484,7 +516,7 @@ __device__ __forceinline__ void w2_epilogue(const Wide2Args& wa, const f32x16_t 
         if (x > bv) { bv = x; bm = m; }  // rows ascend: the first maximum stays
       }
     }
-    unsigned long long key = bv > -INFINITY ? ((unsigned long long)ordered_bits(bv) << 32) | (uint32_t) ~(uint32_t)(base + bm + wa.row_offset) : 0ull;
+    unsigned long long key = bv > -INFINITY ? qmax_key(bv, (uint32_t)(base + bm + wa.row_offset)) : 0ull;
     const unsigned long long other = __shfl_xor(key, 32);
     key = other > key ? other : key;
     if (h == 0 && q < wa.Q && key) atomicMax(&wa.qkeys[q], key);
@@ -506,7 +538,7 @@ struct W2Fast {
 };
 
 template <int OT, int EPI, int NF>
-__device__ __forceinline__ void w2_fast_piece(int i, const Wide2Args& wa, const f32x16_t (&c)[NF], const W2Tile<NF>& t,
+__device__ __forceinline__ void w2_fast_piece(int i, const WideArgs& wa, const f32x16_t (&c)[NF], const W2Tile<NF>& t,
                                               W2State<NF>& st, W2Fast<NF>& fs, int r, int h, int n_qt) {
   const int qbase = t.qt * kWTile + 4 * h;
   if (EPI == SAF_QW_SCORES || EPI == SAF_QW_VS_BACKGROUND) {
@@ -515,15 +547,11 @@ __device__ __forceinline__ void w2_fast_piece(int i, const Wide2Args& wa, const 
     for (int f = 0; f < NF; ++f) {
       float x;
       if (EPI == SAF_QW_VS_BACKGROUND) {
-        // 1 / (1 + exp(lse - z)), z = c * inv, as 1 / (1 + 2^(c ka + kb)) with the row's ka = -inv log2(e), kb = lse log2(e);
-        // query_mesh.py:39's ((p - 0.5) * 2).clamp(0, 1) is clamp(2 p - 1): one FMA whose constants the flag picks (p itself
-        // lies in (0, 1]: the clamp is harmless without the rescale).  Six vector instructions per score instead of eleven.
-        if (i == 0) {
-          fs.ka[f] = -t.inv[f] * 1.4426950408889634f;
-          fs.kb[f] = st.lse[f] * 1.4426950408889634f;
+        if (i == 0) {  // (vs_bg_prob's ka and kb of the row, once per tile)
+          fs.ka[f] = -t.inv[f] * kLog2e;
+          fs.kb[f] = st.lse[f] * kLog2e;
         }
-        const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(c[f][i], fs.ka[f], fs.kb[f])));
-        x = __builtin_amdgcn_fmed3f(__builtin_fmaf(p, rescale ? 2.0f : 1.0f, rescale ? -1.0f : 0.0f), 0.0f, 1.0f);
+        x = vs_bg_prob(c[f][i], fs.ka[f], fs.kb[f], rescale);
       } else {
         x = c[f][i] * t.inv[f];
       }
@@ -558,7 +586,7 @@ __device__ __forceinline__ void w2_fast_piece(int i, const Wide2Args& wa, const 
 // one waits at its barrier or loads its next rows, the other one has the matrix pipes).
 template <int FT, int OT, int KS, int EPI, int NF, int TH>
 __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(NF == 2 ? 1 : 2, NF == 2 ? 1 : 2))) void
-query_wide2_kernel(Wide2Args wa) {
+query_wide2_kernel(WideArgs wa) {
   constexpr int kThreads = TH, kWaves = kThreads / 64, kRows = 32 * NF;
   constexpr int D = KS * 16;
   constexpr int ROWB = D * 2 + 16;  // padded LDS row in bytes: the 16 lanes of a ds_read_b128 group hit distinct bank quads
@@ -627,40 +655,7 @@ query_wide2_kernel(Wide2Args wa) {
       }
       bool bad = false;
 #pragma unroll
-      for (int f = 0; f < NF; ++f) {
-        cur.inv[f] = wa.scale;
-        if (wa.normalize || kReduce) {  // (the reductions look at every row's sum of squares: W2Tile::bad)
-          // the row's squared norm: one v_dot2_f32_{f16,bf16} per pair of elements (exact products, fp32 sums) -- a quarter of the
-          // instructions of widening and two FMAs per pair; two chains, added at the end
-          float ss = 0.f, ss2 = 0.f;
-#pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            const uint32_t w[4] = {a[f][s].x, a[f][s].y, a[f][s].z, a[f][s].w};
-#pragma unroll
-            for (int j = 0; j < 4; j += 2) {
-              ss = dot2_self<FT>(w[j], ss);
-              ss2 = dot2_self<FT>(w[j + 1], ss2);
-            }
-          }
-          ss += ss2;
-          ss += __shfl_xor(ss, 32);
-          // SAF_NORM_L2_CLAMP: norm.clamp_min(0.1); SAF_NORM_L2 with nan_to_num: an all-zero row scores 0
-          if (wa.normalize)
-            cur.inv[f] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
-                                                           : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
-          // a row with an inf or a NaN in it (ss is inf or NaN in both of its lanes).  SAF_NORM_L2: nan_to_num gives the all-zero
-          // row -- in every epilogue, and once per row block instead of a select per score; otherwise its scores are what IEEE
-          // gives, and the reductions keep NaN out of their chains (W2Tile::bad)
-          if (!(ss < INFINITY)) {
-            if (wa.normalize == SAF_NORM_L2) {
-#pragma unroll
-              for (int s = 0; s < KS; ++s) a[f][s] = make_uint4(0u, 0u, 0u, 0u);
-            } else {
-              bad = true;
-            }
-          }
-        }
-      }
+      for (int f = 0; f < NF; ++f) cur.inv[f] = row_block_factor<FT, false>(a[f], wa, wa.normalize || kReduce, bad);
       cur.bad = kReduce && __any(bad);
     }
     cur.qt = qt;
@@ -810,8 +805,7 @@ query_wide2_kernel(Wide2Args wa) {
       tail_ops = EPI == SAF_QW_ROW_ARGMAX ? 0 : EPI == SAF_QW_QUERY_MAX ? 1 : NF * (OT == SAF_F32 ? 2 : 1);
       if (EPI == SAF_QW_QUERY_MAX) {  // the two halves of a query's rows, then one atomic instruction: 32 queries
         const uint32_t row = (uint32_t)(prev.row[0] - r + wa.row_offset) + (uint32_t)fs.bm + 4u * (uint32_t)h;
-        const uint32_t khi = ordered_bits(fs.bv), klo = ~row;
-        const unsigned long long key = ((unsigned long long)khi << 32) | klo;
+        const unsigned long long key = qmax_key(fs.bv, row);
         const unsigned long long other = __shfl_xor(key, 32);
         const unsigned long long best = other > key ? other : key;
         if (h == 0) atomicMax(&wa.qkeys[prev.qt * kWTile + r], best);
@@ -903,7 +897,7 @@ struct W3State {
 };
 
 template <int OT, int EPI>
-__device__ __forceinline__ void w3_epilogue(const Wide2Args& wa, const f32x4_t (&acc)[2][2], const W3Tile& t, W3State& st, int c,
+__device__ __forceinline__ void w3_epilogue(const WideArgs& wa, const f32x4_t (&acc)[2][2], const W3Tile& t, W3State& st, int c,
                                             int g, int n_qt, bool vec_ok) {
   const int qlane = t.qt * kWTile + 4 * g;  // the lane's first query of block qb = 0 (plain layout)
   if (EPI == SAF_QW_SCORES || EPI == SAF_QW_VS_BACKGROUND) {
@@ -936,12 +930,9 @@ __device__ __forceinline__ void w3_epilogue(const Wide2Args& wa, const f32x4_t (
           write = false;
         } else {
           const bool rescale = (wa.flags & 1) != 0;  // query_mesh.py:39: ((r - 0.5) * 2).clamp(0, 1)
-          const float ka = -t.inv[rb] * 1.4426950408889634f, kb = (rb == 0 ? st.lse0 : st.lse1) * 1.4426950408889634f;
+          const float ka = -t.inv[rb] * kLog2e, kb = (rb == 0 ? st.lse0 : st.lse1) * kLog2e;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(acc[rb][j >> 2][j & 3], ka, kb)));
-            v[j] = __builtin_amdgcn_fmed3f(__builtin_fmaf(p, rescale ? 2.0f : 1.0f, rescale ? -1.0f : 0.0f), 0.0f, 1.0f);
-          }
+          for (int j = 0; j < 8; ++j) v[j] = vs_bg_prob(acc[rb][j >> 2][j & 3], ka, kb, rescale);
           colt -= kWTile;
         }
       }
@@ -1033,7 +1024,7 @@ __device__ __forceinline__ void w3_epilogue(const Wide2Args& wa, const f32x4_t (
           if (x > bv) { bv = x; bm = m; }  // the lane's rows ascend: the first maximum stays
         }
       }
-      unsigned long long key = bv > -INFINITY ? ((unsigned long long)ordered_bits(bv) << 32) | (uint32_t) ~(uint32_t)(base + bm + wa.row_offset) : 0ull;
+      unsigned long long key = bv > -INFINITY ? qmax_key(bv, (uint32_t)(base + bm + wa.row_offset)) : 0ull;
 #pragma unroll
       for (int off = 16; off <= 32; off <<= 1) {
         const unsigned long long other = __shfl_xor(key, off);
@@ -1057,7 +1048,7 @@ struct W3Fast {
   uint32_t k0hi, k0lo;  // QUERY_MAX: query block 0's key, until block 1's is complete
 };
 template <int OT, int EPI>
-__device__ __forceinline__ void w3_piece(int k, const Wide2Args& wa, const f32x4_t (&pacc)[2][2], const W3Tile& t, W3State& st,
+__device__ __forceinline__ void w3_piece(int k, const WideArgs& wa, const f32x4_t (&pacc)[2][2], const W3Tile& t, W3State& st,
                                          W3Fast& fs, int c, int g) {
   if (EPI == SAF_QW_SCORES || EPI == SAF_QW_VS_BACKGROUND) {
     const int rb = k >> 3, j = k & 7;
@@ -1066,11 +1057,10 @@ __device__ __forceinline__ void w3_piece(int k, const Wide2Args& wa, const f32x4
     if (EPI == SAF_QW_VS_BACKGROUND) {
       const bool rescale = (wa.flags & 1) != 0;
       if (j == 0) {
-        fs.ka[rb] = -t.inv[rb] * 1.4426950408889634f;
-        fs.kb[rb] = (rb == 0 ? st.lse0 : st.lse1) * 1.4426950408889634f;
+        fs.ka[rb] = -t.inv[rb] * kLog2e;
+        fs.kb[rb] = (rb == 0 ? st.lse0 : st.lse1) * kLog2e;
       }
-      const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(raw, fs.ka[rb], fs.kb[rb])));
-      x = __builtin_amdgcn_fmed3f(__builtin_fmaf(p, rescale ? 2.0f : 1.0f, rescale ? -1.0f : 0.0f), 0.0f, 1.0f);
+      x = vs_bg_prob(raw, fs.ka[rb], fs.kb[rb], rescale);
     } else {
       x = raw * t.inv[rb];
     }
@@ -1176,7 +1166,7 @@ __device__ __forceinline__ void w3_piece(int k, const Wide2Args& wa, const f32x4
 }
 
 template <int FT, int OT, int KS, int EPI>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void query_wide3_kernel(Wide2Args wa) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void query_wide3_kernel(WideArgs wa) {
   constexpr int kThreads = 512, kWaves = 8, kRows = 32;
   constexpr int D = KS * 16, S = KS / 2;  // S k-steps of 32
   constexpr int ROWB = D * 2 + 16;        // padded LDS row: the 16 lanes of a fragment's row group hit distinct bank quads
@@ -1280,37 +1270,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       bool bad = false;
 #pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-        cur.inv[rb] = wa.scale;
-        if (wa.normalize || kReduce) {  // (the reductions look at every row's sum of squares: W3Tile::bad)
-          float ss = 0.f, ss2 = 0.f;
-#pragma unroll
-          for (int s = 0; s < S; ++s) {
-            const uint32_t w[4] = {a[rb][s].x, a[rb][s].y, a[rb][s].z, a[rb][s].w};
-#pragma unroll
-            for (int j = 0; j < 4; j += 2) {
-              ss = dot2_self<FT>(w[j], ss);
-              ss2 = dot2_self<FT>(w[j + 1], ss2);
-            }
-          }
-          ss += ss2;
-          ss += __shfl_xor(ss, 16);
-          ss += __shfl_xor(ss, 32);
-          if (wa.normalize)
-            cur.inv[rb] = wa.normalize == SAF_NORM_L2_CLAMP ? wa.scale / fmaxf(sqrtf(ss), 0.1f)
-                                                            : (ss > 0.0f ? wa.scale / sqrtf(ss) : 0.0f);
-          // a row with an inf or a NaN in it (ss is inf or NaN in all four of its lanes): SAF_NORM_L2: the all-zero row; otherwise
-          // the reductions keep its NaN scores out of their chains (see query_wide2_kernel)
-          if (!(ss < INFINITY)) {
-            if (wa.normalize == SAF_NORM_L2) {
-#pragma unroll
-              for (int s = 0; s < S; ++s) a[rb][s] = make_uint4(0u, 0u, 0u, 0u);
-            } else {
-              bad = true;
-            }
-          }
-        }
-      }
+      for (int rb = 0; rb < 2; ++rb) cur.inv[rb] = row_block_factor<FT, true>(a[rb], wa, wa.normalize || kReduce, bad);
       cur.bad = kReduce && __any(bad);
     }
     cur.qt = qt;
@@ -1447,41 +1407,19 @@ __global__ void qkeys_decode_kernel(const unsigned long long* __restrict__ keys,
   out_row[q] = k ? (int64_t)(uint32_t)~(uint32_t)k + row_hi : -1;
 }
 
+// the first kernel (its parameters are the struct's fields one by one)
 template <int FT, int OT, int KS>
-int launch_wide(const uint16_t* feats, int64_t n_rows, int64_t fstride, const uint16_t* text16, int Q, int Qpad,
-                float scale, int normalize, void* out, int64_t ostride, hipStream_t s) {
+int launch_wide(const WideArgs& wa, hipStream_t s) {
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16);
   auto fn = query_wide_kernel<FT, OT, KS>;
   if (int rc = allow_lds(fn, shmem)) return rc;
-  hipLaunchKernelGGL(fn, dim3(grid_1d(n_rows, 1, 32 * kWWaves)), dim3(kWThreads), shmem, s, feats, n_rows, fstride, text16, Q, Qpad,
-                     scale, normalize, out, ostride);
+  hipLaunchKernelGGL(fn, dim3(grid_1d(wa.n_rows, 1, 32 * kWWaves)), dim3(kWThreads), shmem, s, wa.feats, wa.n_rows, wa.fstride, wa.text16,
+                     wa.Q, wa.Qpad, wa.scale, wa.normalize, wa.out, wa.ostride);
   return check_launch("query_wide_kernel");
 }
 
-template <int FT, int OT>
-int launch_wide_ks(int D, const uint16_t* feats, int64_t n_rows, int64_t fstride, const uint16_t* text16, int Q,
-                   int Qpad, float scale, int normalize, void* out, int64_t ostride, hipStream_t s) {
-  switch (D) {
-    case 128: return launch_wide<FT, OT, 8>(feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    case 256: return launch_wide<FT, OT, 16>(feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    case 512: return launch_wide<FT, OT, 32>(feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    default: return fail(SAF_E_UNSUPPORTED, "wide scan: feat_dim must be 128, 256 or 512 (got %d)", D);
-  }
-}
-
-template <int FT>
-int launch_wide_ot(int ot, int D, const uint16_t* feats, int64_t n_rows, int64_t fstride, const uint16_t* text16, int Q,
-                   int Qpad, float scale, int normalize, void* out, int64_t ostride, hipStream_t s) {
-  switch (ot) {
-    case SAF_F32: return launch_wide_ks<FT, SAF_F32>(D, feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    case SAF_F16: return launch_wide_ks<FT, SAF_F16>(D, feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    case SAF_BF16: return launch_wide_ks<FT, SAF_BF16>(D, feats, n_rows, fstride, text16, Q, Qpad, scale, normalize, out, ostride, s);
-    default: return fail(SAF_E_INVALID, "wide scan: bad out_dtype %d", ot);
-  }
-}
-
 template <int FT, int OT, int KS, int EPI, int NF, int TH>
-int launch_wide2_nf(const Wide2Args& wa, hipStream_t s) {
+int launch_wide2_nf(const WideArgs& wa, hipStream_t s) {
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16) + (EPI == SAF_QW_QUERY_MAX ? (TH / 64) * 32 * NF * sizeof(float) : 0);
   auto fn = query_wide2_kernel<FT, OT, KS, EPI, NF, TH>;
   if (int rc = allow_lds(fn, shmem)) return rc;
@@ -1491,7 +1429,7 @@ int launch_wide2_nf(const Wide2Args& wa, hipStream_t s) {
 }
 
 template <int FT, int OT, int KS, int EPI>
-int launch_wide3(const Wide2Args& wa, hipStream_t s) {
+int launch_wide3(const WideArgs& wa, hipStream_t s) {
   // two text tiles, 1 KiB of 1/norms (QUERY_MAX), and at D = 512 eleven 1 KiB pieces per wave of the next block's rows (kPref)
   constexpr size_t shmem = 2 * (size_t)kWTile * (KS * 32 + 16) + 1024 +
                            ((KS == 32 && (EPI == SAF_QW_SCORES || EPI == SAF_QW_QUERY_MAX)) ? 8 * 11 * 1024 : 0) +
@@ -1503,7 +1441,7 @@ int launch_wide3(const Wide2Args& wa, hipStream_t s) {
 }
 
 template <int FT, int OT, int KS, int EPI>
-int launch_wide2(const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
+int launch_wide2(const WideArgs& wa, const Knobs& kn, hipStream_t s) {
   // The scan runs on v_mfma_f32_16x16x32 (query_wide3_kernel: 4-9 % faster than the 32x32x16 form at the same tile per wave, the
   // chip holds a higher clock on it); SAF_WIDE_MFMA=32 selects query_wide2_kernel.
   if (!kn.wide_mfma32) return launch_wide3<FT, OT, KS, EPI>(wa, s);
@@ -1514,30 +1452,23 @@ int launch_wide2(const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
 }
 
 template <int FT, int KS>
-int launch_wide2_epi(int epi, int ot, const Wide2Args& wa, const Knobs& kn, hipStream_t s) {
+int launch_wide2_epi(int epi, int ot, const WideArgs& wa, const Knobs& kn, hipStream_t s) {
+  const auto bad = [&] { return fail(SAF_E_INVALID, "wide scan: bad epilogue %d / out_dtype %d", epi, ot); };
   switch (epi) {
     case SAF_QW_SCORES:
-      switch (ot) {
-        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_SCORES>(wa, kn, s);
-        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_SCORES>(wa, kn, s);
-        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_SCORES>(wa, kn, s);
-      }
-      break;
+      return dispatch_dtype(ot, [&](auto o) { return launch_wide2<FT, decltype(o)::value, KS, SAF_QW_SCORES>(wa, kn, s); }, bad);
     case SAF_QW_VS_BACKGROUND:
-      switch (ot) {
-        case SAF_F32: return launch_wide2<FT, SAF_F32, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
-        case SAF_F16: return launch_wide2<FT, SAF_F16, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
-        case SAF_BF16: return launch_wide2<FT, SAF_BF16, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s);
-      }
-      break;
+      return dispatch_dtype(ot, [&](auto o) { return launch_wide2<FT, decltype(o)::value, KS, SAF_QW_VS_BACKGROUND>(wa, kn, s); }, bad);
+    // (no N x Q output: these two exist with OT = SAF_F32 only)
     case SAF_QW_ROW_ARGMAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_ROW_ARGMAX>(wa, kn, s);
     case SAF_QW_QUERY_MAX: return launch_wide2<FT, SAF_F32, KS, SAF_QW_QUERY_MAX>(wa, kn, s);
+    default: return bad();
   }
-  return fail(SAF_E_INVALID, "wide scan: bad epilogue %d / out_dtype %d", epi, ot);
 }
 
-// fp32 text -> 16-bit tiles.  SCORES / ROW_ARGMAX / QUERY_MAX: row q of the text is row q.  VS_BACKGROUND: the
-// first n_bg rows (the shared background prompts) fill tile 0, zero padded to 32 rows; target t is row 32 + t.
+// fp32 text [Q][tstride] -> 16-bit tiles [Qpad][D], rows past the text zero: the pre-kernel of all three scans.  SCORES / ROW_ARGMAX /
+// QUERY_MAX and the first kernel (n_bg = 0): row q of the text is row q.  VS_BACKGROUND: the first n_bg rows (the shared background
+// prompts) fill tile 0, zero padded to 32 rows; target t is row 32 + t.  `qkeys` (QUERY_MAX, or nullptr): the Qpad keys are cleared.
 template <int FT>
 __global__ void text_tiles_kernel(const float* __restrict__ text, int Q, int64_t tstride, int D, int Qpad, int n_bg,
                                   uint16_t* __restrict__ out, unsigned long long* __restrict__ qkeys, int negate) {
@@ -1558,11 +1489,40 @@ __global__ void text_tiles_kernel(const float* __restrict__ text, int Q, int64_t
   }
 }
 
-// columns the kernel sees (Q of Wide2Args) and their padding to whole tiles
-inline int wide2_cols(int n_text, int epi, int n_bg) { return epi == SAF_QW_VS_BACKGROUND ? kWTile + (n_text - n_bg) : n_text; }
-inline size_t wide2_ws_bytes(int n_text, int D, int epi, int n_bg) {
-  const size_t qpad = ((size_t)wide2_cols(n_text, epi, n_bg) + kWTile - 1) / kWTile * kWTile;
-  return ((qpad * D * 2 + 255) & ~(size_t)255) + qpad * sizeof(unsigned long long);
+// columns the kernel sees (Q of WideArgs), their padding to whole tiles, and the workspace: the 16-bit text of the padded columns in
+// whole 256 bytes, for the fused scans followed by a 64-bit key per padded column
+inline int wide_cols(int n_text, int epi, int n_bg) { return epi == SAF_QW_VS_BACKGROUND ? kWTile + (n_text - n_bg) : n_text; }
+inline int wide_qpad(int cols) { return (cols + kWTile - 1) / kWTile * kWTile; }
+inline size_t wide_text_bytes(int cols, int D) { return ((size_t)wide_qpad(cols) * D * 2 + 255) & ~(size_t)255; }
+inline size_t wide_ex_ws_bytes(int cols, int D) { return wide_text_bytes(cols, D) + wide_qpad(cols) * sizeof(unsigned long long); }
+
+// The text as the scans read it, into the workspace.  The grid is not grid_1d's: one thread per element, no stride loop.
+int launch_text_tiles(int ft, const float* text, int n_text, int64_t tstride, int D, int Qpad, int n_bg, uint16_t* text16,
+                      unsigned long long* qkeys, int negate, hipStream_t s) {
+  const int items = Qpad * D;
+  return dispatch_ft16(ft, [&](auto f) {
+    hipLaunchKernelGGL(text_tiles_kernel<decltype(f)::value>, dim3((items + 255) / 256), dim3(256), 0, s, text, n_text, tstride, D, Qpad,
+                       n_bg, text16, qkeys, negate);
+    return check_launch("text_tiles_kernel");
+  });
+}
+
+// What both entry points ask of the rows and the text, in the order they report it.  `dim_ok`: the fused scans' own feat_dim rule
+// (the first kernel's is reported at its launch); `args_ok`: the entry's own rule for NULL and negative arguments; `out_stride`:
+// the first kernel's N x n_text output, or nullptr (the fused scans check their outputs per epilogue).
+int check_wide_call(int32_t feat_dtype, bool dim_ok, bool args_ok, const void* feats, int64_t feat_stride, int32_t feat_dim,
+                    int64_t text_stride, const int64_t* out_stride, int32_t n_text) {
+  if (feat_dtype != SAF_F16 && feat_dtype != SAF_BF16)
+    return fail(SAF_E_UNSUPPORTED, "wide scan: features must be SAF_F16 or SAF_BF16");
+  if (!dim_ok) return fail(SAF_E_UNSUPPORTED, "wide scan (fused epilogues): feat_dim must be 256 or 512 (got %d)", feat_dim);
+  if (!args_ok) return fail(SAF_E_INVALID, "wide scan: bad arguments");
+  if (feat_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: feat_stride %lld is below feat_dim %d", (long long)feat_stride, feat_dim);
+  if (text_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: text_stride %lld is below feat_dim %d", (long long)text_stride, feat_dim);
+  if (out_stride && *out_stride < n_text)
+    return fail(SAF_E_INVALID, "wide scan: out_stride %lld is below n_text %d", (long long)*out_stride, n_text);
+  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0)
+    return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned (feats on 16 bytes, feat_stride a multiple of 8)");
+  return SAF_OK;
 }
 
 }  // namespace
@@ -1574,48 +1534,47 @@ extern "C" {
 
 size_t saf_query_wide_workspace_bytes(int32_t n_text, int32_t feat_dim) {
   if (n_text <= 0 || feat_dim <= 0) return 0;
-  const size_t qpad = ((size_t)n_text + kWTile - 1) / kWTile * kWTile;
-  return (qpad * feat_dim * 2 + 255) & ~(size_t)255;
+  return wide_text_bytes(n_text, feat_dim);
 }
 
 int saf_query_scan_wide(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride, int32_t feat_dim,
                         const float* text, int32_t n_text, int64_t text_stride, float scale, int32_t normalize,
                         void* out, int32_t out_dtype, int64_t out_stride, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  if (feat_dtype != SAF_F16 && feat_dtype != SAF_BF16)
-    return fail(SAF_E_UNSUPPORTED, "wide scan: features must be SAF_F16 or SAF_BF16");
-  if (!feats || !text || !out || n_rows < 0 || n_text <= 0) return fail(SAF_E_INVALID, "wide scan: bad arguments");
-  if (feat_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: feat_stride %lld is below feat_dim %d", (long long)feat_stride, feat_dim);
-  if (text_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: text_stride %lld is below feat_dim %d", (long long)text_stride, feat_dim);
-  if (out_stride < n_text) return fail(SAF_E_INVALID, "wide scan: out_stride %lld is below n_text %d", (long long)out_stride, n_text);
-  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0)
-    return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned (feats on 16 bytes, feat_stride a multiple of 8)");
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < saf_query_wide_workspace_bytes(n_text, feat_dim))
-    return fail(SAF_E_WORKSPACE, "wide scan: workspace needs %zu bytes", saf_query_wide_workspace_bytes(n_text, feat_dim));
+  // (feats and out may not be NULL here even with no rows; any feat_dim passes until the launch)
+  if (int rc = check_wide_call(feat_dtype, true, feats && text && out && n_rows >= 0 && n_text > 0, feats, feat_stride, feat_dim,
+                               text_stride, &out_stride, n_text))
+    return rc;
+  const size_t need = saf_query_wide_workspace_bytes(n_text, feat_dim);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+    return fail(SAF_E_WORKSPACE, "wide scan: workspace needs %zu bytes", need);
   if (n_rows == 0) return SAF_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int Qpad = (n_text + kWTile - 1) / kWTile * kWTile;
-  uint16_t* text16 = static_cast<uint16_t*>(workspace);
-  const int items = Qpad * feat_dim;
-  if (feat_dtype == SAF_BF16)
-    hipLaunchKernelGGL(text_to_16_kernel<SAF_BF16>, dim3((items + 255) / 256), dim3(256), 0, s, text, n_text, text_stride,
-                       feat_dim, Qpad, text16);
-  else
-    hipLaunchKernelGGL(text_to_16_kernel<SAF_F16>, dim3((items + 255) / 256), dim3(256), 0, s, text, n_text, text_stride,
-                       feat_dim, Qpad, text16);
-  int rc = check_launch("text_to_16_kernel");
-  if (rc) return rc;
-  const uint16_t* f = static_cast<const uint16_t*>(feats);
-  return feat_dtype == SAF_BF16
-             ? launch_wide_ot<SAF_BF16>(out_dtype, feat_dim, f, n_rows, feat_stride, text16, n_text, Qpad, scale, normalize,
-                                        out, out_stride, s)
-             : launch_wide_ot<SAF_F16>(out_dtype, feat_dim, f, n_rows, feat_stride, text16, n_text, Qpad, scale, normalize,
-                                       out, out_stride, s);
+  WideArgs wa = {};
+  wa.feats = static_cast<const uint16_t*>(feats);
+  wa.n_rows = n_rows; wa.fstride = feat_stride; wa.text16 = static_cast<uint16_t*>(workspace); wa.Q = n_text; wa.Qpad = wide_qpad(n_text);
+  wa.scale = scale; wa.normalize = normalize; wa.out = out; wa.ostride = out_stride;
+  if (int rc = launch_text_tiles(feat_dtype, text, n_text, text_stride, feat_dim, wa.Qpad, 0, static_cast<uint16_t*>(workspace), nullptr, 0, s))
+    return rc;
+  return dispatch_ft16(feat_dtype, [&](auto ft) {
+    return dispatch_dtype(
+        out_dtype,
+        [&](auto ot) {
+          constexpr int FT = decltype(ft)::value, OT = decltype(ot)::value;
+          switch (feat_dim) {
+            case 128: return launch_wide<FT, OT, 8>(wa, s);
+            case 256: return launch_wide<FT, OT, 16>(wa, s);
+            case 512: return launch_wide<FT, OT, 32>(wa, s);
+            default: return fail(SAF_E_UNSUPPORTED, "wide scan: feat_dim must be 128, 256 or 512 (got %d)", feat_dim);
+          }
+        },
+        [&] { return fail(SAF_E_INVALID, "wide scan: bad out_dtype %d", out_dtype); });
+  });
 }
 
 size_t saf_query_wide_ex_workspace_bytes(int32_t n_text, int32_t feat_dim, int32_t epilogue, int32_t n_background) {
   if (n_text <= 0 || feat_dim <= 0 || n_background < 0 || n_background > n_text) return 0;
-  return wide2_ws_bytes(n_text, feat_dim, epilogue, n_background);
+  return wide_ex_ws_bytes(wide_cols(n_text, epilogue, n_background), feat_dim);
 }
 
 int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride, int32_t feat_dim,
@@ -1623,15 +1582,10 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
                            int32_t epilogue, int32_t n_background, int32_t flags, void* out, int32_t out_dtype,
                            int64_t out_stride, int32_t* out_index, float* out_value, int64_t* out_row, int64_t row_offset,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (feat_dtype != SAF_F16 && feat_dtype != SAF_BF16)
-    return fail(SAF_E_UNSUPPORTED, "wide scan: features must be SAF_F16 or SAF_BF16");
-  if (feat_dim != 256 && feat_dim != 512)
-    return fail(SAF_E_UNSUPPORTED, "wide scan (fused epilogues): feat_dim must be 256 or 512 (got %d)", feat_dim);
-  if ((!feats && n_rows > 0) || !text || n_rows < 0 || n_text <= 0) return fail(SAF_E_INVALID, "wide scan: bad arguments");
-  if (feat_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: feat_stride %lld is below feat_dim %d", (long long)feat_stride, feat_dim);
-  if (text_stride < feat_dim) return fail(SAF_E_INVALID, "wide scan: text_stride %lld is below feat_dim %d", (long long)text_stride, feat_dim);
-  if (((uintptr_t)feats & 15) || (feat_stride % 8) != 0)
-    return fail(SAF_E_INVALID, "wide scan: feature rows must be 16-byte aligned (feats on 16 bytes, feat_stride a multiple of 8)");
+  // (with no rows feats and the outputs per row may be NULL: the text is still converted and QUERY_MAX still answers)
+  if (int rc = check_wide_call(feat_dtype, feat_dim == 256 || feat_dim == 512, (feats || n_rows <= 0) && text && n_rows >= 0 && n_text > 0,
+                               feats, feat_stride, feat_dim, text_stride, nullptr, n_text))
+    return rc;
   int n_bg = 0, n_out_cols = n_text;
   switch (epilogue) {
     case SAF_QW_SCORES:
@@ -1654,43 +1608,33 @@ int saf_query_scan_wide_ex(const void* feats, int32_t feat_dtype, int64_t n_rows
       break;
     default: return fail(SAF_E_INVALID, "wide scan: bad epilogue %d", epilogue);
   }
-  const size_t need = wide2_ws_bytes(n_text, feat_dim, epilogue, n_bg);
+  const int cols = wide_cols(n_text, epilogue, n_bg);
+  const size_t need = wide_ex_ws_bytes(cols, feat_dim);
   if (!workspace || ((uintptr_t)workspace & 255) || workspace_bytes < need)
     return fail(SAF_E_WORKSPACE, "wide scan: workspace needs %zu bytes, 256-byte aligned", need);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cols = wide2_cols(n_text, epilogue, n_bg);
-  const int Qpad = (cols + kWTile - 1) / kWTile * kWTile;
-  uint16_t* text16 = static_cast<uint16_t*>(workspace);
-  unsigned long long* qkeys = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(workspace) +
-                                                                   (((size_t)Qpad * feat_dim * 2 + 255) & ~(size_t)255));
-  const int items = Qpad * feat_dim;
   // ROW_ARGMAX compares raw dot products (a row's scale / norm must not flip their order): a negative scale goes into the text
   const int negate = epilogue == SAF_QW_ROW_ARGMAX && scale < 0.0f ? 1 : 0;
-  if (negate) scale = -scale;
-  if (feat_dtype == SAF_BF16)
-    hipLaunchKernelGGL(text_tiles_kernel<SAF_BF16>, dim3((items + 255) / 256), dim3(256), 0, s, text, n_text, text_stride,
-                       feat_dim, Qpad, n_bg, text16, epilogue == SAF_QW_QUERY_MAX ? qkeys : nullptr, negate);
-  else
-    hipLaunchKernelGGL(text_tiles_kernel<SAF_F16>, dim3((items + 255) / 256), dim3(256), 0, s, text, n_text, text_stride,
-                       feat_dim, Qpad, n_bg, text16, epilogue == SAF_QW_QUERY_MAX ? qkeys : nullptr, negate);
-  int rc = check_launch("text_tiles_kernel");
-  if (rc) return rc;
+  WideArgs wa;
+  wa.feats = static_cast<const uint16_t*>(feats);
+  wa.n_rows = n_rows; wa.fstride = feat_stride; wa.text16 = static_cast<uint16_t*>(workspace); wa.Q = cols; wa.Qpad = wide_qpad(cols);
+  wa.scale = negate ? -scale : scale; wa.normalize = normalize; wa.n_bg = n_bg; wa.flags = flags; wa.out = out; wa.ostride = out_stride;
+  wa.out_index = out_index; wa.out_value = out_value; wa.row_offset = row_offset;
+  wa.qkeys = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(workspace) + wide_text_bytes(cols, feat_dim));
+  const Knobs kn = read_knobs();
+  wa.safe_wait = kn.w2_safe_wait ? 1 : 0;  // (SAF_W2_SAFE_WAIT)
+  if (int rc = launch_text_tiles(feat_dtype, text, n_text, text_stride, feat_dim, wa.Qpad, n_bg, static_cast<uint16_t*>(workspace),
+                                 epilogue == SAF_QW_QUERY_MAX ? wa.qkeys : nullptr, negate, s))
+    return rc;
   if (n_rows > 0) {
-    Wide2Args wa;
-    wa.feats = static_cast<const uint16_t*>(feats);
-    wa.n_rows = n_rows; wa.fstride = feat_stride; wa.text16 = text16; wa.Q = cols; wa.Qpad = Qpad; wa.scale = scale;
-    wa.normalize = normalize; wa.n_bg = n_bg; wa.flags = flags; wa.out = out; wa.ostride = out_stride;
-    wa.out_index = out_index; wa.out_value = out_value; wa.qkeys = qkeys; wa.row_offset = row_offset;
-    const Knobs kn = read_knobs();
-    wa.safe_wait = kn.w2_safe_wait ? 1 : 0;  // (SAF_W2_SAFE_WAIT)
-    if (feat_dtype == SAF_BF16)
-      rc = feat_dim == 512 ? launch_wide2_epi<SAF_BF16, 32>(epilogue, out_dtype, wa, kn, s) : launch_wide2_epi<SAF_BF16, 16>(epilogue, out_dtype, wa, kn, s);
-    else
-      rc = feat_dim == 512 ? launch_wide2_epi<SAF_F16, 32>(epilogue, out_dtype, wa, kn, s) : launch_wide2_epi<SAF_F16, 16>(epilogue, out_dtype, wa, kn, s);
-    if (rc) return rc;
+    if (int rc = dispatch_ft16(feat_dtype, [&](auto ft) {
+          constexpr int FT = decltype(ft)::value;
+          return feat_dim == 512 ? launch_wide2_epi<FT, 32>(epilogue, out_dtype, wa, kn, s) : launch_wide2_epi<FT, 16>(epilogue, out_dtype, wa, kn, s);
+        }))
+      return rc;
   }
   if (epilogue == SAF_QW_QUERY_MAX) {
-    hipLaunchKernelGGL(qkeys_decode_kernel, dim3((n_text + 255) / 256), dim3(256), 0, s, qkeys, n_text, out_value, out_row,
+    hipLaunchKernelGGL(qkeys_decode_kernel, dim3((n_text + 255) / 256), dim3(256), 0, s, wa.qkeys, n_text, out_value, out_row,
                        (int64_t)0);
     return check_launch("qkeys_decode_kernel");
   }
