@@ -536,6 +536,35 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
                          int64_t n_rows, const void* recv, int64_t mine, int32_t world, void* stream);
 
 /*
+ * A fused volume carried into another box of the SAME lattice (additive under ABI 7; new capability, nothing to mirror in the
+ * reference: its manager re-fuses every frame of a scan into a new grid when the scan grows, get_path(config, curr_ver, ...)).
+ * `src` and `dst` are two boxes of one lattice -- same origin, same voxel size, corners that differ by whole voxels -- so the pass
+ * is a copy and nothing is recomputed; resampling, coarsening and blending two volumes are not offered.
+ *   mapping   destination voxel (x, y, z) corresponds to source voxel (x + off_x, y + off_y, z + off_z); the caller passes
+ *             off = dst's index offset - src's.  The OVERLAP is the set of destination voxels whose source voxel lies inside
+ *             `src`.  A destination voxel outside the overlap is not touched: every buffer keeps its bytes there.
+ *   copied    per overlap voxel: tsdf, tsdf_weight, weight, the three rgb floats, and aux_src -> aux_dst ([N_src] / [N_dst] i32,
+ *             an optional pair: whatever the caller keeps per voxel, e.g. an object index).  If and only if the source `weight`
+ *             is > 0, also the feature row and, with n_classes > 0, the label histogram row.  Bytes are copied, whatever the
+ *             dtype (SAF_F32, SAF_BF16, SAF_F16; any feat_dim).
+ *   not read  the feature / label row of a source voxel with weight == 0: after a deferred clear (saf_clear_unwritten_rows still
+ *             owed) it holds stale data, which the windowed fuse path never reads either.  The destination row of such a voxel
+ *             is NOT WRITTEN: the caller supplies a destination whose weight-0 rows are zero, or owes it the same clear.
+ *             The axis tables, accum_mode and trunc of the two descriptors are not inspected: a copy is a copy.
+ *   counts    device u64[2], ADDED to (may be NULL): [0] += overlap voxels with weight > 0 (rows carried), [1] += overlap voxels
+ *             with tsdf_weight > 0.  Integer atomics: exact whatever the scheduling.
+ * SAF_E_INVALID (on the host, nothing is launched) for a NULL src / dst or a NULL tsdf, tsdf_weight, weight, rgb or clip_feat (or
+ * labels_one_hot with n_classes > 0), non-positive sizes or feat_dim, a grid of 2^31 voxels or more, feat_dim, feat_dtype or
+ * n_classes that differ between the two, only one of aux_src / aux_dst, and any destination buffer whose byte range intersects
+ * the source buffer of the same name (the pass works out of place only).  An empty overlap is SAF_OK with nothing launched.
+ * One launch; a wave takes 64 consecutive voxels of the flattened overlap box and copies the touched rows one after the other,
+ * 16 bytes per lane where the row pitch and both bases allow it, else 4 (the 572-byte label rows) or 2.  Per call
+ * 28 N_overlap + M (row_bytes + label_row_bytes) bytes are read and as many written, M = counts[0].
+ */
+int saf_volume_carry(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
+                     const int32_t* aux_src, int32_t* aux_dst, uint64_t* counts, void* stream);
+
+/*
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for
  * marching-cubes vertices given in voxel-index coordinates, grid = (v + 0.5) * (1/nvox) * 2 - 1 and
  * 3-D grid_sample(align_corners=False, zeros padding) of the volume:

@@ -15,6 +15,8 @@ __all__ = [
     "backproject_pcd",
     "get_pix_vecs",
     "scene_bounds",
+    "lattice_box",
+    "GridMove",
     "label_components",
     "discover_objects",
     "evaluation",
@@ -34,7 +36,7 @@ __all__ = [
 
 
 def __getattr__(name):
-    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds"):
+    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove"):
         from . import clipfusion as _m
 
         return getattr(_m, name)

@@ -8,6 +8,7 @@ Same names, arguments and error behaviour as the reference classes so that its c
   * ``backproject_pcd`` -- reference clipfusion.py:510-572
   * ``get_pix_vecs``    -- reference clipfusion.py:497-507
   * ``scene_bounds``    -- the bounds arithmetic of clipfusion.py:1098-1106
+  * ``lattice_box`` / ``move_grid`` -- not in the reference: a volume moved by whole voxels on its own lattice
 
 PyTorch is plumbing here (device memory, streams, the backbone GEMMs); the fusion loop and the
 query scan are the hand-written HIP kernels behind ``include/saf.h``.  There is no CPU
@@ -58,6 +59,19 @@ def _axis_tables(origin, voxel_size, nvox, index_offset=(0, 0, 0), x_planes=None
     return [(idx[a] * voxel_size + origin[a]).to(torch.float32).contiguous() for a in range(3)]
 
 
+def _xyz_world(ax, nvox):
+    """The reference's ``xyz_world`` [N,3] (clipfusion.py:617-622) from the three axis tables."""
+    nx, ny, nz = (int(v) for v in nvox)
+    return torch.stack(
+        (
+            ax[0][:, None, None].expand(nx, ny, nz),
+            ax[1][None, :, None].expand(nx, ny, nz),
+            ax[2][None, None, :].expand(nx, ny, nz),
+        ),
+        dim=-1,
+    ).reshape(-1, 3)
+
+
 # `fusion.borrow_inputs = True` (default: SAF_BORROW_INPUTS=1 in the environment, else False): the queue behind integrate() does
 # not copy a call's depth / rgb / label images into its staging ring but reads them where they are when their window is fused --
 # up to 512 frames later.  The caller promises not to WRITE those tensors until flush() (dropping them is fine: the queue holds
@@ -103,16 +117,7 @@ class _FusionVolumeMixin:
         self.register_buffer("axis_z", ax[2], persistent=False)
         self.register_buffer("fuse_stats", zeros(_abi.SAF_STATS_WORDS, dtype=torch.int64), persistent=False)
         if keep_xyz_world:
-            nx, ny, nz = (int(v) for v in nvox)
-            xyz_world = torch.stack(
-                (
-                    ax[0][:, None, None].expand(nx, ny, nz),
-                    ax[1][None, :, None].expand(nx, ny, nz),
-                    ax[2][None, None, :].expand(nx, ny, nz),
-                ),
-                dim=-1,
-            ).reshape(-1, 3)
-            self.register_buffer("xyz_world", xyz_world)
+            self.register_buffer("xyz_world", _xyz_world(ax, nvox))
         self._workspace = None
         self._shard_stripes = None  # [(first, count)] while the volume holds only its reduce-scattered stripes of a merged job
         self.__dict__.setdefault("defer_frames", True)  # queue small integrate() calls into 128-frame windows
@@ -516,6 +521,101 @@ class _FusionVolumeMixin:
         self.__dict__["_shard16"] = None  # (distributed.shard_features_16's copy of the rows that were just discarded)
         self.__dict__["_feat_stale"] = lazy
 
+    def move_grid(self, index_offset, nvox):
+        """Move the volume to another box of ITS OWN lattice and keep what is fused: afterwards the module holds the ``nvox`` voxels
+        that start at voxel index ``index_offset`` of the grid anchored at ``origin`` (offsets may be negative), and every voxel
+        the old and the new box share holds, byte for byte, what it held before (saf_volume_carry, include/saf.h).
+        Voxels the new box adds are empty, voxels it drops are lost.  Because the axis tables of two boxes of one lattice agree bit
+        for bit on the indices they share, fusing further frames now gives, on the shared voxels, exactly the volume that would
+        have held all the frames from the start.  ``origin``, ``voxel_size`` and ``trunc`` do not change; the module keeps its
+        backbones, its queue and ``fuse_stats``.  Frames still queued behind ``integrate()`` are fused first.
+
+        BOTH volumes are resident during the call: the new buffers are allocated before the old ones are let go.
+
+        ``voxel_obj_idx``, if the caller has set one of the old grid's length, is carried along (-1 = no object in the voxels the new
+        box adds); ``objects_segmentation_color`` is derived from it and is deleted: the caller recomputes it.  Returns a
+        ``GridMove``; its counters are device tensors, nothing is read back here.  ``SafError``, with the volume unchanged, for a
+        module built with ``x_planes``, one that holds only reduce-scattered stripes, a poisoned one, a non-positive ``nvox`` and a
+        box of 2^31 voxels or more."""
+        if self.x_planes is not None:
+            raise SafError("move_grid() needs a box of consecutive x-planes: this module was built with x_planes")
+        if getattr(self, "_shard_stripes", None) is not None:
+            raise SafError("this volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
+                           "(distributed.gather_shards, or merge_volumes(..., gather=True)) before moving it")
+        self._check_poisoned()
+        new_off = tuple(int(v) for v in index_offset)
+        new_nvox = tuple(int(v) for v in nvox)
+        if len(new_off) != 3 or len(new_nvox) != 3 or min(new_nvox) <= 0:
+            raise SafError(f"move_grid: nvox must be three positive sizes and index_offset three indices, got {new_nvox} at {new_off}")
+        n_new = new_nvox[0] * new_nvox[1] * new_nvox[2]
+        if n_new >= 1 << 31:
+            raise SafError(f"move_grid: a box of {n_new} voxels (2^31 or more)")
+        # the frames still queued belong to the old box; the session's state is sized by it and goes, as in _apply.  A deferred
+        # clear stays owed: the pass never reads the row of a weight-0 voxel
+        self._flush_pending(final=True)
+        q = self.__dict__["_queue"]
+        q.wait(self)
+        q.close()
+        old = dict(self._buffers)
+        require_cuda(old["clip_feat"], "the fusion volume")
+        dev = old["tsdf"].device
+        old_off, old_nvox = self.index_offset, tuple(int(v) for v in self.nvox)
+        src = self._c_volume(for_fuse=True)
+        labels = old.get("labels_one_hot")
+        obj = getattr(self, "voxel_obj_idx", None)
+        if obj is not None and (not torch.is_tensor(obj) or obj.numel() != old["tsdf"].numel()):
+            obj = None  # (not of this grid: left alone)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            new = {"tsdf": torch.zeros(n_new, dtype=torch.float32, device=dev),
+                   "rgb": torch.zeros((n_new, 3), dtype=torch.float32, device=dev),
+                   "weight": torch.zeros(n_new, dtype=torch.int32, device=dev),
+                   "tsdf_weight": torch.zeros(n_new, dtype=torch.int32, device=dev),
+                   # not cleared here: the rows of voxels that are still unwritten (weight 0) are zeroed when something first
+                   # looks, by the deferred clear of reset() -- the windowed path never reads them (DESIGN 4.18)
+                   "clip_feat": torch.empty((n_new, int(self.n_clip_feats)), dtype=old["clip_feat"].dtype, device=dev)}
+            if labels is not None:
+                new["labels_one_hot"] = torch.zeros((n_new, int(labels.shape[1])), dtype=torch.int32, device=dev)
+            ax = [t.to(dev) for t in _axis_tables(self.origin, self.voxel_size, new_nvox, new_off)]
+            aux_src = aux_dst = None
+            if obj is not None:
+                aux_src = obj.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+                aux_dst = torch.full((n_new,), -1, dtype=torch.int32, device=dev)  # saf_label_components' "no object"
+            p = _abi.ptr
+            dst = _abi.SafVolume(new_nvox[0], new_nvox[1], new_nvox[2], src.feat_dim, src.n_classes, src.feat_dtype, src.accum_mode,
+                                 src.trunc, p(ax[0]), p(ax[1]), p(ax[2]), p(new["tsdf"]), p(new["tsdf_weight"]), p(new["weight"]),
+                                 p(new["rgb"]), p(new["clip_feat"]), p(new.get("labels_one_hot")))
+            counts = torch.zeros(2, dtype=torch.int64, device=dev)
+            before = torch.stack(((old["weight"] > 0).sum(), (old["tsdf_weight"] > 0).sum()))
+            off = tuple(new_off[a] - old_off[a] for a in range(3))
+            check(lib().saf_volume_carry(C.byref(src), C.byref(dst), off[0], off[1], off[2], p(aux_src), p(aux_dst), p(counts),
+                                         stream.cuda_stream), "saf_volume_carry")
+            for t in list(old.values()) + ([aux_src] if aux_src is not None else []):
+                t.record_stream(stream)  # (the old buffers are let go below; the pass reads them on this stream)
+        # the new box is installed (straight into _buffers: an assignment would pay the old volume's deferred clear first)
+        b = self._buffers
+        for name, t in new.items():
+            b[name] = t
+        b["axis_x"], b["axis_y"], b["axis_z"] = ax
+        if "xyz_world" in b:
+            b["xyz_world"] = _xyz_world(ax, new_nvox)
+        self.nvox = torch.as_tensor(new_nvox, dtype=self.nvox.dtype)
+        self.index_offset = new_off
+        self.__dict__["_feat_stale"] = True
+        self._workspace = None  # (sized by the grid)
+        self.__dict__["_shard16"] = None
+        if obj is not None:
+            self.voxel_obj_idx = aux_dst.view(*new_nvox) if obj.dim() == 3 else aux_dst
+        if getattr(self, "objects_segmentation_color", None) is not None:
+            del self.objects_segmentation_color
+        lo = tuple(max(old_off[a], new_off[a]) for a in range(3))
+        hi = tuple(min(old_off[a] + old_nvox[a], new_off[a] + new_nvox[a]) for a in range(3))
+        ext = tuple(max(hi[a] - lo[a], 0) for a in range(3)) if all(hi[a] > lo[a] for a in range(3)) else (0, 0, 0)
+        return GridMove(old_index_offset=old_off, old_nvox=old_nvox, index_offset=new_off, nvox=new_nvox, overlap_nvox=ext,
+                        overlap_in_old=tuple(lo[a] - old_off[a] for a in range(3)) if any(ext) else (0, 0, 0),
+                        overlap_in_new=tuple(lo[a] - new_off[a] for a in range(3)) if any(ext) else (0, 0, 0),
+                        rows_carried=counts[0], rows_dropped=before[0] - counts[0],
+                        tsdf_carried=counts[1], tsdf_dropped=before[1] - counts[1])
 
     def integrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None):
         """``integrate`` with the backbone outputs supplied by the caller (fuse-only entry used by
@@ -658,6 +758,8 @@ class _FusionVolumeMixin:
         return verts[used], faces
 
     def _verts_world(self, verts):
+        if any(self.index_offset):  # a box that does not start at the lattice's voxel 0 (move_grid)
+            verts = verts + np.asarray(self.index_offset, dtype=verts.dtype)
         return verts * self.voxel_size + torch.as_tensor(self.origin).cpu().numpy()
 
     def extract_mesh(self, marching_cubes=None):
@@ -807,6 +909,26 @@ class RenderResult:
     hit: torch.Tensor
     label: torch.Tensor | None = None      # ClipSeemFusion.render: panoptic class of the voxel, -1 = miss
     relevance: torch.Tensor | None = None  # render_query: [H,W,L]
+
+
+@dataclass
+class GridMove:
+    """What ``move_grid`` returns.  Boxes are (index offset on the module's lattice, voxels per axis); the overlap is given by its
+    size and by its low corner in the old and in the new box's own indices (all zeros when the boxes share no voxel).  The four
+    counters are 0-d int64 DEVICE tensors -- reading one synchronises: feature rows (voxels with ``weight > 0``) and TSDF voxels
+    (``tsdf_weight > 0``) that the new box took over, and those of the old box that it left behind."""
+
+    old_index_offset: tuple
+    old_nvox: tuple
+    index_offset: tuple
+    nvox: tuple
+    overlap_nvox: tuple
+    overlap_in_old: tuple
+    overlap_in_new: tuple
+    rows_carried: torch.Tensor
+    rows_dropped: torch.Tensor
+    tsdf_carried: torch.Tensor
+    tsdf_dropped: torch.Tensor
 
 
 @dataclass
@@ -1419,3 +1541,25 @@ def scene_bounds(xyz, voxel_size, trunc_m):
     maxbound = torch.tensor(np.percentile(pts, 99, axis=0)).float() + trunc_m
     nvox = ((maxbound - minbound) / voxel_size).round().int()
     return minbound, nvox
+
+
+def lattice_box(fusion, xyz, trunc_m=None, union=True, multiple=4):
+    """The box of ``fusion``'s own lattice for the sparse cloud ``xyz`` -- what ``move_grid`` takes: (index_offset, nvox), tuples
+    of ints.  The bounds are ``scene_bounds``'s (1st / 99th percentile -/+ ``trunc_m``, default the module's ``trunc``), snapped
+    OUTWARD to the lattice in float64 -- the lattice index of a coordinate c is (c - origin) / voxel_size; floor for the low corner,
+    ceil for the high one, so the first voxel centre is at or below the low bound and the last at or above the high one --, united
+    with the module's current box (``union``), and ``nvox`` rounded up per axis, at the high end, to a multiple of ``multiple``
+    (the windowed path's bricks are 4 x 4 x 16 voxels; 1: as snapped).  Offsets may be negative.  Host only."""
+    pts = xyz.cpu().numpy() if isinstance(xyz, torch.Tensor) else np.asarray(xyz)
+    trunc_m = float(fusion.trunc if trunc_m is None else trunc_m)
+    origin = torch.as_tensor(fusion.origin).detach().cpu().numpy().astype(np.float64)
+    vs = float(fusion.voxel_size)
+    lo = np.floor((np.percentile(pts, 1, axis=0).astype(np.float64) - trunc_m - origin) / vs).astype(np.int64)
+    hi = np.ceil((np.percentile(pts, 99, axis=0).astype(np.float64) + trunc_m - origin) / vs).astype(np.int64)
+    if union:
+        off, nvox = np.asarray(fusion.index_offset, dtype=np.int64), np.asarray([int(v) for v in fusion.nvox], dtype=np.int64)
+        lo, hi = np.minimum(lo, off), np.maximum(hi, off + nvox - 1)
+    n = hi - lo + 1
+    m = max(int(multiple), 1)
+    n = (n + m - 1) // m * m
+    return tuple(int(v) for v in lo), tuple(int(v) for v in n)

@@ -6,7 +6,9 @@ attributes the manager sets on the volume from outside, ``extract_mesh``'s 6-tup
 and ``SceneResult.text_query`` is ``InSituManager.clip_text_query`` (:482-561) over what the reconstruction left.  Every
 stage is one of the package's existing entry points (nothing is computed here that the hot path does not already own);
 what this module adds is the chain and a wall-clock split per stage, the counterpart of the reference's one published
-performance statement ("within a few minutes after a user scans the environment", README.md:4).
+performance statement ("within a few minutes after a user scans the environment", README.md:4).  ``extend_scene`` fuses a later
+scan version's new frames into the volume a reconstruction left (not in the reference, which fuses every version from its
+first frame).
 
 The Flask app, the datasets' decoders and the DGCNN in-situ learner stay the reference's.
 """
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from .clip_seem_fusion import ClipSeemFusion, TextQueryEngine, discover_objects, extract_mesh_by_object
-from .clipfusion import backproject_pcd, scene_bounds
+from .clipfusion import backproject_pcd, lattice_box, scene_bounds
 from .io import ArrayList, dumps_scene_knowledge, save_npy, save_ply, save_scene_arrays
 
 
@@ -149,34 +151,8 @@ class _Clock:
         self._t = now
 
 
-def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class_colors=None, device="cuda", out_dir=None,
-                      max_depth=4, scale_patches_by_depth=False, feat_dtype=torch.float32, num_workers=0,
-                      object_meshes=True, marching_cubes=None, python_lists=False):
-    """``InSituManager.run_clipfusion`` (clip_seem_fusion.py:247-437).
-
-    ``dataset`` yields the reference loaders' 5-tuple ``(rgb[H,W,3], depth[H,W], pose[4,4], K[3,3], idx)`` and has
-    ``imwidth`` / ``imheight``; ``config`` needs ``voxel_size``, ``trunc_vox``, ``clip_patch_size``,
-    ``clip_patch_stride`` (the reference's config dict, clip_seem_fusion.py:63-94).  ``class_names`` /
-    ``class_colors`` are kMaX's ``COCO_PANOPTIC_CLASSES`` / ``COCO_PANOPTIC_COLORS`` in the reference
-    (handy_utils.py:23-26).  Returns a ``SceneResult``; ``result.seconds`` holds the wall clock of every stage.
-
-    ``python_lists``: keep the bulky members of ``scene_knowledge`` -- every object's ``voxels`` and ``mesh`` -- as the nested
-    Python lists the reference builds (handy_utils.py:430-452, clip_seem_fusion.py:393-417); by default they are
-    ``io.ArrayList``s around the arrays (same reads, same JSON: 0.8 s of a 2 s scan were spent building those lists and
-    encoding them).  With ``out_dir`` the volume's ``.npy`` files (3.4 GB at the reference's largest grid) are written by a
-    second thread from the moment the fusion is complete, beside the object / mesh stages."""
-    clk = _Clock()
-    clk.start()
-    # ---- scene bounds (clip_seem_fusion.py:266-287)
-    xyz, _ = backproject_pcd(dataset, batch_size=1, num_workers=num_workers, device="cpu", max_depth=max_depth)
-    trunc_m = config["trunc_vox"] * config["voxel_size"]
-    origin, nvox = scene_bounds(xyz, config["voxel_size"], trunc_m)
-    clk.lap("bounds")
-    # ---- the volume and the fusion loop, one frame per call (clip_seem_fusion.py:291-313)
-    # (the reference builds the module on the host and moves it, clip_seem_fusion.py:291-302: gigabytes of zeros through pageable
-    #  memory -- 0.7 s at the reference's largest grid; `device=` lets the buffers be born on the device)
-    fusion = ClipSeemFusion(origin, config["voxel_size"], nvox, trunc_m, scale_patches_by_depth, config["clip_patch_size"],
-                            config["clip_patch_stride"], clip_model, seg_model, feat_dtype=feat_dtype, device=device).to(device)
+def _fuse_one_by_one(fusion, dataset, config, device, num_workers):
+    """The fusion loop, one frame per ``integrate`` call (clip_seem_fusion.py:303-313); returns where the host's time went."""
     loader = torch.utils.data.DataLoader(dataset, batch_size=1, num_workers=num_workers)
     stage = FrameStager(device)
     refine_poses = bool(config.get("refine_poses", False))  # not in the reference's config: poses that drift (headsets)
@@ -195,9 +171,13 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
         host["stage"] += t1 - t0
         host["integrate"] += t2 - t1
         t_prev = t2
-    fusion.flush()
-    clk.lap("fuse")
-    clk.seconds["fuse_host_split"] = {k: round(v, 4) for k, v in host.items()}
+    return host
+
+
+def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, scan_version, out_dir, object_meshes,
+                  marching_cubes, python_lists):
+    """The stages behind the fusion loop (clip_seem_fusion.py:315-424, :563-607): labels, objects, the scene mesh, per-object
+    meshes, artefacts -- shared by ``reconstruct_scene`` and ``extend_scene``.  ``clk`` has just lapped the fusion."""
     # ---- the volume's artefacts (save_files_and_broadcast, :566-581) start now, on a thread of their own: nothing below writes
     #      clip_feat or rgb (the lap above synchronised the device; ctypes releases the interpreter lock for the whole write)
     writer = None
@@ -226,7 +206,7 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
     clk.lap("label_argmax")
     # ---- objects (flood_fill_3d, :341-348) and the attributes the manager sets from outside (:351-372)
     scene_knowledge, voxel_obj_idx = discover_objects(onehot_to_index, class_names, class_colors, arrays=not python_lists)
-    scene_knowledge["scan_version"] = 0
+    scene_knowledge["scan_version"] = scan_version
     fusion.unique_objects = scene_knowledge["unique_objects"]
     fusion.voxel_obj_idx = voxel_obj_idx
     seg_color = torch.clone(fusion.rgb).view(*[int(v) for v in fusion.nvox], -1)
@@ -274,5 +254,80 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
         clk.seconds["volume_write_beside"] = round(wpaths.pop("_seconds"), 4)
         res.paths.update(wpaths)
         clk.lap("save_volume_wait")
+    return res
+
+
+def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class_colors=None, device="cuda", out_dir=None,
+                      max_depth=4, scale_patches_by_depth=False, feat_dtype=torch.float32, num_workers=0,
+                      object_meshes=True, marching_cubes=None, python_lists=False):
+    """``InSituManager.run_clipfusion`` (clip_seem_fusion.py:247-437).
+
+    ``dataset`` yields the reference loaders' 5-tuple ``(rgb[H,W,3], depth[H,W], pose[4,4], K[3,3], idx)`` and has
+    ``imwidth`` / ``imheight``; ``config`` needs ``voxel_size``, ``trunc_vox``, ``clip_patch_size``,
+    ``clip_patch_stride`` (the reference's config dict, clip_seem_fusion.py:63-94).  ``class_names`` /
+    ``class_colors`` are kMaX's ``COCO_PANOPTIC_CLASSES`` / ``COCO_PANOPTIC_COLORS`` in the reference
+    (handy_utils.py:23-26).  Returns a ``SceneResult``; ``result.seconds`` holds the wall clock of every stage.
+
+    ``python_lists``: keep the bulky members of ``scene_knowledge`` -- every object's ``voxels`` and ``mesh`` -- as the nested
+    Python lists the reference builds (handy_utils.py:430-452, clip_seem_fusion.py:393-417); by default they are
+    ``io.ArrayList``s around the arrays (same reads, same JSON: 0.8 s of a 2 s scan were spent building those lists and
+    encoding them).  With ``out_dir`` the volume's ``.npy`` files (3.4 GB at the reference's largest grid) are written by a
+    second thread from the moment the fusion is complete, beside the object / mesh stages."""
+    clk = _Clock()
+    clk.start()
+    # ---- scene bounds (clip_seem_fusion.py:266-287)
+    xyz, _ = backproject_pcd(dataset, batch_size=1, num_workers=num_workers, device="cpu", max_depth=max_depth)
+    trunc_m = config["trunc_vox"] * config["voxel_size"]
+    origin, nvox = scene_bounds(xyz, config["voxel_size"], trunc_m)
+    clk.lap("bounds")
+    # ---- the volume and the fusion loop, one frame per call (clip_seem_fusion.py:291-313)
+    # (the reference builds the module on the host and moves it, clip_seem_fusion.py:291-302: gigabytes of zeros through pageable
+    #  memory -- 0.7 s at the reference's largest grid; `device=` lets the buffers be born on the device)
+    fusion = ClipSeemFusion(origin, config["voxel_size"], nvox, trunc_m, scale_patches_by_depth, config["clip_patch_size"],
+                            config["clip_patch_stride"], clip_model, seg_model, feat_dtype=feat_dtype, device=device).to(device)
+    host = _fuse_one_by_one(fusion, dataset, config, device, num_workers)
+    fusion.flush()
+    clk.lap("fuse")
+    clk.seconds["fuse_host_split"] = {k: round(v, 4) for k, v in host.items()}
+    res = _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, 0, out_dir, object_meshes, marching_cubes,
+                        python_lists)
+    res.seconds = clk.seconds
+    return res
+
+
+def extend_scene(result, dataset, config, clip_model, seg_model, class_names, class_colors=None, out_dir=None, max_depth=4,
+                 num_workers=0, object_meshes=True, marching_cubes=None, python_lists=False, multiple=4):
+    """A later version of a scan: fuse its NEW frames (``dataset`` holds only those) into ``result.fusion`` and run the stages
+    behind the fusion again.  The reference's manager fuses every frame of every version into a new grid (``/reprocess_scan``,
+    ``get_path(config, curr_ver, ...)``): the backbones, which cost far more than the fusion, see the whole scan again.  Here the
+    new frames are back-projected, the volume is moved to the box of its own lattice that holds the old box and the new frames'
+    bounds (``lattice_box(..., union=True)``, ``move_grid``: a copy), and only the new frames go through the backbones
+    and the one-frame-per-call loop.  On the voxels of the old box the volume is bit for bit the one that would have fused all
+    the frames into the new box from the start (in the frame-ordered form; the default form within its own rounding).
+
+    ``clip_model`` / ``seg_model`` replace the module's backbones when they are other objects than the ones it holds; the other
+    arguments are ``reconstruct_scene``'s.  Objects are discovered anew from the new labels: an object keeps no identity across
+    versions.  Returns a new ``SceneResult`` around the same module -- ``result`` itself describes a box the module no longer
+    holds --; ``scene_knowledge["scan_version"]`` counts on, ``seconds`` gains ``move_grid``."""
+    clk = _Clock()
+    clk.start()
+    fusion = result.fusion
+    device = fusion._buffers["tsdf"].device
+    if clip_model is not None and clip_model is not fusion.clip:
+        fusion.clip = clip_model
+    if seg_model is not None and seg_model is not fusion.segmentation_model:
+        fusion.segmentation_model = seg_model
+    xyz_new, _ = backproject_pcd(dataset, batch_size=1, num_workers=num_workers, device="cpu", max_depth=max_depth)
+    index_offset, nvox = lattice_box(fusion, xyz_new, union=True, multiple=multiple)
+    clk.lap("bounds")
+    fusion.move_grid(index_offset, nvox)
+    clk.lap("move_grid")
+    host = _fuse_one_by_one(fusion, dataset, config, device, num_workers)
+    fusion.flush()
+    clk.lap("fuse")
+    clk.seconds["fuse_host_split"] = {k: round(v, 4) for k, v in host.items()}
+    version = int(result.scene_knowledge.get("scan_version", 0)) + 1
+    res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, xyz_new)), clk, class_names, class_colors, version,
+                        out_dir, object_meshes, marching_cubes, python_lists)
     res.seconds = clk.seconds
     return res

@@ -1,0 +1,222 @@
+"""CPU: moving a fused volume on its lattice (``lattice_box``, ``move_grid``; include/saf.h: saf_volume_carry) as far as it can
+be checked without a GPU -- the box arithmetic, the bit-identity of the axis tables that the whole feature rests on, the refusals
+the library decides on the host, and the NumPy restatement (tests/carry_reference.py) on itself."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from spatially_aware_ai_amd import _abi, _lib
+from spatially_aware_ai_amd import synthetic as syn
+from spatially_aware_ai_amd._lib import SafError
+from spatially_aware_ai_amd.clipfusion import _axis_tables, lattice_box
+
+import carry_reference as ref
+from host_stubs import P, fake_volume
+
+FAR = 1 << 40  # the destination's stand-in pointers: far from the source's, so that no byte range intersects
+
+
+def _cpu_module(nvox=(12, 10, 14), index_offset=(0, 0, 0), x_planes=None, dim=8):
+    from spatially_aware_ai_amd import ClipFusion
+    from test_gpu_parity import FakeClip
+
+    grid = syn.make_grid((12, 10, 14))
+    return ClipFusion(grid.origin, grid.voxel_size, torch.tensor(nvox), grid.trunc, False, FakeClip(dim), None, 10, 10,
+                      keep_xyz_world=False, index_offset=index_offset, x_planes=x_planes)
+
+
+def _bounds(fz, xyz, trunc):
+    return np.percentile(xyz, 1, axis=0).astype(np.float64) - trunc, np.percentile(xyz, 99, axis=0).astype(np.float64) + trunc
+
+
+def _centres(fz, off, n):
+    """First and last voxel centre of a box, per axis, in float64."""
+    origin = fz.origin.numpy().astype(np.float64)
+    off, n = np.asarray(off, dtype=np.float64), np.asarray(n, dtype=np.float64)
+    return origin + off * fz.voxel_size, origin + (off + n - 1) * fz.voxel_size
+
+
+# ---- lattice_box -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift", [(0.0, 0.0, 0.0), (-3.1, 0.4, 2.2), (5.0, -7.3, -0.05)])
+def test_lattice_box_is_the_smallest_box_of_the_lattice_that_contains_the_bounds(shift):
+    fz = _cpu_module()
+    rng = np.random.default_rng(3)
+    xyz = rng.normal(size=(4000, 3)) * np.array([0.9, 0.5, 1.3]) + np.array(shift)
+    lo, hi = _bounds(fz, xyz, fz.trunc)
+    off, n = lattice_box(fz, torch.from_numpy(xyz), union=False, multiple=1)
+    assert all(isinstance(v, int) for v in off + n) and min(n) > 0
+    first, last = _centres(fz, off, n)
+    assert (first <= lo).all() and (last >= hi).all(), "the box does not contain the percentile bounds"
+    # one voxel less on any side, and it no longer does
+    first_in, _ = _centres(fz, np.add(off, 1), n)
+    _, last_in = _centres(fz, off, np.subtract(n, 1))
+    assert (first_in > lo).all() and (last_in < hi).all(), "the box is larger than the snap asks for"
+    if shift[0] < 0:
+        assert off[0] < 0, "a cloud below the origin needs a negative offset"
+    # an explicit truncation distance widens it
+    off2, n2 = lattice_box(fz, xyz, trunc_m=4 * fz.trunc, union=False, multiple=1)
+    assert all(a <= b for a, b in zip(off2, off)) and all(a + c >= b + d for a, c, b, d in zip(off2, n2, off, n))
+
+
+def test_lattice_box_union_and_multiple():
+    fz = _cpu_module(nvox=(12, 10, 14), index_offset=(-2, 3, 0))
+    xyz = np.random.default_rng(4).normal(size=(2000, 3)) * 0.2 + np.array([2.0, 0.0, -1.5])
+    alone = lattice_box(fz, xyz, union=False, multiple=1)
+    off, n = lattice_box(fz, xyz, union=True, multiple=1)
+    for a in range(3):
+        lo = min(alone[0][a], fz.index_offset[a])
+        hi = max(alone[0][a] + alone[1][a], fz.index_offset[a] + int(fz.nvox[a]))
+        assert (off[a], n[a]) == (lo, hi - lo), "the union is the smallest box around both"
+    assert off[2] < 0 and off[0] == -2
+    for m in (4, 16, 5):
+        off_m, n_m = lattice_box(fz, xyz, union=True, multiple=m)
+        assert off_m == off, "rounding moves the high end only"
+        assert all(v % m == 0 and 0 <= v - w < m for v, w in zip(n_m, n))
+    # a cloud inside the current box leaves it as it is
+    small = np.zeros((10, 3)) + (_centres(fz, fz.index_offset, [int(v) for v in fz.nvox])[0] + 6 * fz.voxel_size)
+    assert lattice_box(fz, small, trunc_m=0.0, union=True, multiple=1) == (fz.index_offset, tuple(int(v) for v in fz.nvox))
+
+
+# ---- the identity the feature rests on ----------------------------------------------------------------------------------------
+def test_axis_tables_of_two_boxes_of_one_lattice_agree_bit_for_bit_on_shared_indices():
+    grid = syn.make_grid((24, 20, 28))
+    a_off, a_n = (0, 0, 0), (24, 20, 28)
+    for b_off, b_n in (((-5, 3, -9), (32, 20, 40)), ((7, -11, 2), (12, 36, 8)), ((-24, -20, -28), (48, 40, 56))):
+        ta, tb = _axis_tables(grid.origin, grid.voxel_size, a_n, a_off), _axis_tables(grid.origin, grid.voxel_size, b_n, b_off)
+        for k in range(3):
+            lo, hi = max(a_off[k], b_off[k]), min(a_off[k] + a_n[k], b_off[k] + b_n[k])
+            assert hi > lo
+            sa, sb = ta[k][lo - a_off[k]:hi - a_off[k]], tb[k][lo - b_off[k]:hi - b_off[k]]
+            assert sa.dtype == torch.float32 and torch.equal(sa.view(torch.int32), sb.view(torch.int32))
+
+
+# ---- the entry point's refusals, decided before anything is launched ----------------------------------------------------------
+def _pair(n_src=8, n_dst=8, dim=8, dtype=_abi.SAF_F32, classes=0):
+    src = fake_volume(n_src, dim, dtype, n_classes=classes, labels_one_hot=P if classes else None)
+    dst = fake_volume(n_dst, dim, dtype, n_classes=classes)
+    for f in ("tsdf", "tsdf_weight", "weight", "rgb", "clip_feat") + (("labels_one_hot",) if classes else ()):
+        setattr(dst, f, FAR)
+    return src, dst
+
+
+def _carry(src, dst, off=(100, 0, 0), aux=(None, None), counts=None):
+    """(status, message).  The default offset leaves no overlap: a call that passes the checks returns 0 with nothing launched."""
+    l = _lib.lib()
+    rc = l.saf_volume_carry(None if src is None else ctypes.byref(src), None if dst is None else ctypes.byref(dst), off[0], off[1],
+                            off[2], aux[0], aux[1], counts, None)
+    return rc, l.saf_last_error().decode()
+
+
+def test_carry_accepts_a_well_formed_pair_and_an_empty_overlap_is_ok():
+    for off in ((100, 0, 0), (0, -8, 0), (0, 0, 8), (2 ** 31 - 1, 0, 0), (-2 ** 31, 0, 0)):
+        assert _carry(*_pair(), off=off)[0] == 0
+    assert _carry(*_pair(classes=143))[0] == 0
+    assert _carry(*_pair(), aux=(P, FAR))[0] == 0
+    assert _carry(*_pair(dim=12, dtype=_abi.SAF_F16))[0] == 0
+
+
+def test_carry_refuses_nulls_and_bad_sizes():
+    src, dst = _pair()
+    assert _carry(None, dst)[0] == _abi.SAF_E_INVALID and _carry(src, None)[0] == _abi.SAF_E_INVALID
+    for which in (0, 1):
+        for f in ("tsdf", "tsdf_weight", "weight", "rgb", "clip_feat"):
+            pair = _pair()
+            setattr(pair[which], f, None)
+            rc, msg = _carry(*pair)
+            assert rc == _abi.SAF_E_INVALID and "NULL" in msg, (which, f)
+        for f in ("nx", "ny", "nz"):
+            for bad in (0, -3):
+                pair = _pair()
+                setattr(pair[which], f, bad)
+                assert _carry(*pair)[0] == _abi.SAF_E_INVALID, (which, f, bad)
+        pair = _pair(classes=143)
+        pair[which].labels_one_hot = None
+        assert _carry(*pair)[0] == _abi.SAF_E_INVALID
+        pair = _pair()
+        pair[which].nx, pair[which].ny, pair[which].nz = 2048, 1024, 1024  # 2^31 voxels
+        rc, msg = _carry(*pair)
+        assert rc == _abi.SAF_E_INVALID and "2^31" in msg
+    pair = _pair(dim=0)
+    assert _carry(*pair)[0] == _abi.SAF_E_INVALID
+
+
+def test_carry_refuses_volumes_that_differ_and_half_an_aux_pair():
+    for change in (dict(feat_dim=16), dict(feat_dtype=_abi.SAF_BF16), dict(n_classes=143, labels_one_hot=FAR)):
+        src, dst = _pair()
+        for k, v in change.items():
+            setattr(dst, k, v)
+        rc, msg = _carry(src, dst)
+        assert rc == _abi.SAF_E_INVALID and "differ" in msg, change
+    assert _carry(*_pair(), aux=(P, None))[0] == _abi.SAF_E_INVALID
+    rc, msg = _carry(*_pair(), aux=(None, FAR))
+    assert rc == _abi.SAF_E_INVALID and "pair" in msg
+
+
+def test_carry_refuses_a_destination_that_shares_bytes_with_its_source():
+    n, dim = 8, 8
+    sizes = {"tsdf": 4, "tsdf_weight": 4, "weight": 4, "rgb": 12, "clip_feat": 4 * dim, "labels_one_hot": 4 * 143}
+    for f, per_voxel in sizes.items():
+        span = n ** 3 * per_voxel
+        for delta, aliased in ((0, True), (span - 1, True), (-(span - 1), True), (span, False), (-span, False)):
+            src, dst = _pair(classes=143)
+            setattr(src, f, FAR // 2)
+            setattr(dst, f, FAR // 2 + delta)
+            rc, msg = _carry(src, dst)
+            assert (rc == _abi.SAF_E_INVALID and "out of place" in msg) if aliased else rc == 0, (f, delta)
+    span = 4 * n ** 3
+    assert _carry(*_pair(), aux=(FAR // 2, FAR // 2 + span - 4))[0] == _abi.SAF_E_INVALID
+    assert _carry(*_pair(), aux=(FAR // 2, FAR // 2 + span))[0] == 0
+    # the same name only: a destination's tsdf may sit where the source's weight does not reach ... and the whole volume on itself
+    src = fake_volume(8, 8)
+    assert _carry(src, src, off=(0, 0, 0))[0] == _abi.SAF_E_INVALID
+
+
+# ---- move_grid's own refusals ---------------------------------------------------------------------------------------------------
+def test_move_grid_refuses_slabs_stripes_and_bad_boxes_and_leaves_the_volume_alone():
+    fz = _cpu_module(nvox=(8, 10, 14), x_planes=[0, 1, 2, 3, 8, 9, 10, 11])
+    with pytest.raises(SafError, match="x_planes"):
+        fz.move_grid((0, 0, 0), (8, 10, 14))
+    fz = _cpu_module()
+    fz._shard_stripes = [(0, 100)]
+    with pytest.raises(SafError, match="stripes"):
+        fz.move_grid((1, 0, 0), (12, 10, 14))
+    fz = _cpu_module()
+    for nvox in ((0, 10, 14), (12, -1, 14), (2048, 1024, 1024)):
+        with pytest.raises(SafError, match="move_grid"):
+            fz.move_grid((0, 0, 0), nvox)
+    fz.__dict__["_poisoned"] = "a flush failed"
+    with pytest.raises(SafError, match="a flush failed"):
+        fz.move_grid((0, 0, 0), (12, 10, 14))
+    assert tuple(int(v) for v in fz.nvox) == (12, 10, 14) and fz.index_offset == (0, 0, 0) and fz._buffers["tsdf"].numel() == 12 * 10 * 14
+
+
+# ---- the restatement on itself ------------------------------------------------------------------------------------------------
+def test_restatement_moves_what_it_should_and_nothing_else():
+    rng = np.random.default_rng(0)
+    s_n, d_n, off, dim = (5, 4, 6), (7, 3, 6), (-1, 2, 3), 3
+
+    def vol(n, fill):
+        v = {"tsdf": np.full(n, fill, np.float32), "tsdf_weight": np.full(n, int(fill), np.int32), "weight": np.full(n, int(fill), np.int32),
+             "rgb": np.full(n + (3,), fill, np.float32), "clip_feat": np.full(n + (dim,), fill, np.float32), "aux": np.full(n, int(fill), np.int32)}
+        return v
+
+    src, dst = vol(s_n, 0.0), vol(d_n, -7.0)
+    src["weight"][:] = rng.integers(0, 2, s_n)
+    src["tsdf_weight"][:] = rng.integers(0, 2, s_n)
+    src["clip_feat"][:] = np.where(src["weight"][..., None] > 0, 1.0 + np.arange(np.prod(s_n)).reshape(s_n)[..., None], np.nan)
+    out, (rows, tsdf) = ref.carry(src, {k: v.copy() for k, v in dst.items()}, off)
+    inside, touched = ref.written_masks(src, d_n, off)
+    assert inside.sum() == 5 * 2 * 3 and rows == touched.sum() > 0 and tsdf > 0
+    for x in range(d_n[0]):
+        for y in range(d_n[1]):
+            for z in range(d_n[2]):
+                sx, sy, sz = x + off[0], y + off[1], z + off[2]
+                ok = 0 <= sx < s_n[0] and 0 <= sy < s_n[1] and 0 <= sz < s_n[2]
+                assert ok == inside[x, y, z]
+                assert out["weight"][x, y, z] == (src["weight"][sx, sy, sz] if ok else -7)
+                row = src["clip_feat"][sx, sy, sz] if ok and src["weight"][sx, sy, sz] > 0 else np.full(dim, -7.0)
+                assert np.array_equal(out["clip_feat"][x, y, z], row)
+    assert not np.isnan(out["clip_feat"]).any(), "a row of a weight-0 voxel was read"
+    assert ref.carry(src, dst, (9, 0, 0))[1] == (0, 0)
