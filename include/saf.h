@@ -666,6 +666,36 @@ int saf_object_stats(const saf_volume* vol, const int32_t* slot, int32_t n_objec
                      float* rgb_mean /*[K,3]*/, float* feat_mean /*[K,D]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Overlap of two labellings of one lattice (added under ABI 7: additive, the version number stays; new capability: the reference
+ * asks its in-situ classifier whether a newly found component "existed", handy_utils.py flood_fill_3d -- here the two versions of a
+ * scan are compared voxel by voxel, and objects.assign_identities decides on the host which object is which).
+ *   slot_a    [ax ay az] i32 and slot_b [bx by bz] i32: a dense object number per voxel, as for saf_object_stats (flat index
+ *             (x ny + y) nz + z).  Voxel n is a member of object k = slot[n] iff 0 <= k < n_a (n_b); any other value means no object.
+ *   mapping   the convention of saf_volume_carry: the two grids are boxes of one lattice, voxel (x, y, z) of `b` corresponds to
+ *             voxel (x + off_x, y + off_y, z + off_z) of `a`; the caller passes off = b's index offset - a's.  The OVERLAP is the
+ *             set of `b` voxels whose `a` voxel lies inside `a`.
+ *   pair      [n_a, n_b] i64: pair[i, j] = overlap voxels that are members of i in `a` and of j in `b`
+ *   in_a      [n_a] i64 members of i inside the overlap;  in_b [n_b] i64 likewise for `b`.  Members outside the overlap count
+ *             nowhere.  pair.sum(1) <= in_a and pair.sum(0) <= in_b: the rest faces voxels without an object on the other side.
+ *   workspace saf_object_overlap_workspace_bytes(n_a, n_b) bytes, 256-byte aligned (0 for a bad size): one (n_a + 1) x (n_b + 1)
+ *             table of 64-bit counters, row n_a / column n_b standing for "no object"
+ * Every output is written in full: the caller zeroes nothing.  An empty overlap gives zeros everywhere and SAF_OK.
+ * Determinism: 64-bit integer atomics only -- the counts are exact, and two calls return the same bytes whatever the grid or the
+ * scheduling.
+ * SAF_E_INVALID (on the host, nothing is launched) for a NULL slot_a / slot_b / pair / in_a / in_b, non-positive sizes, a grid of
+ * 2^31 voxels or more, n_a < 1 or n_b < 1, a workspace that is too small or not on a 256-byte boundary.  SAF_E_UNSUPPORTED for
+ * n_a n_b > 2^24: the dense table would exceed 128 MB (the cap; scenes hold hundreds of objects).
+ * Three launches (init, count, finish).  A wave takes 512 consecutive voxels of the flattened overlap box, z fastest; voxels that
+ * are no member on either side are dropped by a ballot, and the wave issues ONE atomic per distinct pair key of the chunk (objects
+ * are runs along z: a few as a rule), not one per voxel.  Both slots are read once per overlap voxel: 8 N_overlap bytes,
+ * beside 24 (n_a + 1)(n_b + 1) for the table's init and finish.
+ */
+size_t saf_object_overlap_workspace_bytes(int32_t n_a, int32_t n_b);
+int saf_object_overlap(const int32_t* slot_a, int32_t ax, int32_t ay, int32_t az, const int32_t* slot_b, int32_t bx, int32_t by,
+                       int32_t bz, int32_t off_x, int32_t off_y, int32_t off_z, int32_t n_a, int32_t n_b, int64_t* pair /*[n_a,n_b]*/,
+                       int64_t* in_a /*[n_a]*/, int64_t* in_b /*[n_b]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Rig front-end (added under ABI 6: additive, the version number stays; magicleap2_camera_match.py states the problem and the
  * metadata layout, not this arithmetic -- its per-pixel loop has no occlusion test, its relative pose is not mirrored, and cv2's
  * fixed-point remap is not in the build image: parity with it is unpinned).  A headset frame has a depth and a colour image from

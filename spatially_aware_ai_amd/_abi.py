@@ -222,6 +222,12 @@ PROTOTYPES = {
         C.c_int,
         [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp],
     ),
+    "saf_object_overlap_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "saf_object_overlap": (
+        C.c_int,
+        [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+         C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp],
+    ),
     "saf_pose_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "saf_pose_linearize": (
         C.c_int,

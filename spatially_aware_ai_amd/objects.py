@@ -10,7 +10,12 @@ per-object ``{"clip_feats", "rgb", "voxels"}`` that ``flood_fill_3d`` hands the 
   * ``describe_objects``  -- the same for a fusion module and its scene knowledge: an ``ObjectDescriptors``;
   * ``ObjectDescriptors.query`` -- the existing text-query scan over the K descriptor rows: "which object is the mug, where is
                              it, how big is it" without a heat map over 16.8 M voxels;
-  * ``merge_objects`` / ``mark_object_of_interest`` -- the reference's bookkeeping, optionally relabelling the grid.
+  * ``merge_objects`` / ``mark_object_of_interest`` -- the reference's bookkeeping, optionally relabelling the grid;
+  * ``object_overlap``    -- saf_object_overlap: the voxels every object of one labelling shares with every object of another
+                             labelling of the same lattice, on the HIP device;
+  * ``assign_identities`` / ``match_objects`` / ``carry_identities`` -- which object of a scan's new version is which object
+                             of the previous one (kept in place, moved, absorbed into a user's merge, new, missing), and the
+                             scene knowledge and index grid under the previous identities.
 """
 from __future__ import annotations
 
@@ -147,6 +152,7 @@ class ObjectDescriptors:
     origin: np.ndarray = field(default_factory=lambda: np.zeros(3))
     voxel_size: float = 1.0
     nvox: tuple = (0, 0, 0)
+    index_offset: tuple = (0, 0, 0)  # the grid's first voxel on the module's lattice (``origin`` already includes it)
 
     def __len__(self):
         return len(self.ids)
@@ -201,7 +207,8 @@ class ObjectDescriptors:
             count=count, n_fused=cat(self.n_fused, tot), weight_sum=cat(self.weight_sum, self.weight_sum[pos].sum()),
             bbox_min=bmin, bbox_max=bmax, coord_sum=coord, centroid_world=centroid, extent_world=extent,
             rgb=np.concatenate([self.rgb[keep], rgb[None]], axis=0),
-            feat=torch.cat([self.feat[keep], feat[None]], dim=0), origin=self.origin, voxel_size=self.voxel_size, nvox=self.nvox)
+            feat=torch.cat([self.feat[keep], feat[None]], dim=0), origin=self.origin, voxel_size=self.voxel_size, nvox=self.nvox,
+            index_offset=self.index_offset)
 
 
 def describe_objects(fusion, voxel_obj_idx, scene_knowledge, normalize="l2"):
@@ -226,18 +233,19 @@ def describe_objects(fusion, voxel_obj_idx, scene_knowledge, normalize="l2"):
     index = np.array([int(uo[i]["object_index"]) for i in ids], dtype=np.int64)
     origin = np.asarray(torch.as_tensor(fusion.origin).detach().cpu().numpy(), dtype=np.float64).reshape(3)
     voxel_size = float(fusion.voxel_size)
-    origin = origin + voxel_size * np.asarray(fusion.index_offset, dtype=np.float64)
+    index_offset = tuple(int(v) for v in fusion.index_offset)
+    origin = origin + voxel_size * np.asarray(index_offset, dtype=np.float64)
     if k == 0:
         z = lambda shape, dt: np.zeros(shape, dtype=dt)
         return ObjectDescriptors(ids, index, z(0, np.int64), z(0, np.int64), z(0, np.int64), z((0, 3), np.int32), z((0, 3), np.int32),
                                  z((0, 3), np.int64), z((0, 3), np.float64), z((0, 3), np.float64), z((0, 3), np.float32),
-                                 torch.zeros((0, d), dtype=torch.float32, device=dev), origin, voxel_size, nvox)
+                                 torch.zeros((0, d), dtype=torch.float32, device=dev), origin, voxel_size, nvox, index_offset)
     out = _object_stats(vol, dev, slot, k, d, mode, ("n_fused", "weight_sum", "coord_sum", "rgb", "feat"))
     h = {name: out[name].cpu().numpy() for name in ("count", "n_fused", "weight_sum", "bbox", "coord_sum", "rgb")}
     bmin, bmax = h["bbox"][:, :3].copy(), h["bbox"][:, 3:].copy()
     centroid, extent = ObjectDescriptors._world(origin, voxel_size, h["count"], h["coord_sum"], bmin, bmax)
     return ObjectDescriptors(ids, index, h["count"], h["n_fused"], h["weight_sum"], bmin, bmax, h["coord_sum"], centroid, extent,
-                             h["rgb"], out["feat"], origin, voxel_size, nvox)
+                             h["rgb"], out["feat"], origin, voxel_size, nvox, index_offset)
 
 
 def mark_object_of_interest(scene_knowledge, insitu_model, object_list):
@@ -302,3 +310,223 @@ def merge_objects(scene_knowledge, vertex_obj_idx, insitu_model, merge_list, new
         old = torch.tensor(old_index, dtype=voxel_obj_idx.dtype, device=voxel_obj_idx.device)
         voxel_obj_idx.masked_fill_(torch.isin(voxel_obj_idx, old), obj_index)
     return new_label, scene_knowledge
+
+
+# --------------------------------------------------------------------------------- identities across scan versions
+def object_overlap(slot_a, nvox_a, slot_b, nvox_b, offset, n_a, n_b):
+    """saf_object_overlap (include/saf.h) on two slot grids of one lattice (``object_slots``; int32, contiguous, on the HIP
+    device): voxel (x, y, z) of ``b`` is voxel (x, y, z) + ``offset`` of ``a``, ``offset`` = b's index offset - a's.  A dict of
+    device tensors: ``pair`` [n_a, n_b] i64 shared voxels, ``in_a`` [n_a] / ``in_b`` [n_b] i64 members inside the overlap."""
+    for t, name in ((slot_a, "slot_a"), (slot_b, "slot_b")):
+        require_cuda(t, name)
+        if not t.is_contiguous():
+            raise SafError(f"{name} must be contiguous")
+    na3, nb3 = tuple(int(v) for v in nvox_a), tuple(int(v) for v in nvox_b)
+    off = tuple(int(v) for v in offset)
+    n_a, n_b = int(n_a), int(n_b)
+    if slot_a.dtype != torch.int32 or slot_b.dtype != torch.int32 or slot_a.numel() != na3[0] * na3[1] * na3[2] or \
+            slot_b.numel() != nb3[0] * nb3[1] * nb3[2]:
+        raise ValueError("slot_a and slot_b must be int32 with nx ny nz entries of their grids")
+    if slot_a.device != slot_b.device:
+        raise ValueError("slot_a and slot_b live on different devices")
+    dev = slot_a.device
+    out = {"pair": torch.empty((max(n_a, 0), max(n_b, 0)), dtype=torch.int64, device=dev),
+           "in_a": torch.empty(max(n_a, 0), dtype=torch.int64, device=dev), "in_b": torch.empty(max(n_b, 0), dtype=torch.int64, device=dev)}
+    L = lib()
+    wsb = L.saf_object_overlap_workspace_bytes(n_a, n_b)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    p = _abi.ptr
+    with torch.cuda.device(dev):
+        rc = L.saf_object_overlap(p(slot_a), *na3, p(slot_b), *nb3, *off, n_a, n_b, p(out["pair"]), p(out["in_a"]), p(out["in_b"]),
+                                  p(ws), wsb, current_stream_ptr())
+    check(rc, "saf_object_overlap")
+    return out
+
+
+KIND_NEW, KIND_KEPT, KIND_ABSORBED, KIND_MOVED = 0, 1, 2, 3
+
+
+def _take_one_to_one(score, a_idx, b_idx, free_a, free_b, match_of_b, kind_of_b, kind):
+    """Greedy one-to-one matching of the candidates (a_idx[i], b_idx[i]) by descending score, then a, then b."""
+    for i in np.lexsort((b_idx, a_idx, -score)):
+        a, b = int(a_idx[i]), int(b_idx[i])
+        if free_a[a] and free_b[b]:
+            free_a[a] = free_b[b] = False
+            match_of_b[b], kind_of_b[b] = a, kind
+
+
+def assign_identities(pair, in_a, in_b, count_a, count_b, class_a, class_b, merged_a, cos, iou_min=0.25, contain_min=0.5,
+                      cos_min=0.9, size_ratio_min=0.5):
+    """Which new object ``b`` is which previous object ``a`` (host arrays, NumPy; nothing is launched): ``(match_of_b [n_b] i64,
+    kind_of_b [n_b] i64)`` -- an index into ``a`` or -1, and 0 new / 1 kept / 2 absorbed / 3 moved.  ``pair``, ``in_a``, ``in_b``
+    are ``object_overlap``'s counts, ``count_*`` the full member counts, ``class_*`` class ids, ``merged_a`` the previous objects'
+    ``merged`` flag, ``cos`` [n_a, n_b] the cosine of the two versions' descriptor rows.  Comparisons in fp64; ties go to the
+    smaller ``a``, then the smaller ``b``.  The four knobs are policy, not tolerances.
+
+    1. absorb (merged ``a`` only: a user's merge is not undone by the next scan): every ``b`` with a merged ``a`` such that
+       ``pair > 0`` and ``pair >= contain_min in_b`` goes to the ``a`` with the largest ``pair``; an ``a`` that absorbed takes no
+       part below.
+    2. in place: free pairs with ``pair > 0`` and ``pair >= iou_min (in_a + in_b - pair)``, by descending ``pair / union``,
+       greedily, one to one.  Class is not compared: a chair that version 2 calls a couch is still the same object.
+    3. moved: free ``a`` and ``b`` of one class with ``cos >= cos_min`` and ``min(count) >= size_ratio_min max(count)``, by
+       descending ``cos``, greedily, one to one.
+    Unmatched ``b`` are new; an ``a`` that no ``b`` names is missing."""
+    pair = np.asarray(pair, dtype=np.int64)
+    n_a, n_b = pair.shape
+    pf = pair.astype(np.float64)
+    in_a, in_b = np.asarray(in_a, dtype=np.float64).reshape(n_a), np.asarray(in_b, dtype=np.float64).reshape(n_b)
+    count_a, count_b = np.asarray(count_a, dtype=np.float64).reshape(n_a), np.asarray(count_b, dtype=np.float64).reshape(n_b)
+    class_a, class_b = np.asarray(class_a).reshape(n_a), np.asarray(class_b).reshape(n_b)
+    merged_a = np.asarray(merged_a, dtype=bool).reshape(n_a)
+    cos = np.asarray(cos, dtype=np.float64).reshape(n_a, n_b)
+    match_of_b, kind_of_b = np.full(n_b, -1, dtype=np.int64), np.zeros(n_b, dtype=np.int64)
+    free_a, free_b = np.ones(n_a, dtype=bool), np.ones(n_b, dtype=bool)
+    # 1. absorb
+    ok = merged_a[:, None] & (pair > 0) & (pf >= float(contain_min) * in_b[None, :])
+    if ok.any():
+        best = np.where(ok, pair, -1).argmax(axis=0)  # (argmax takes the first, i.e. smallest, a among equal counts)
+        for b in np.nonzero(ok.any(axis=0))[0]:
+            match_of_b[b], kind_of_b[b] = best[b], KIND_ABSORBED
+            free_b[b] = False
+        free_a[np.unique(match_of_b[kind_of_b == KIND_ABSORBED])] = False
+    # 2. in place
+    union = in_a[:, None] + in_b[None, :] - pf
+    ok = free_a[:, None] & free_b[None, :] & (pair > 0) & (pf >= float(iou_min) * union)
+    a_idx, b_idx = np.nonzero(ok)
+    _take_one_to_one(pf[a_idx, b_idx] / union[a_idx, b_idx], a_idx, b_idx, free_a, free_b, match_of_b, kind_of_b, KIND_KEPT)
+    # 3. moved
+    lo, hi = np.minimum(count_a[:, None], count_b[None, :]), np.maximum(count_a[:, None], count_b[None, :])
+    ok = free_a[:, None] & free_b[None, :] & (class_a[:, None] == class_b[None, :]) & (cos >= float(cos_min)) & \
+        (lo >= float(size_ratio_min) * hi)
+    a_idx, b_idx = np.nonzero(ok)
+    _take_one_to_one(cos[a_idx, b_idx], a_idx, b_idx, free_a, free_b, match_of_b, kind_of_b, KIND_MOVED)
+    return match_of_b, kind_of_b
+
+
+@dataclass
+class ObjectMatches:
+    """What ``match_objects`` decides: ids of the previous and of the new version's scene knowledge."""
+
+    kept: list = field(default_factory=list)           # [(prev_id, new_id, iou)]
+    absorbed: list = field(default_factory=list)       # [(prev_id, [new_ids])]: parts of a user's merge
+    moved: list = field(default_factory=list)          # [(prev_id, new_id, cos, displacement_world [3] f64)]
+    new: list = field(default_factory=list)            # [new_id]
+    missing: list = field(default_factory=list)        # [prev_id]
+    class_changed: list = field(default_factory=list)  # [prev_id] of kept objects whose class_id differs in the new version
+
+
+def match_objects(prev, new, overlap, knowledge_prev, knowledge_new, **knobs):
+    """``ObjectMatches`` of two versions of a scan: ``prev`` / ``new`` are their ``ObjectDescriptors`` (``describe_objects``),
+    ``overlap`` is ``object_overlap`` of their slot grids (None when either version has no object), ``knowledge_*`` supply each
+    object's ``class_id`` and the previous objects' ``merged`` flag; ``knobs`` are ``assign_identities``'s.  The cosine of the
+    descriptor rows is formed on the device (rows normalised, a row of zeros gives 0); the rule runs on the host.  A moved
+    object's ``displacement_world`` is new centroid - old centroid, formed on the lattice: voxel_size times the difference of the
+    two mean voxel indices, each counted from the lattice's voxel 0, in fp64."""
+    n_a, n_b = len(prev), len(new)
+    uo_a, uo_b = knowledge_prev["unique_objects"], knowledge_new["unique_objects"]
+    out = ObjectMatches()
+    if n_a == 0 or n_b == 0:
+        out.new, out.missing = list(new.ids), list(prev.ids)
+        return out
+    fa = torch.nan_to_num(prev.feat / prev.feat.norm(dim=1, keepdim=True), nan=0.0, posinf=0.0, neginf=0.0)
+    fb = torch.nan_to_num(new.feat.to(fa.device) / new.feat.to(fa.device).norm(dim=1, keepdim=True), nan=0.0, posinf=0.0, neginf=0.0)
+    cos = (fa @ fb.T).double().cpu().numpy()
+    pair, in_a, in_b = (overlap[k].cpu().numpy() for k in ("pair", "in_a", "in_b"))
+    class_a = np.array([int(uo_a[i]["class_id"]) for i in prev.ids], dtype=np.int64)
+    class_b = np.array([int(uo_b[i]["class_id"]) for i in new.ids], dtype=np.int64)
+    merged_a = np.array([bool(uo_a[i].get("merged")) for i in prev.ids], dtype=bool)
+    match_of_b, kind_of_b = assign_identities(pair, in_a, in_b, prev.count, new.count, class_a, class_b, merged_a, cos, **knobs)
+    parts = {}
+    for b in range(n_b):
+        a, kind = int(match_of_b[b]), int(kind_of_b[b])
+        if kind == KIND_KEPT:
+            union = int(in_a[a]) + int(in_b[b]) - int(pair[a, b])
+            out.kept.append((prev.ids[a], new.ids[b], float(pair[a, b]) / float(union)))
+            if class_a[a] != class_b[b]:
+                out.class_changed.append(prev.ids[a])
+        elif kind == KIND_ABSORBED:
+            parts.setdefault(a, []).append(new.ids[b])
+        elif kind == KIND_MOVED:
+            where = lambda d, k: d.coord_sum[k].astype(np.float64) / float(d.count[k]) + np.asarray(d.index_offset, dtype=np.float64)
+            out.moved.append((prev.ids[a], new.ids[b], float(cos[a, b]), float(new.voxel_size) * (where(new, b) - where(prev, a))))
+        else:
+            out.new.append(new.ids[b])
+    out.absorbed = [(prev.ids[a], parts[a]) for a in sorted(parts)]
+    named = set(int(a) for a in match_of_b if a >= 0)
+    out.missing = [prev.ids[a] for a in range(n_a) if a not in named]
+    return out
+
+
+def carry_identities(knowledge_prev, knowledge_new, voxel_obj_idx_new, matches):
+    """The bookkeeping that makes ``matches`` visible: ``(scene_knowledge, voxel_obj_idx)`` of the new version under the previous
+    version's identities.  Neither input dict nor ``voxel_obj_idx_new`` is changed.  The new objects are walked in
+    ``knowledge_new``'s order (discovery order):
+
+    * kept / moved: the entry is keyed by the PREVIOUS id and carries the previous ``object_index``, ``gt_label``,
+      ``user_modified`` and ``merged``; ``voxels`` (and ``mesh``) are the new entry's.  A ``user_modified`` object keeps its
+      ``class_label`` and ``color`` too; otherwise ``class_id``, ``class_label`` and ``color`` follow the new labelling.
+    * absorbed: one entry under the previous id with the previous labels; the parts' ``voxels`` joined in discovery order.
+    * new: the id counts on from a copy of the PREVIOUS ``object_counts`` (an id is never used again, not even a missing
+      object's); ``object_index`` counts down from below ``min(-1, every previous object_index)``.
+    ``voxel_obj_idx`` is relabelled through a lookup table on its device: every object's index marks exactly its ``voxels``.
+    ``unchanged_objects`` = kept + absorbed, ``moved_objects`` (entries gain ``displacement_world``), ``new_objects``, and
+    ``missing_objects`` = the previous entries of the missing objects (as flood_fill_3d fills it from ``scene_knowledge_prev``)."""
+    uo_prev, uo_new = knowledge_prev["unique_objects"], knowledge_new["unique_objects"]
+    role = {}
+    for prev_id, new_id, _ in matches.kept:
+        role[new_id] = ("kept", prev_id, None)
+    for prev_id, new_id, _, disp in matches.moved:
+        role[new_id] = ("moved", prev_id, disp)
+    for prev_id, new_ids in matches.absorbed:
+        for new_id in new_ids:
+            role[new_id] = ("absorbed", prev_id, None)
+    counts = dict(knowledge_prev.get("object_counts", {}))
+    next_index = min([-1] + [int(o["object_index"]) for o in uo_prev.values()]) - 1
+    unique, unchanged, moved, fresh = {}, {}, {}, {}
+    old_index, final_index = [], []
+    for new_id, entry in uo_new.items():
+        kind, prev_id, disp = role.get(new_id, ("new", None, None))
+        if kind == "new":
+            obj = dict(entry)
+            oid, class_label = _obj_counts(counts, entry["class_label"])
+            obj.update(class_label=class_label, gt_label=oid, object_index=next_index)
+            next_index -= 1
+            unique[oid] = fresh[oid] = obj
+        elif kind == "absorbed":
+            obj = unique.get(prev_id)
+            if obj is None:
+                obj = dict(uo_prev[prev_id])
+                obj.pop("mesh", None)
+                vox = entry["voxels"]
+                obj["voxels"] = list(vox) if isinstance(vox, list) else vox  # (_join_voxels appends to a list in place)
+                unique[prev_id] = unchanged[prev_id] = obj
+            else:
+                obj["voxels"] = _join_voxels(obj["voxels"], entry["voxels"])
+        else:
+            old = uo_prev[prev_id]
+            obj = dict(entry)
+            for key in ("object_index", "gt_label", "user_modified", "merged"):
+                obj[key] = old[key]
+            if old.get("user_modified"):
+                obj["class_label"], obj["color"] = old["class_label"], old.get("color")
+            if kind == "moved":
+                obj["displacement_world"] = [float(v) for v in disp]
+                moved[prev_id] = obj
+            else:
+                unchanged[prev_id] = obj
+            unique[prev_id] = obj
+        old_index.append(int(entry["object_index"]))
+        final_index.append(int(obj["object_index"]))
+    grid = torch.as_tensor(voxel_obj_idx_new)
+    if old_index:
+        vals, perm = torch.sort(torch.tensor(old_index, dtype=torch.int64, device=grid.device))
+        to = torch.tensor(final_index, dtype=torch.int64, device=grid.device)[perm]
+        f = grid.reshape(-1).long()
+        pos = torch.searchsorted(vals, f).clamp_(max=len(old_index) - 1)
+        grid = torch.where(vals[pos] == f, to[pos], f).to(grid.dtype).view(grid.shape)
+    else:
+        grid = grid.clone()
+    knowledge = dict(knowledge_new)
+    knowledge.update(unique_objects=unique, object_counts=counts, unchanged_objects=unchanged, moved_objects=moved, new_objects=fresh,
+                     missing_objects={i: uo_prev[i] for i in matches.missing})
+    return knowledge, grid

@@ -48,6 +48,7 @@ class SceneResult:
     seconds: dict = field(default_factory=dict)
     engine: TextQueryEngine | None = None
     objects: object | None = None  # objects.ObjectDescriptors, computed by the first object_query
+    object_matches: object | None = None  # objects.ObjectMatches of extend_scene(keep_identities=True)
 
     def text_query(self, clip_model, text):
         """``clip_text_query`` (clip_seem_fusion.py:482-561): RGBA heat map over the scene mesh, or None."""
@@ -175,9 +176,11 @@ def _fuse_one_by_one(fusion, dataset, config, device, num_workers):
 
 
 def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, scan_version, out_dir, object_meshes,
-                  marching_cubes, python_lists):
+                  marching_cubes, python_lists, prev=None):
     """The stages behind the fusion loop (clip_seem_fusion.py:315-424, :563-607): labels, objects, the scene mesh, per-object
-    meshes, artefacts -- shared by ``reconstruct_scene`` and ``extend_scene``.  ``clk`` has just lapped the fusion."""
+    meshes, artefacts -- shared by ``reconstruct_scene`` and ``extend_scene``.  ``clk`` has just lapped the fusion.  ``prev``
+    (``_describe_version`` of the previous version, or None): the discovered objects take the previous version's identities
+    before anything is built from their indices."""
     # ---- the volume's artefacts (save_files_and_broadcast, :566-581) start now, on a thread of their own: nothing below writes
     #      clip_feat or rgb (the lap above synchronised the device; ctypes releases the interpreter lock for the whole write)
     writer = None
@@ -207,6 +210,11 @@ def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, sca
     # ---- objects (flood_fill_3d, :341-348) and the attributes the manager sets from outside (:351-372)
     scene_knowledge, voxel_obj_idx = discover_objects(onehot_to_index, class_names, class_colors, arrays=not python_lists)
     scene_knowledge["scan_version"] = scan_version
+    matches = None
+    if prev is not None:
+        clk.lap("objects")
+        scene_knowledge, voxel_obj_idx, matches = _carry_version(fusion, prev, scene_knowledge, voxel_obj_idx)
+        clk.lap("identities")
     fusion.unique_objects = scene_knowledge["unique_objects"]
     fusion.voxel_obj_idx = voxel_obj_idx
     seg_color = torch.clone(fusion.rgb).view(*[int(v) for v in fusion.nvox], -1)
@@ -233,7 +241,7 @@ def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, sca
             scene_knowledge["unique_objects"][obj_key]["mesh"] = None if len(of_) < 10 else mesh
         clk.lap("object_meshes")
     res = SceneResult(fusion, origin, nvox, xyz, onehot_to_index, scene_knowledge, voxel_obj_idx, verts, faces, vertex_colors,
-                      vertex_clip_feats, vertex_obj_idx, segmentation_color)
+                      vertex_clip_feats, vertex_obj_idx, segmentation_color, object_matches=matches)
     # ---- artefacts (save_files_and_broadcast, :563-607)
     if out_dir is not None:
         res.paths = {"vertex_clip_feats": save_npy(os.path.join(out_dir, "vertex_clip_feats.npy"), torch.as_tensor(vertex_clip_feats)),
@@ -255,6 +263,35 @@ def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, sca
         res.paths.update(wpaths)
         clk.lap("save_volume_wait")
     return res
+
+
+def _describe_version(fusion, result, knobs):
+    """What ``_carry_version`` needs of the version ``result`` describes, taken while ``fusion`` still holds that version's box:
+    the objects' descriptors, their slot grid and the box."""
+    from .objects import describe_objects, object_slots
+
+    desc = describe_objects(fusion, result.voxel_obj_idx, result.scene_knowledge)
+    dev = fusion._buffers["weight"].device
+    slot, _ = object_slots(torch.as_tensor(result.voxel_obj_idx).to(dev), result.scene_knowledge)
+    return {"desc": desc, "slot": slot.contiguous(), "index_offset": tuple(int(v) for v in fusion.index_offset),
+            "nvox": tuple(int(v) for v in fusion.nvox), "knowledge": result.scene_knowledge, "knobs": dict(knobs or {})}
+
+
+def _carry_version(fusion, prev, scene_knowledge, voxel_obj_idx):
+    """The new labelling under the previous version's identities (objects.py): descriptors of the new objects, the
+    overlap table of the two slot grids on their shared lattice, the match, the bookkeeping."""
+    from .objects import carry_identities, describe_objects, match_objects, object_overlap, object_slots
+
+    desc = describe_objects(fusion, voxel_obj_idx, scene_knowledge)
+    overlap = None
+    if len(prev["desc"]) and len(desc):
+        slot, _ = object_slots(voxel_obj_idx, scene_knowledge)
+        off = tuple(n - o for n, o in zip(fusion.index_offset, prev["index_offset"]))
+        overlap = object_overlap(prev["slot"], prev["nvox"], slot.contiguous(), tuple(int(v) for v in fusion.nvox), off,
+                                 len(prev["desc"]), len(desc))
+    matches = match_objects(prev["desc"], desc, overlap, prev["knowledge"], scene_knowledge, **prev["knobs"])
+    scene_knowledge, voxel_obj_idx = carry_identities(prev["knowledge"], scene_knowledge, voxel_obj_idx, matches)
+    return scene_knowledge, voxel_obj_idx, matches
 
 
 def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class_colors=None, device="cuda", out_dir=None,
@@ -296,7 +333,8 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
 
 
 def extend_scene(result, dataset, config, clip_model, seg_model, class_names, class_colors=None, out_dir=None, max_depth=4,
-                 num_workers=0, object_meshes=True, marching_cubes=None, python_lists=False, multiple=4):
+                 num_workers=0, object_meshes=True, marching_cubes=None, python_lists=False, multiple=4, keep_identities=False,
+                 identity_knobs=None):
     """A later version of a scan: fuse its NEW frames (``dataset`` holds only those) into ``result.fusion`` and run the stages
     behind the fusion again.  The reference's manager fuses every frame of every version into a new grid (``/reprocess_scan``,
     ``get_path(config, curr_ver, ...)``): the backbones, which cost far more than the fusion, see the whole scan again.  Here the
@@ -306,9 +344,17 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     the frames into the new box from the start (in the frame-ordered form; the default form within its own rounding).
 
     ``clip_model`` / ``seg_model`` replace the module's backbones when they are other objects than the ones it holds; the other
-    arguments are ``reconstruct_scene``'s.  Objects are discovered anew from the new labels: an object keeps no identity across
-    versions.  Returns a new ``SceneResult`` around the same module -- ``result`` itself describes a box the module no longer
-    holds --; ``scene_knowledge["scan_version"]`` counts on, ``seconds`` gains ``move_grid``."""
+    arguments are ``reconstruct_scene``'s.  Objects are discovered anew from the new labels; by default an object keeps no
+    identity across versions.  Returns a new ``SceneResult`` around the same module -- ``result`` itself describes a box the module
+    no longer holds --; ``scene_knowledge["scan_version"]`` counts on, ``seconds`` gains ``move_grid``.
+
+    ``keep_identities``: the new version's objects are matched against ``result``'s (``objects.match_objects``: kept in place by
+    voxel overlap, absorbed into a user's merge, moved by descriptor, new, missing; ``identity_knobs`` are
+    ``objects.assign_identities``'s thresholds) and take their ids, indices, user labels and merges
+    (``objects.carry_identities``) before the mesh and the per-object meshes are built: ``scene_knowledge`` gains
+    ``unchanged_objects``, ``moved_objects``, ``new_objects`` and ``missing_objects`` without a trained in-situ model, the result
+    ``object_matches``, ``seconds`` ``identities``.  The fused volume is the same either way.  A float16 module is refused
+    (``describe_objects``)."""
     clk = _Clock()
     clk.start()
     fusion = result.fusion
@@ -320,6 +366,10 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     xyz_new, _ = backproject_pcd(dataset, batch_size=1, num_workers=num_workers, device="cpu", max_depth=max_depth)
     index_offset, nvox = lattice_box(fusion, xyz_new, union=True, multiple=multiple)
     clk.lap("bounds")
+    prev = None
+    if keep_identities:  # the previous version's objects, described while the module still holds their box
+        prev = _describe_version(fusion, result, identity_knobs)
+        clk.lap("identities")
     fusion.move_grid(index_offset, nvox)
     clk.lap("move_grid")
     host = _fuse_one_by_one(fusion, dataset, config, device, num_workers)
@@ -328,6 +378,6 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     clk.seconds["fuse_host_split"] = {k: round(v, 4) for k, v in host.items()}
     version = int(result.scene_knowledge.get("scan_version", 0)) + 1
     res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, xyz_new)), clk, class_names, class_colors, version,
-                        out_dir, object_meshes, marching_cubes, python_lists)
+                        out_dir, object_meshes, marching_cubes, python_lists, prev=prev)
     res.seconds = clk.seconds
     return res
