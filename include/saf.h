@@ -384,6 +384,21 @@ enum saf_query_normalize {
  * scales (per label; per feature row, following the row's running maximum), 16-bit features as one piece: a score is within
  * 3 x 2^-22 of sum_k |f_k t_k| of the exact dot product for rows and labels of any magnitude the dtype holds (the reference's scores
  * are compared at 1e-4).  SAF_Q_SPLIT=0 in the environment (read per call): the exact-fp32 matrix instructions instead.
+ *
+ * Rows with an inf or a NaN in them (fp16 fusion can leave them: SAF_F16 above) -- a row is "bad" when it holds an inf or a NaN.
+ * On every route of the dispatch (one wave per row, the exact-fp32 and the split matrix scans, blocks of labels with their
+ * finishing pass), for `out` and for `out_last`:
+ *   SAF_NORM_L2        a bad row is the all-zero row (clip_seem_fusion.py:507-511, nan_to_num of f / |f|): SAF_Q_SCORES gives 0.0
+ *                      in every column, SAF_Q_SOFTMAX 1 / n_text, SAF_Q_SURGERY 0.0 (the zero row's value); a bad row 0 gives the
+ *                      surgery weights of the zero row (every weight 1);
+ *   SAF_NORM_NONE, SAF_NORM_L2_CLAMP   no nan_to_num in the reference: every output of a bad row is the IEEE result and not
+ *                      finite.  Whether it is NaN or an infinity depends on the route (the split scans cut an inf into the pieces
+ *                      hi = inf, lo = NaN and give NaN where exact arithmetic has an infinity); an infinity has the exact
+ *                      result's sign;
+ *   in every mode all other rows' outputs are bit for bit what they are without the bad rows, and out_last is the last column of
+ *   the same call bit for bit.
+ * Not covered by this rule: finite rows whose fp32 sum of squares overflows or underflows (the factor 1 / |f| is then 0 or
+ * infinite where the exact norm is not), and text rows that are not finite.
  */
 int saf_query_scan(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride,
                    int32_t feat_dim, const float* text, int32_t n_text, int64_t text_stride,
@@ -405,6 +420,15 @@ size_t saf_query_workspace_bytes(int32_t n_text, int32_t epilogue);
  *              top-k and softmax maximum / denominator between blocks of 64 (32 at feat_dim > 512) labels
  * Numerics as saf_query_scan: the split scan for feat_dim % 16 == 0 (SAF_Q_SPLIT=0: exact fp32), exact fp32 matrix instructions for
  * feat_dim % 8 == 0; other widths (or rows not on 16-byte boundaries) one wave per row, fp32.
+ *
+ * Rows with an inf or a NaN in them ("bad" rows, as at saf_query_scan), on every route:
+ *   SAF_NORM_L2        a bad row is the all-zero row: every score is 0, so out_index is 0 .. k - 1 in that order (equal scores: the
+ *                      smaller label first) and out_prob is fp32(1) / fp32(n_text) each, within one fp32 ulp;
+ *   SAF_NORM_NONE, SAF_NORM_L2_CLAMP   the scores are the IEEE results.  A NaN score is never chosen: a row whose scores are all
+ *                      NaN reports out_index -1 and out_prob 0 in all k places.  Any other bad row reports labels in [-1, n_text),
+ *                      none of them twice (-1 where fewer than k scores are not NaN); its out_prob need not be finite;
+ *   in every mode all other rows' labels and probabilities are bit for bit what they are without the bad rows.
+ * Not covered: finite rows whose fp32 sum of squares overflows or underflows, and text rows that are not finite.
  */
 size_t saf_query_topk_workspace_bytes(int64_t n_rows, int32_t n_text, int32_t k);
 int saf_query_topk(const void* feats, int32_t feat_dtype, int64_t n_rows, int64_t feat_stride, int32_t feat_dim, const float* text,

@@ -215,7 +215,7 @@ __device__ __forceinline__ T row_of_half(T v, int src, int h) {
 }
 
 // ---- epilogue on the MFMA accumulator layout: this lane holds column n = m (+32 t) of 16 rows.  `inv`: the factor of row m
-// (1 / norm); CS (the split scan): the row's and the columns' power-of-two scales 2^rexp, 2^cexp undone by one v_ldexp_f32,
+// (1 / norm), `l2`: the mode is SAF_NORM_L2; CS (the split scan): the row's and the columns' power-of-two scales 2^rexp, 2^cexp undone by one v_ldexp_f32,
 // which cannot leave fp32's range half-way the way two multiplications can.
 // ---- top-k labels per row (saf_query_topk; eval_scannet_segmentation.py:546-561): the scan's epilogue keeps, per row, the k best
 // (score, label) pairs and the softmax's running maximum and denominator.  Over more than one block of labels the state travels
@@ -336,8 +336,8 @@ __device__ __forceinline__ float row_inverse(float ss, int normalize) {
 }
 
 template <int EPI, int TILES, bool CS>
-__device__ __forceinline__ void scan_epilogue(const f32x16 (&acc)[TILES], float inv, int rexp, const int (&cexp)[TILES], int64_t tile,
-                                              int64_t n_rows, int L, float scale, const float (&wl)[TILES],
+__device__ __forceinline__ void scan_epilogue(const f32x16 (&acc)[TILES], float inv, bool l2, int rexp, const int (&cexp)[TILES],
+                                              int64_t tile, int64_t n_rows, int L, float scale, const float (&wl)[TILES],
                                               float* __restrict__ out, float* __restrict__ out_last, int64_t out_stride,
                                               int out_col0, float* __restrict__ stage = nullptr, const TopkArgs& tk = TopkArgs{}) {
   const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
@@ -351,13 +351,16 @@ __device__ __forceinline__ void scan_epilogue(const f32x16 (&acc)[TILES], float 
     const int mi = (i & 3) + 8 * (i >> 2) + 4 * h;  // row of accumulator register i in this half
     const float inv_i = row_of_half(inv, (i & 3) + 8 * (i >> 2), h);
     const int rexp_i = CS ? row_of_half(rexp, (i & 3) + 8 * (i >> 2), h) : 0;
+    // SAF_NORM_L2 (`l2`): a row whose factor is 0 -- all zero, or with an inf or a NaN in it (row_inverse) -- is the all-zero row,
+    // nan_to_num of f / |f| (clip_seem_fusion.py:507-511): it scores 0, where acc * 0 of a non-finite acc is NaN.  One flag per row.
+    const bool zero_i = l2 && inv_i == 0.0f;
     const int64_t r = tile * 32 + mi;
     float val[TILES];
     bool ok[TILES];
 #pragma unroll
     for (int t = 0; t < TILES; ++t) {
       ok[t] = (m + 32 * t) < L;
-      val[t] = acc[t][i] * inv_i;  // cosine score S[r][n]
+      val[t] = zero_i ? 0.0f : acc[t][i] * inv_i;  // cosine score S[r][n]
       if (CS) val[t] = ldexpf(val[t], -(rexp_i + cexp[t]));
     }
     if constexpr (EPI == EPI_TOPK) {
@@ -512,8 +515,8 @@ __global__ __launch_bounds__(TH) void query_mfma_kernel(const void* __restrict__
     }
     ss += __shfl_xor(ss, 32);  // both halves of row m
     const int none[TILES] = {};
-    scan_epilogue<EPI, TILES, false>(acc, row_inverse(ss, normalize), 0, none, tile, n_rows, L, scale, wl, out, out_last, out_stride, out_col0,
-                                     nullptr, tk);
+    scan_epilogue<EPI, TILES, false>(acc, row_inverse(ss, normalize), normalize == SAF_NORM_L2, 0, none, tile, n_rows, L, scale, wl, out,
+                                     out_last, out_stride, out_col0, nullptr, tk);
   }
 }
 
@@ -721,8 +724,8 @@ __global__ __launch_bounds__(TH, 2) void query_split_kernel(const void* __restri
       step(a0, a1, k0 >> 4);
     }
     ss = other_half_sum(ss);  // both halves of row m
-    scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), re, ce, tile, n_rows, L, scale, wl, out, out_last,
-                                    out_stride, out_col0, stage, tk);
+    scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), normalize == SAF_NORM_L2, re, ce, tile, n_rows, L, scale, wl, out,
+                                    out_last, out_stride, out_col0, stage, tk);
   }
 }
 
@@ -909,8 +912,8 @@ __global__ __launch_bounds__(TH, 2) void query_split16_kernel(const void* __rest
       step(a, p);
     }
     ss = other_half_sum(ss);  // both halves of row m
-    scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), re, ce, tile, n_rows, L, scale, wl, out, out_last,
-                                    out_stride, out_col0, stage, tk);
+    scan_epilogue<EPI, TILES, true>(acc, row_inverse(ss, normalize), normalize == SAF_NORM_L2, re, ce, tile, n_rows, L, scale, wl, out,
+                                    out_last, out_stride, out_col0, stage, tk);
   }
 }
 
