@@ -563,7 +563,8 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
  * A fused volume carried into another box of the SAME lattice (additive under ABI 7; new capability, nothing to mirror in the
  * reference: its manager re-fuses every frame of a scan into a new grid when the scan grows, get_path(config, curr_ver, ...)).
  * `src` and `dst` are two boxes of one lattice -- same origin, same voxel size, corners that differ by whole voxels -- so the pass
- * is a copy and nothing is recomputed; resampling, coarsening and blending two volumes are not offered.
+ * is a copy and nothing is recomputed; resampling and coarsening are not offered (blending two volumes of
+ * one lattice: saf_volume_absorb below).
  *   mapping   destination voxel (x, y, z) corresponds to source voxel (x + off_x, y + off_y, z + off_z); the caller passes
  *             off = dst's index offset - src's.  The OVERLAP is the set of destination voxels whose source voxel lies inside
  *             `src`.  A destination voxel outside the overlap is not touched: every buffer keeps its bytes there.
@@ -587,6 +588,42 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
  */
 int saf_volume_carry(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
                      const int32_t* aux_src, int32_t* aux_dst, uint64_t* counts, void* stream);
+
+/*
+ * A second fused volume of the SAME lattice absorbed into this one: blended by weights (additive under ABI 7; new capability,
+ * nothing to mirror in the reference, which fuses every frame of the second scan again).  Mapping and
+ * overlap are saf_volume_carry's: destination voxel (x, y, z) corresponds to source voxel (x + off_x, y + off_y, z + off_z), the
+ * caller passes off = dst's index offset - src's.  `dst` is updated IN PLACE over the overlap; outside it no byte of `dst` changes;
+ * `src` is only read.  Both volumes are running means (SAF_RUNNING_MEAN) of the same truncation distance: the pass does not
+ * inspect trunc or the axis tables.
+ *   per voxel  the feature side (ws, wd = the source's and the destination's `weight`; it owns weight, the three rgb floats, the
+ *             feature row and, with n_classes > 0, the label histogram row) and the TSDF side (`tsdf_weight`; it owns tsdf_weight
+ *             and tsdf) are treated independently, by the same three cases:
+ *   ws == 0   nothing of that side is written: the destination keeps its bytes, whatever they are.  The source's row is not read
+ *             (after a deferred clear it holds stale data).
+ *   wd == 0   (ws > 0) a copy, as in carry: the destination takes the source's bytes.  The destination's old row is NOT READ:
+ *             after a deferred clear it is stale, and a weight-0 row that is never written stays owed that clear.
+ *   blend     (ws > 0, wd > 0) w' = wd + ws (int32; not checked for overflow: these are frame counts), r = 1.0f / (float)w' by
+ *             IEEE division, cs = (float)ws * r, cd = (float)wd * r, and every rgb and feature channel (and tsdf) becomes
+ *             x' = xs * cs + xd * cd: two separately rounded products, one rounded sum, no FMA.  16-bit rows (SAF_BF16, SAF_F16)
+ *             are widened exactly, computed in fp32 and narrowed with one round-to-nearest-even.  The label histogram is an int32
+ *             add.  weight = w'.  NaN and inf travel as IEEE arithmetic carries them.  With ws == 1 this is the running-mean step
+ *             of saf_fuse_frames for weight, rgb, feature rows and labels; the forward sweep's TSDF uses the hardware reciprocal
+ *             and so differs from this one by rounding (the TSDF is compared at 1e-4 throughout).
+ *   counts    device u64[4], ADDED to (may be NULL): [0] rows blended, [1] rows copied, [2] tsdf voxels blended, [3] tsdf voxels
+ *             copied.  Integer atomics, one per wave and counter: exact whatever the scheduling.
+ * SAF_E_INVALID (on the host, nothing is launched) for everything saf_volume_carry refuses -- a NULL src / dst or volume buffer,
+ * non-positive sizes or feat_dim, a grid of 2^31 voxels or more, feat_dim, feat_dtype or n_classes that differ, any destination
+ * buffer whose byte range intersects the source buffer of the same name -- and for a feature or label buffer that is not aligned
+ * to its element type.  SAF_E_UNSUPPORTED if either accum_mode is SAF_SUM.  An empty overlap is SAF_OK with nothing launched.
+ * One launch, carry's shape: a wave takes 64 consecutive voxels of the flattened overlap box, two ballots name the rows to copy and
+ * the rows to blend, and the wave takes them one after the other, 16 bytes per lane where the row pitch and both bases allow it,
+ * else 4 or 2; a blended row's loads (both rows) are issued before its arithmetic.  No LDS, no scratch, no floating-point atomics.
+ * Per call 28 N_overlap bytes are read from each volume and at most 28 N_overlap written; per copied row one row (feature + label
+ * bytes) is read and one written, per blended row two are read and one written.
+ */
+int saf_volume_absorb(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
+                      uint64_t* counts, void* stream);
 
 /*
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for

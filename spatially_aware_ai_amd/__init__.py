@@ -17,6 +17,7 @@ __all__ = [
     "scene_bounds",
     "lattice_box",
     "GridMove",
+    "GridAbsorb",
     "label_components",
     "discover_objects",
     "evaluation",
@@ -36,7 +37,7 @@ __all__ = [
 
 
 def __getattr__(name):
-    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove"):
+    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove", "GridAbsorb"):
         from . import clipfusion as _m
 
         return getattr(_m, name)

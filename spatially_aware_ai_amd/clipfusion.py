@@ -9,6 +9,7 @@ Same names, arguments and error behaviour as the reference classes so that its c
   * ``get_pix_vecs``    -- reference clipfusion.py:497-507
   * ``scene_bounds``    -- the bounds arithmetic of clipfusion.py:1098-1106
   * ``lattice_box`` / ``move_grid`` -- not in the reference: a volume moved by whole voxels on its own lattice
+  * ``absorb`` -- not in the reference: a second volume of the same lattice blended in by weights
 
 PyTorch is plumbing here (device memory, streams, the backbone GEMMs); the fusion loop and the
 query scan are the hand-written HIP kernels behind ``include/saf.h``.  There is no CPU
@@ -617,6 +618,96 @@ class _FusionVolumeMixin:
                         rows_carried=counts[0], rows_dropped=before[0] - counts[0],
                         tsdf_carried=counts[1], tsdf_dropped=before[1] - counts[1])
 
+    def _absorb_refusals(self, other):
+        """``absorb``'s refusals, decided before either volume is touched."""
+        if other is self:
+            raise SafError("absorb: a volume cannot absorb itself")
+        if not isinstance(other, _FusionVolumeMixin):
+            raise SafError(f"absorb: the other volume must be a fusion module, got {type(other).__name__}")
+        for who, m in (("this", self), ("the other", other)):
+            if m.x_planes is not None:
+                raise SafError(f"absorb() needs boxes of consecutive x-planes: {who} module was built with x_planes")
+            if getattr(m, "_shard_stripes", None) is not None:
+                raise SafError(f"absorb: {who} volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
+                               "(distributed.gather_shards, or merge_volumes(..., gather=True)) first")
+            m._check_poisoned()
+        a, b = self._buffers, other._buffers
+        if a["tsdf"].device != b["tsdf"].device:
+            raise SafError(f"absorb: the volumes are on different devices ({a['tsdf'].device} and {b['tsdf'].device})")
+        o_a = torch.as_tensor(self.origin).detach().cpu().to(torch.float32).reshape(-1)
+        o_b = torch.as_tensor(other.origin).detach().cpu().to(torch.float32).reshape(-1)
+        # (TSDF values are in units of trunc: blending two truncation distances would be wrong)
+        if o_a.shape != o_b.shape or not torch.equal(o_a, o_b) or float(self.voxel_size) != float(other.voxel_size) or \
+                float(self.trunc) != float(other.trunc):
+            raise SafError("absorb: the volumes are not on the same lattice (origin, voxel_size and trunc must be equal): "
+                           f"{o_a.tolist()} / {float(self.voxel_size)} / {float(self.trunc)} and "
+                           f"{o_b.tolist()} / {float(other.voxel_size)} / {float(other.trunc)}")
+        classes = lambda bufs: 0 if bufs.get("labels_one_hot") is None else int(bufs["labels_one_hot"].shape[1])
+        if int(self.n_clip_feats) != int(other.n_clip_feats) or a["clip_feat"].dtype != b["clip_feat"].dtype or \
+                classes(a) != classes(b) or bool(self._rgb_bilinear) != bool(other._rgb_bilinear):
+            raise SafError("absorb: the volumes differ in feature width, feature dtype, classes or rgb sampling "
+                           f"({int(self.n_clip_feats)} / {a['clip_feat'].dtype} / {classes(a)} / {bool(self._rgb_bilinear)} and "
+                           f"{int(other.n_clip_feats)} / {b['clip_feat'].dtype} / {classes(b)} / {bool(other._rgb_bilinear)})")
+        if self.accum_mode != _abi.SAF_RUNNING_MEAN or other.accum_mode != _abi.SAF_RUNNING_MEAN:
+            raise SafError("absorb: running means only: a SAF_SUM volume belongs to the multi-rank job, whose merge adds its sums")
+
+    def absorb(self, other, grow=True, multiple=4):
+        """Take in what ``other`` -- a second module fused separately on the SAME lattice (equal ``origin``, ``voxel_size`` and
+        ``trunc``; boxes that differ by whole voxels) -- has fused: per voxel and side, a count of 0 in ``other`` changes nothing, a
+        count of 0 here takes ``other``'s values, and two positive counts blend by weights, the running mean of all the frames
+        within fp32 rounding (saf_volume_absorb, include/saf.h).  ``other`` is only read and stays as it is.
+
+        ``grow``: if ``other``'s box is not inside this one's, the volume is first moved (``move_grid``) to the box around both,
+        ``nvox`` rounded up at the high end to a multiple of ``multiple`` as ``lattice_box`` does; with ``grow=False`` only the
+        overlap is absorbed.  Frames still queued behind either module's ``integrate()`` are fused first; a deferred clear of
+        either stays owed.  ``voxel_obj_idx`` and ``objects_segmentation_color`` describe a labelling the volume no longer has
+        and are deleted.  Returns a ``GridAbsorb``; nothing is read back here.  ``SafError``, with both volumes unchanged, for
+        ``other is self``, a module built with ``x_planes``, holding only reduce-scattered stripes or poisoned, another device,
+        another lattice, a different feature width, feature dtype, class count or rgb sampling, and a ``SAF_SUM`` volume."""
+        self._absorb_refusals(other)
+        require_cuda(self._buffers["clip_feat"], "the fusion volume")
+        # the queued frames of both; this module's session goes as in move_grid, the other's only finishes.  A deferred clear of
+        # either stays owed: the pass reads no row of a weight-0 voxel, and writes every row whose voxel gains a weight
+        self._flush_pending(final=True)
+        q = self.__dict__["_queue"]
+        q.wait(self)
+        q.close()
+        other._flush_pending(final=True)
+        other.__dict__["_queue"].wait(other)
+        o_off, o_n = other.index_offset, tuple(int(v) for v in other.nvox)
+        s_off, s_n = self.index_offset, tuple(int(v) for v in self.nvox)
+        move = None
+        if grow and not all(s_off[a] <= o_off[a] and o_off[a] + o_n[a] <= s_off[a] + s_n[a] for a in range(3)):
+            m = max(int(multiple), 1)
+            lo = tuple(min(s_off[a], o_off[a]) for a in range(3))
+            hi = tuple(max(s_off[a] + s_n[a], o_off[a] + o_n[a]) for a in range(3))
+            move = self.move_grid(lo, tuple((hi[a] - lo[a] + m - 1) // m * m for a in range(3)))
+            s_off, s_n = self.index_offset, tuple(int(v) for v in self.nvox)
+        # (_buffers, never attribute access: that would pay a deferred clear)
+        dev = self._buffers["tsdf"].device
+        ob = other._buffers
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+            before = torch.stack(((ob["weight"] > 0).sum(), (ob["tsdf_weight"] > 0).sum()))
+            off = tuple(s_off[a] - o_off[a] for a in range(3))
+            check(lib().saf_volume_absorb(C.byref(other._c_volume(for_fuse=True)), C.byref(self._c_volume(for_fuse=True)), off[0],
+                                          off[1], off[2], _abi.ptr(counts), stream.cuda_stream), "saf_volume_absorb")
+        self.__dict__["_shard16"] = None
+        for name in ("voxel_obj_idx", "objects_segmentation_color"):
+            if getattr(self, name, None) is not None:
+                delattr(self, name)
+        lo = tuple(max(o_off[a], s_off[a]) for a in range(3))
+        hi = tuple(min(o_off[a] + o_n[a], s_off[a] + s_n[a]) for a in range(3))
+        some = all(hi[a] > lo[a] for a in range(3))
+        zero = (0, 0, 0)
+        return GridAbsorb(index_offset=s_off, nvox=s_n, other_index_offset=o_off, other_nvox=o_n,
+                          overlap_nvox=tuple(hi[a] - lo[a] for a in range(3)) if some else zero,
+                          overlap_in_self=tuple(lo[a] - s_off[a] for a in range(3)) if some else zero,
+                          overlap_in_other=tuple(lo[a] - o_off[a] for a in range(3)) if some else zero,
+                          move=move, rows_blended=counts[0], rows_copied=counts[1], tsdf_blended=counts[2], tsdf_copied=counts[3],
+                          rows_outside=before[0] - counts[0] - counts[1], tsdf_outside=before[1] - counts[2] - counts[3])
+
     def integrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None):
         """``integrate`` with the backbone outputs supplied by the caller (fuse-only entry used by
         the benchmark and the parity tests)."""
@@ -929,6 +1020,30 @@ class GridMove:
     rows_dropped: torch.Tensor
     tsdf_carried: torch.Tensor
     tsdf_dropped: torch.Tensor
+
+
+@dataclass
+class GridAbsorb:
+    """What ``absorb`` returns.  Boxes are (index offset on the shared lattice, voxels per axis): this module's after the call and
+    the other's; the overlap is given by its size and by its low corner in each box's own indices (all zeros when the boxes share no
+    voxel); ``move`` is the ``GridMove`` of the growth, or None.  The counters are 0-d int64 DEVICE tensors -- reading one
+    synchronises: feature rows (``weight > 0`` in the other volume) and TSDF voxels (``tsdf_weight > 0``) that were blended with
+    what was here, that were copied into empty voxels, and that lie outside this module's final box and were not taken in."""
+
+    index_offset: tuple
+    nvox: tuple
+    other_index_offset: tuple
+    other_nvox: tuple
+    overlap_nvox: tuple
+    overlap_in_self: tuple
+    overlap_in_other: tuple
+    move: GridMove | None
+    rows_blended: torch.Tensor
+    rows_copied: torch.Tensor
+    tsdf_blended: torch.Tensor
+    tsdf_copied: torch.Tensor
+    rows_outside: torch.Tensor
+    tsdf_outside: torch.Tensor
 
 
 @dataclass

@@ -4,12 +4,10 @@
 // boxes contain holds afterwards, byte for byte, what it held before.  One streaming kernel, shaped like pack_rows_kernel
 // (saf_merge.hip): 28 bytes of small fields per overlap voxel, and the feature / label rows of the touched voxels only -- a row
 // whose voxel has weight 0 is neither read (after a lazy reset it holds the previous scan) nor written.
-#include "saf_host.h"
+#include "saf_pair.h"
 
 namespace saf {
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // (a native vector stays one 16-byte access: saf_merge.hip)
 
 struct CarryArgs {
   const float* s_tsdf;
@@ -34,18 +32,6 @@ struct CarryArgs {
   int32_t ox, oy, oz;               // destination index + o = source index
   int32_t s_ny, s_nz, d_ny, d_nz;
 };
-
-// All 64 lanes on one row, `unit` bytes per lane and access (wave-uniform: the branch costs nothing).
-__device__ __forceinline__ void copy_row(unsigned char* __restrict__ d, const unsigned char* __restrict__ s, int64_t bytes, int unit,
-                                         int lane) {
-  if (unit == 16) {
-    for (int64_t o = (int64_t)lane * 16; o < bytes; o += 64 * 16) *reinterpret_cast<u32x4*>(d + o) = *reinterpret_cast<const u32x4*>(s + o);
-  } else if (unit == 4) {
-    for (int64_t o = (int64_t)lane * 4; o < bytes; o += 64 * 4) *reinterpret_cast<uint32_t*>(d + o) = *reinterpret_cast<const uint32_t*>(s + o);
-  } else {
-    for (int64_t o = (int64_t)lane * 2; o < bytes; o += 64 * 2) *reinterpret_cast<uint16_t*>(d + o) = *reinterpret_cast<const uint16_t*>(s + o);
-  }
-}
 
 // A wave takes 64 consecutive voxels of the FLATTENED overlap box (z fastest, as the volume is laid out): an overlap a few voxels
 // deep keeps its lanes busy.  Each lane copies its own voxel's small fields; the ballot names the touched voxels, whose rows
@@ -98,18 +84,6 @@ __global__ __launch_bounds__(256) void carry_kernel(const CarryArgs a) {
   }
 }
 
-// [p, p + bytes) of the two buffers of one name share a byte
-bool intersect(const void* s, const void* d, int64_t s_bytes, int64_t d_bytes) {
-  const uintptr_t sp = (uintptr_t)s, dp = (uintptr_t)d;
-  return sp < dp + (uintptr_t)d_bytes && dp < sp + (uintptr_t)s_bytes;
-}
-
-// bytes per lane and access that a row pitch and the two bases allow
-int copy_unit(int64_t row_bytes, const void* s, const void* d) {
-  const uintptr_t all = (uintptr_t)row_bytes | (uintptr_t)s | (uintptr_t)d;
-  return all % 16 == 0 ? 16 : all % 4 == 0 ? 4 : 2;
-}
-
 }  // namespace
 }  // namespace saf
 
@@ -117,38 +91,13 @@ using namespace saf;
 
 extern "C" int saf_volume_carry(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
                                 const int32_t* aux_src, int32_t* aux_dst, uint64_t* counts, void* stream) {
-  if (!src || !dst) return fail(SAF_E_INVALID, "volume_carry: NULL volume");
-  for (const saf_volume* v : {src, dst}) {
-    if (v->nx <= 0 || v->ny <= 0 || v->nz <= 0 || v->feat_dim <= 0 || v->n_classes < 0)
-      return fail(SAF_E_INVALID, "volume_carry: bad volume shape (%d x %d x %d voxels, %d channels, %d classes)", (int)v->nx, (int)v->ny,
-                  (int)v->nz, (int)v->feat_dim, (int)v->n_classes);
-    if (n_voxels(v) >= (int64_t)1 << 31) return fail(SAF_E_INVALID, "volume_carry: a grid of 2^31 voxels or more");
-    if (!v->tsdf || !v->tsdf_weight || !v->weight || !v->rgb || !v->clip_feat || (v->n_classes > 0 && !v->labels_one_hot))
-      return fail(SAF_E_INVALID, "volume_carry: NULL volume buffer");
-  }
-  if (src->feat_dtype != SAF_F32 && src->feat_dtype != SAF_BF16 && src->feat_dtype != SAF_F16)
-    return fail(SAF_E_INVALID, "volume_carry: unknown feature dtype %d", (int)src->feat_dtype);
-  if (src->feat_dim != dst->feat_dim || src->feat_dtype != dst->feat_dtype || src->n_classes != dst->n_classes)
-    return fail(SAF_E_INVALID, "volume_carry: the volumes differ in feature width, feature dtype or classes (%d/%d/%d and %d/%d/%d)",
-                (int)src->feat_dim, (int)src->feat_dtype, (int)src->n_classes, (int)dst->feat_dim, (int)dst->feat_dtype, (int)dst->n_classes);
+  if (int rc = check_pair("volume_carry", src, dst, "the pass works out of place only")) return rc;
   if ((aux_src == nullptr) != (aux_dst == nullptr)) return fail(SAF_E_INVALID, "volume_carry: aux_src and aux_dst come as a pair");
-  const int64_t ns = n_voxels(src), nd = n_voxels(dst);
-  const int64_t feat_bytes = (int64_t)src->feat_dim * (src->feat_dtype == SAF_F32 ? 4 : 2), label_bytes = (int64_t)src->n_classes * 4;
-  if (intersect(src->tsdf, dst->tsdf, ns * 4, nd * 4) || intersect(src->tsdf_weight, dst->tsdf_weight, ns * 4, nd * 4) ||
-      intersect(src->weight, dst->weight, ns * 4, nd * 4) || intersect(src->rgb, dst->rgb, ns * 12, nd * 12) ||
-      intersect(src->clip_feat, dst->clip_feat, ns * feat_bytes, nd * feat_bytes) ||
-      (label_bytes && intersect(src->labels_one_hot, dst->labels_one_hot, ns * label_bytes, nd * label_bytes)) ||
-      (aux_src && intersect(aux_src, aux_dst, ns * 4, nd * 4)))
+  if (aux_src && intersect(aux_src, aux_dst, n_voxels(src) * 4, n_voxels(dst) * 4))
     return fail(SAF_E_INVALID, "volume_carry: a destination buffer overlaps its source (the pass works out of place only)");
-  // the overlap, in destination indices: 0 <= x < dst.n and 0 <= x + off < src.n, per axis (int64: off may be anything)
-  const int64_t off[3] = {off_x, off_y, off_z}, sn[3] = {src->nx, src->ny, src->nz}, dn[3] = {dst->nx, dst->ny, dst->nz};
+  const int64_t feat_bytes = feat_row_bytes(src), label_bytes = (int64_t)src->n_classes * 4;
   int32_t lo[3], ext[3];
-  for (int k = 0; k < 3; ++k) {
-    const int64_t l = off[k] < 0 ? -off[k] : 0, h = dn[k] < sn[k] - off[k] ? dn[k] : sn[k] - off[k];
-    if (h <= l) return SAF_OK;  // the boxes share no voxel: nothing to carry
-    lo[k] = (int32_t)l;
-    ext[k] = (int32_t)(h - l);
-  }
+  if (!pair_overlap(src, dst, off_x, off_y, off_z, lo, ext)) return SAF_OK;  // the boxes share no voxel: nothing to carry
   CarryArgs a;
   a.s_tsdf = src->tsdf, a.s_tsdf_weight = src->tsdf_weight, a.s_weight = src->weight, a.s_rgb = src->rgb;
   a.s_feat = static_cast<const unsigned char*>(src->clip_feat);

@@ -8,7 +8,8 @@ stage is one of the package's existing entry points (nothing is computed here th
 what this module adds is the chain and a wall-clock split per stage, the counterpart of the reference's one published
 performance statement ("within a few minutes after a user scans the environment", README.md:4).  ``extend_scene`` fuses a later
 scan version's new frames into the volume a reconstruction left (not in the reference, which fuses every version from its
-first frame).
+first frame); ``join_scenes`` puts two reconstructions of one lattice together (``reconstruct_scene(lattice_of=...)``,
+``fusion.absorb``).
 
 The Flask app, the datasets' decoders and the DGCNN in-situ learner stay the reference's.
 """
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from .clip_seem_fusion import ClipSeemFusion, TextQueryEngine, discover_objects, extract_mesh_by_object
+from ._lib import SafError
 from .clipfusion import backproject_pcd, lattice_box, scene_bounds
 from .io import ArrayList, dumps_scene_knowledge, save_npy, save_ply, save_scene_arrays
 
@@ -294,9 +296,23 @@ def _carry_version(fusion, prev, scene_knowledge, voxel_obj_idx):
     return scene_knowledge, voxel_obj_idx, matches
 
 
+def _scene_box(xyz, voxel_size, trunc_m, lattice_of=None):
+    """(origin, nvox, index_offset) of a new scene's volume: ``scene_bounds`` of its cloud, or -- ``lattice_of``, a ``SceneResult``
+    -- the box of that result's lattice around the cloud alone (``lattice_box(..., union=False)``).  Host only."""
+    if lattice_of is None:
+        origin, nvox = scene_bounds(xyz, voxel_size, trunc_m)
+        return origin, nvox, (0, 0, 0)
+    base = lattice_of.fusion
+    if float(base.voxel_size) != float(voxel_size) or float(base.trunc) != float(trunc_m):
+        raise SafError(f"lattice_of: the scene was fused at voxel size {float(base.voxel_size)} and truncation {float(base.trunc)}, "
+                       f"the config asks for {float(voxel_size)} and {float(trunc_m)}")
+    index_offset, nvox = lattice_box(base, xyz, trunc_m=trunc_m, union=False)
+    return base.origin, torch.tensor(nvox, dtype=torch.int32), index_offset
+
+
 def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class_colors=None, device="cuda", out_dir=None,
                       max_depth=4, scale_patches_by_depth=False, feat_dtype=torch.float32, num_workers=0,
-                      object_meshes=True, marching_cubes=None, python_lists=False):
+                      object_meshes=True, marching_cubes=None, python_lists=False, lattice_of=None):
     """``InSituManager.run_clipfusion`` (clip_seem_fusion.py:247-437).
 
     ``dataset`` yields the reference loaders' 5-tuple ``(rgb[H,W,3], depth[H,W], pose[4,4], K[3,3], idx)`` and has
@@ -309,19 +325,24 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
     Python lists the reference builds (handy_utils.py:430-452, clip_seem_fusion.py:393-417); by default they are
     ``io.ArrayList``s around the arrays (same reads, same JSON: 0.8 s of a 2 s scan were spent building those lists and
     encoding them).  With ``out_dir`` the volume's ``.npy`` files (3.4 GB at the reference's largest grid) are written by a
-    second thread from the moment the fusion is complete, beside the object / mesh stages."""
+    second thread from the moment the fusion is complete, beside the object / mesh stages.
+
+    ``lattice_of`` (not in the reference; default None: the bounds above): a ``SceneResult`` on whose LATTICE the new volume is
+    built -- its ``origin``, and the box ``lattice_box(lattice_of.fusion, xyz, union=False)`` of this scan's own cloud -- so that
+    ``join_scenes`` can put the two together.  ``config`` must give the same voxel size and truncation distance."""
     clk = _Clock()
     clk.start()
     # ---- scene bounds (clip_seem_fusion.py:266-287)
     xyz, _ = backproject_pcd(dataset, batch_size=1, num_workers=num_workers, device="cpu", max_depth=max_depth)
     trunc_m = config["trunc_vox"] * config["voxel_size"]
-    origin, nvox = scene_bounds(xyz, config["voxel_size"], trunc_m)
+    origin, nvox, index_offset = _scene_box(xyz, config["voxel_size"], trunc_m, lattice_of)
     clk.lap("bounds")
     # ---- the volume and the fusion loop, one frame per call (clip_seem_fusion.py:291-313)
     # (the reference builds the module on the host and moves it, clip_seem_fusion.py:291-302: gigabytes of zeros through pageable
     #  memory -- 0.7 s at the reference's largest grid; `device=` lets the buffers be born on the device)
     fusion = ClipSeemFusion(origin, config["voxel_size"], nvox, trunc_m, scale_patches_by_depth, config["clip_patch_size"],
-                            config["clip_patch_stride"], clip_model, seg_model, feat_dtype=feat_dtype, device=device).to(device)
+                            config["clip_patch_stride"], clip_model, seg_model, feat_dtype=feat_dtype, index_offset=index_offset,
+                            device=device).to(device)
     host = _fuse_one_by_one(fusion, dataset, config, device, num_workers)
     fusion.flush()
     clk.lap("fuse")
@@ -378,6 +399,33 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     clk.seconds["fuse_host_split"] = {k: round(v, 4) for k, v in host.items()}
     version = int(result.scene_knowledge.get("scan_version", 0)) + 1
     res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, xyz_new)), clk, class_names, class_colors, version,
+                        out_dir, object_meshes, marching_cubes, python_lists, prev=prev)
+    res.seconds = clk.seconds
+    return res
+
+
+def join_scenes(result, other, class_names, class_colors=None, out_dir=None, object_meshes=True, marching_cubes=None,
+                python_lists=False, multiple=4, keep_identities=False, identity_knobs=None):
+    """Two reconstructions of ONE lattice put together (``other`` built with ``reconstruct_scene(..., lattice_of=result)``: two
+    sessions in one room, a second headset, the far end of a corridor): ``result.fusion.absorb(other.fusion)`` -- the volume grows
+    to the box around both and blends ``other``'s running means in by weights (saf_volume_absorb), no frame goes through
+    the backbones again -- and the stages behind the fusion run again on the joined volume.  ``other`` and its module are unchanged.
+
+    Returns a new ``SceneResult`` around ``result.fusion`` -- ``result`` itself describes a volume the module no longer holds --;
+    ``xyz`` is the two clouds concatenated, ``scene_knowledge["scan_version"]`` counts on from ``result``'s, ``seconds`` gains
+    ``absorb``.  ``multiple`` is ``absorb``'s; ``keep_identities`` / ``identity_knobs`` are ``extend_scene``'s: ``result``'s objects
+    are described before the absorb and the joined volume's objects are matched against them."""
+    clk = _Clock()
+    clk.start()
+    fusion = result.fusion
+    prev = None
+    if keep_identities:  # the previous version's objects, described while the module still holds their box
+        prev = _describe_version(fusion, result, identity_knobs)
+        clk.lap("identities")
+    fusion.absorb(other.fusion, grow=True, multiple=multiple)
+    clk.lap("absorb")
+    version = int(result.scene_knowledge.get("scan_version", 0)) + 1
+    res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, other.xyz)), clk, class_names, class_colors, version,
                         out_dir, object_meshes, marching_cubes, python_lists, prev=prev)
     res.seconds = clk.seconds
     return res
