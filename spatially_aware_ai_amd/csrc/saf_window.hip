@@ -131,10 +131,16 @@ __device__ unsigned long long g_win_t[16];
 #define SAF_WIN_P2 2  // tap groups in flight: 2 -> 133 VGPRs, so that two row-kernel waves leave room for classification waves on a SIMD (alone, 2 / 3 / 4 / 6 time the same)
 #endif
 #ifndef SAF_CLS_WPE
-#define SAF_CLS_WPE 5  // classify_bricks_kernel: waves per SIMD the register budget is set for (78 VGPRs, no spills)
+#define SAF_CLS_WPE 5  // classify_bricks_kernel: waves per SIMD the register budget is set for, at the least (69-71 VGPRs: seven alone, two beside
+                       // two row waves; forced to eight = 64 VGPRs the kernel spills 18 registers to scratch: the job 82.3 ms against 73.1)
 #endif
 #ifndef SAF_CLS_FU
-#define SAF_CLS_FU 1   // frames classified together: with the frame cull, occupancy hides the depth gathers better than batching does (1: 1.13 ms, 2: 1.17, 4: 1.29, 8: 2.08 per launch)
+#define SAF_CLS_FU 2   // frames in flight: both frames' projections and depth gathers are issued before the first one's TSDF update waits.  With
+                       // the cameras in scalar registers (58-60 VGPRs for one frame) a second frame costs 11 VGPRs; the job 74.7 / 73.1 / 73.7 /
+                       // 74.7 ms for 1 / 2 / 3 / 4 frames (77-80 and 88-90 VGPRs for 3 and 4), bf16 rows with labels 69.2 / 62.6 / 63.6 ms for 1 / 2 / 3:
+                       // one frame's launch is the shortest beside a row kernel (2.0 ms against 2.5) and slows that kernel the most
+                       // (profiles/r14/classification_knobs_ab.txt).  (Before that, with a frame's camera in 27 VGPRs and its gathers
+                       // serialised, one frame was the faster: 1.13 / 1.17 / 1.29 / 2.08 ms per launch for 1 / 2 / 4 / 8.)
 #endif
 #ifndef SAF_CLS_GUARD_EPS
 #define SAF_CLS_GUARD_EPS 0x1p-20f  // the guard band per pixel of image width / height (the chain's error bound is 11.1 * 2^-24 = 0.69 of it)
@@ -222,8 +228,31 @@ __device__ __forceinline__ int nearest_offset(float gx, float gy, const Cam& c, 
   const bool inb = (xn > -1.0f) && (xn < c.fw) && (yn > -1.0f) && (yn < c.fh);
   return inb ? depth_offset<TILED>((int)xn, (int)yn, width, tiles_x8) : -1;
 }
+// A value that is the same in every lane of the wave, in a form the compiler can see it (a scalar register).
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ float wave_uniform(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+// The classification loop's camera of one frame: its pose and K by scalar loads (the constant address space: neither is written
+// while a classification launch runs), on top of `img`, the image-size terms of the launch.  Every field is a scalar operand of
+// the projection -- no per-lane copy, no LDS read.
+typedef const __attribute__((address_space(4))) float* cls_const_f32;
+__device__ __forceinline__ Cam load_cam_scalar(const Cam& img, const float* pose, const float* K) {
+  const cls_const_f32 p = (cls_const_f32)pose, k = (cls_const_f32)K;
+  Cam c;
+  c.fw = img.fw; c.fh = img.fh; c.rfw = img.rfw; c.rfh = img.rfh; c.sfx = img.sfx; c.sfy = img.sfy;
+  c.r00 = p[0]; c.r01 = p[1]; c.r02 = p[2];  c.tx = p[3];
+  c.r10 = p[4]; c.r11 = p[5]; c.r12 = p[6];  c.ty = p[7];
+  c.r20 = p[8]; c.r21 = p[9]; c.r22 = p[10]; c.tz = p[11];
+  c.k00 = k[0]; c.k01 = k[1]; c.k02 = k[2];
+  c.k10 = k[3]; c.k11 = k[4]; c.k12 = k[5];
+  c.k20 = k[6]; c.k21 = k[7]; c.k22 = k[8];
+  return c;
+}
+// `live` and `img` are wave-uniform (scalar registers): the frame loop is a scalar loop, a frame's depth pointer and camera
+// come by scalar loads, and the frames after the first are fetched behind the gathers of the frames before them.
 template <int KFU, bool SUM, bool VERIFY = false, bool TILED = false>
-__device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa, const Cam* __restrict__ s_cam, uint32_t nb,
+__device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa, const Cam& img, uint32_t nb,
                                                 const float (&xw)[4], const float (&yw)[4], const float (&zw)[4],
                                                 const bool (&inb)[4], float rtrunc, bool tsdf_aligned,
                                                 uint32_t live, uint32_t (&mk4)[4], unsigned long long& nt_done,
@@ -247,19 +276,29 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
   // kFU frames at a time: all their depth gathers are in flight together, then the frames are
   // applied one after the other (the TSDF running mean is order dependent)
   constexpr int kFU = KFU;
-  while (live) {
-    int fr[kFU];  // local frame index (bit of `live`), -1 past the end
+  int nfr[kFU];  // the next kFU frames of `live`: local frame index (bit of `live`), -1 past the end
+  Cam ncam[kFU];
+  const float* ndepth[kFU];
+  auto fetch_frames = [&]() {  // (past the end: frame 0's, read and not used -- no branch around the scalar loads)
 #pragma unroll
     for (int u = 0; u < kFU; ++u) {
-      fr[u] = live ? __ffs((int)live) - 1 : -1;
+      nfr[u] = live ? __ffs((int)live) - 1 : -1;
       live &= live - (live ? 1u : 0u);
+      const int k = nfr[u] >= 0 ? nfr[u] : 0;
+      ncam[u] = load_cam_scalar(img, wa.pose[k], wa.K[k]);
+      ndepth[u] = wa.depth[k];
     }
+  };
+  fetch_frames();
+  while (nfr[0] >= 0) {
+    int fr[kFU];
     int pix[kFU][4];  // >= 0: pixel; -1: in view, no pixel (zeros padding); -2: not in view
     float pz[kFU][4];
 #pragma unroll
     for (int u = 0; u < kFU; ++u) {
+      fr[u] = nfr[u];
       const bool on = fr[u] >= 0;
-      const Cam cam = s_cam[on ? fr[u] : 0];
+      const Cam cam = ncam[u];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         // The voxel's pixel without the normalise / un-normalise round trip (clipfusion.py:654-661 and grid_sample's own
@@ -303,16 +342,18 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
     float depth[kFU][4];
 #pragma unroll
     for (int u = 0; u < kFU; ++u) {
-      // through a buffer descriptor of the frame's depth image (the frame is wave-uniform): a 32-bit offset per lane instead of
-      // a 64-bit address, and "no pixel" (pix < 0: an offset beyond the image) reads 0 by the range check -- zeros padding
-      const __amdgpu_buffer_rsrc_t dimg = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(wa.depth[fr[u] >= 0 ? fr[u] : 0]), 0, wa.depth_bytes, 0x00020000);
+      // through a buffer descriptor of the frame's depth image (built from scalars: the pointer fetched a frame ago and a kernel
+      // argument): a 32-bit offset per lane instead of a 64-bit address, and "no pixel" (pix < 0: an offset beyond the image)
+      // reads 0 by the range check -- zeros padding
+      const __amdgpu_buffer_rsrc_t dimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ndepth[u]), 0, wa.depth_bytes, 0x00020000);
       // (not issuing the gathers of voxel slots without a single pixel in the wave was measured slower: the ballot and branch per
       //  slot cost the vector-bound kernel more than the skipped requests save, profiles/r06/classification_skipdead_ab.txt)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         depth[u][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dimg, pix[u][j] * 4, 0, 0));
     }
+    // the next frames' depth pointers and cameras: scalar loads behind this frame's gathers, in flight during its TSDF update
+    fetch_frames();
 #pragma unroll
     for (int u = 0; u < kFU; ++u) {
 #pragma unroll
@@ -488,7 +529,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
   __shared__ Cam s_cam[kClsFrames];
   __shared__ unsigned long long s_acc[4][2];
   __shared__ uint32_t s_cull[4][kCullWords];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the wave's index is the same in all its lanes; the compiler cannot tell that of threadIdx.x >> 6, and everything derived
+  //  from it -- the brick, `on`, the cull's box -- would be per-lane values to it)
+  const int tid = threadIdx.x, lane = tid & 63, wave = (int)wave_uniform((uint32_t)tid >> 6);
   const int n_f = wa.n;
   if (tid < n_f) s_cam[tid] = load_cam(wa.pose[tid], wa.K[tid], wa.W, wa.H);
   file_frames(wa, tab, tid);
@@ -607,7 +650,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
         }
       }
     }
-    live = on ? (uint32_t)__ballot(lane < n_f && !dead) : 0u;
+    // `live` is the same in every lane: `on` depends on the wave's index and blockIdx alone, the ballot is a scalar, and all 64
+    // lanes are active here (no early return above; the branches of the cull have joined again).  The readfirstlane tells the
+    // compiler so: the frame loop of classify_voxels becomes a scalar loop, and the depth descriptor built per frame stays in
+    // scalar registers (as a per-lane value, each of a frame's four gathers was wrapped in a loop over the descriptor's values).
+    live = wave_uniform(on ? (uint32_t)__ballot(lane < n_f && !dead) : 0u);
     cull[0] = on ? (uint32_t)n_f : 0u;
 #pragma unroll
     for (int k = 1; k < kCullWords; ++k) cull[k] = on ? (uint32_t)__popcll(__ballot(why == k)) : 0u;
@@ -616,8 +663,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
   const bool tsdf_aligned = (((uintptr_t)v.tsdf | (uintptr_t)v.tsdf_w) & 15) == 0;
   unsigned long long nt_done = 0, tsdf_rows_done = 0;
   uint32_t mk4[4] = {0u, 0u, 0u, 0u};
-  if (live)
-    classify_voxels<SAF_CLS_FU, SUM, VERIFY, TILED>(v, wa, s_cam, nb, xw, yw, zw, inb, rtrunc, tsdf_aligned, live, mk4, nt_done, tsdf_rows_done);
+  if (live) {
+    // the image-size terms of a camera (load_cam's, from W and H): once per wave instead of per frame, in scalar registers
+    Cam img;
+    img.fw = wave_uniform((float)wa.W);
+    img.fh = wave_uniform((float)wa.H);
+    img.rfw = wave_uniform(1.0f / img.fw);
+    img.rfh = wave_uniform(1.0f / img.fh);
+    img.sfx = wave_uniform(img.fw / 2.0f);
+    img.sfy = wave_uniform(img.fh / 2.0f);
+    classify_voxels<SAF_CLS_FU, SUM, VERIFY, TILED>(v, wa, img, nb, xw, yw, zw, inb, rtrunc, tsdf_aligned, live, mk4, nt_done, tsdf_rows_done);
+  }
   // every voxel of the grid gets its mask word (the row kernel reads them all); 16 bytes at once where the four lie in the grid
   // and the run is aligned (always, when nz is a multiple of 4)
   if (inb[3] && (nb & 3u) == 0u) {
