@@ -207,6 +207,37 @@ int saf_unfuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_
 int saf_unfuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspace,
                      size_t workspace_bytes, uint64_t* stats, void* stream);
 
+/* The windowed removal (added under ABI 7): the same frames leave the same voxels, a window at a time -- per window of
+ * SAF_WINDOW_FRAMES frames (64 under SAF_WIN_FRAMES=64) one backward classification launch per 32 frames (the TSDF leaves in
+ * registers, frame after frame) and one backward row kernel that reads and writes every touched feature row ONCE, where
+ * saf_unfuse_frames reads and writes it once per frame.  A bulk call: no streaming-session form.
+ *   saf_unfuse_path             1 if saf_unfuse_frames_windowed takes the call: an SAF_F32, SAF_RUNNING_MEAN volume with feat_dim
+ *                               256 / 512 / 768 / 1024, 16 or more frames of one shape, a workspace the windowed forward path
+ *                               accepts, SAF_WINDOW not 0 and SAF_WIN_FORM unset or "sums" (only the order-free form is built
+ *                               backwards); 0 if only saf_unfuse_frames takes it; -1 for bad arguments.  Host-only, launches nothing.
+ *   saf_unfuse_frames_windowed  signature, refusals and counters of saf_unfuse_frames; SAF_E_UNSUPPORTED before anything is
+ *                               launched wherever saf_unfuse_path is not 1.
+ * Arithmetic, per touched voxel:
+ *   TSDF     frame by frame in frame order, tw the voxel's tsdf_weight and t the frame's clamped sdf: tw == 0 -> skipped,
+ *            nothing written, stats[14]; tw - 1 == 0 -> 0.0f exactly; else r = rcp((float)(tw - 1)) (hardware reciprocal),
+ *            b = (float)tw * r, tsdf = tsdf * b - t * r (two products rounded separately, no FMA) -- saf_unfuse_frames' order.
+ *   weight   w0 before, k hits in the window: k_eff = min(k, w0).  The FIRST k_eff hits in frame order are removed, the other
+ *            k - k_eff found the voxel empty and are counted in stats[13]; weight' = w0 - k_eff.  (What frame-after-frame
+ *            removal does: a weight only falls during a removal.)
+ *   rgb      the first k_eff hits one by one in frame order with saf_unfuse_frames' x * b - s * r; exact zeros at weight' == 0.
+ *   labels   minus one per removed hit in its class, never below 0; a class outside [0, n_classes) is skipped.
+ *   feature row   w0 == 0: nothing of the voxel is read or written.  k >= w0 > 0: an exact zero row is stored.  k < w0: the
+ *            accumulator starts as the old row; every hit adds its four taps by four chained FMAs, in frame order, with tap weights
+ *            scaled (one rounding each) by -(1 / (float)w0); the row leaves as acc * ((float)w0 * (1 / (float)(w0 - k))).
+ * tsdf, tsdf_weight, weight, rgb, the label histograms and stats[13] / stats[14] are BIT FOR BIT those of saf_unfuse_frames on
+ * the same frames in the same order, guard cases included; emptied rows are exact zeros either way.  The other feature rows are
+ * within fp32 rounding of it, not equal: |row - (w0 old - S) / (w0 - k)| <= 16 * 2^-24 * k * w0 / (w0 - k) * M per element (S the
+ * sum of the k samples, M the largest magnitude among the old row and the samples), reproducible bit for bit from run to run.
+ * stats[0..3], [5], [6] and [8..12] are not touched. */
+int saf_unfuse_path(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes);
+int saf_unfuse_frames_windowed(const saf_volume* vol, const saf_frame* frames, int32_t n_frames,
+                               void* workspace, size_t workspace_bytes, uint64_t* stats, void* stream);
+
 /* Copy one frame's inputs (depth, rgb, pose, K, feature map, label map -- all f32) from `src` into the buffers `dst`
  * points to, in ONE launch: the host queue behind integrate() keeps the frames of small calls in a staging ring until a
  * window is full.  The source feature map is addressed through element strides (Clip.img_inference_tiled returns a

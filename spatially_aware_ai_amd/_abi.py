@@ -111,6 +111,11 @@ PROTOTYPES = {
         C.c_int,
         [C.POINTER(SafVolume), C.POINTER(SafFrame), C.c_int32, _fp, C.c_size_t, _fp, _fp],
     ),
+    "saf_unfuse_path": (C.c_int, [C.POINTER(SafVolume), C.POINTER(SafFrame), C.c_int32, C.c_size_t]),
+    "saf_unfuse_frames_windowed": (
+        C.c_int,
+        [C.POINTER(SafVolume), C.POINTER(SafFrame), C.c_int32, _fp, C.c_size_t, _fp, _fp],
+    ),
     "saf_poll_async_error": (C.c_int, []),
     "saf_stage_frame": (C.c_int, [C.POINTER(SafFrame), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SafFrame), _fp]),
     "saf_fuse_frames_slabs": (

@@ -714,8 +714,15 @@ class _FusionVolumeMixin:
         self._fuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, self._rgb_bilinear)
 
     # -- taking fused frames out again (not in the reference: its running means only ever grow) --------------------------------
-    def _unfuse(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict):
-        """``saf_unfuse_frames`` (include/saf.h) behind everything handed to ``integrate()`` so far.  Returns the two skip
+    # What ``windowed=None`` means: the windowed removal for calls of this many frames or more (where ``saf_unfuse_path`` is 1),
+    # the per-frame removal below it (None: never).  Measured on an MI355X (tools/measure_unfuse.py, profiles/r15/unfuse_rate.txt:
+    # 256^3 x 512 f32, 640 x 480 frames): at 16 frames -- the smallest count the windowed entry takes, and the smallest measured --
+    # 3.99 ms against 5.01 .. 5.45 ms for the per-frame removal, a margin of 1.0 ms over a spread of 0.44 ms; 2.5 x at 128 frames.
+    _UNFUSE_WINDOWED_MIN_FRAMES = 16
+
+    def _unfuse(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict, windowed=None):
+        """``saf_unfuse_frames`` (include/saf.h) behind everything handed to ``integrate()`` so far -- ``windowed=True``:
+        ``saf_unfuse_frames_windowed``, refused with ``SafError`` where ``saf_unfuse_path`` is not 1.  Returns the two skip
         counters as they stood before the call (``strict``; a device sync) or None."""
         if getattr(self, "_shard_stripes", None) is not None:
             raise SafError(
@@ -738,8 +745,17 @@ class _FusionVolumeMixin:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             before = stats[13:15].tolist() if strict else None
-            check(lib().saf_unfuse_frames(C.byref(vol), arr, len(arr), ws.data_ptr(), ws.numel(), stats.data_ptr(), stream.cuda_stream),
-                  "saf_unfuse_frames")
+            L = lib()
+            takes = L.saf_unfuse_path(C.byref(vol), arr, len(arr), ws.numel()) == 1
+            if windowed is None:
+                floor = self._UNFUSE_WINDOWED_MIN_FRAMES
+                windowed = takes and floor is not None and len(arr) >= floor
+            if windowed and not takes:
+                raise SafError("windowed=True: the windowed removal does not take this call (saf_unfuse_path, include/saf.h: f32 "
+                               "running means of feat_dim 256 / 512 / 768 / 1024, 16 or more frames of one shape, SAF_WIN_FORM "
+                               "unset or sums); windowed=False removes the frames through the per-frame pipeline")
+            entry, name = (L.saf_unfuse_frames_windowed, "saf_unfuse_frames_windowed") if windowed else (L.saf_unfuse_frames, "saf_unfuse_frames")
+            check(entry(C.byref(vol), arr, len(arr), ws.data_ptr(), ws.numel(), stats.data_ptr(), stream.cuda_stream), name)
             # the launches are asynchronous: keep inputs alive until the stream has consumed them
             for t in keep[:5]:
                 t.record_stream(stream)
@@ -754,33 +770,42 @@ class _FusionVolumeMixin:
                 raise SafError(f"de-integration skipped {after[0] - before[0]} valid and {after[1] - before[1]} tsdf-valid voxel updates "
                                "whose count was already 0: these frames were not fused under these poses")
 
-    def deintegrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None, strict=False):
+    def deintegrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None, strict=False, windowed=None):
         """The mirror of ``integrate_features``: take these frames OUT of the volume again, given the inputs they were fused with
         (depth, pose and ``K`` decide which voxels a frame touches; rgb, feature and label maps what leaves them).  Frames still
         queued behind ``integrate()`` are fused first.  A voxel whose last frame leaves is zero again, bit for bit; every other
         running mean is within fp32 rounding of the mean without the frame.  A touched voxel whose count is already
         0 -- the frame was never fused, or under another pose -- is skipped and counted (``stats()["deintegrate_skipped"]``);
         ``strict=True`` synchronises and raises ``SafError`` if that happened during this call.  float32 running-mean volumes
-        only; a voxel-sharded (striped) volume is refused."""
-        self._unfuse_strict(self._unfuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict))
+        only; a voxel-sharded (striped) volume is refused.
 
-    def reintegrate_features(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, clip_feat_img, label_maps=None, strict=False):
+        ``windowed``: ``False`` = the per-frame pipeline run backwards (every width and grid); ``True`` = the windowed removal
+        (``saf_unfuse_frames_windowed``: every touched feature row read and written once per window of 128 frames -- counts, tsdf,
+        rgb and histograms bit for bit the per-frame removal's, feature rows within fp32 rounding of it), ``SafError`` where it
+        does not apply (f32 volumes of feat_dim 256 / 512 / 768 / 1024, calls of 16 or more frames of one shape); ``None`` = the
+        windowed removal wherever it applies (from 16 frames it is the faster one: 1.3 x there, 2.5 x at 128 frames),
+        the per-frame pipeline elsewhere."""
+        self._unfuse_strict(self._unfuse(depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps, strict, windowed))
+
+    def reintegrate_features(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, clip_feat_img, label_maps=None, strict=False,
+                             windowed=None):
         """Move fused frames to corrected poses: ``deintegrate_features`` under ``old_poses``, ``integrate_features`` under
-        ``new_poses``, with the same maps.  ``strict`` as there (the frames are put back either way)."""
-        before = self._unfuse(depth_imgs, rgb_imgs, old_poses, K, clip_feat_img, label_maps, strict)
+        ``new_poses``, with the same maps.  ``strict`` and ``windowed`` (the removal's path) as there; the frames are put back
+        either way, by the path ``integrate_features`` takes."""
+        before = self._unfuse(depth_imgs, rgb_imgs, old_poses, K, clip_feat_img, label_maps, strict, windowed)
         self._fuse(depth_imgs, rgb_imgs, new_poses, K, clip_feat_img, label_maps, self._rgb_bilinear)
         self._unfuse_strict(before)
 
-    def deintegrate(self, depth_imgs, rgb_imgs, poses, K, strict=False):
+    def deintegrate(self, depth_imgs, rgb_imgs, poses, K, strict=False, windowed=None):
         """The mirror of ``integrate``: the same backbone calls yield the feature (and label) maps, then ``deintegrate_features``."""
         feat, label_maps = self._frame_maps(depth_imgs, rgb_imgs, K)
-        self.deintegrate_features(depth_imgs, rgb_imgs, poses, K, feat, label_maps, strict=strict)
+        self.deintegrate_features(depth_imgs, rgb_imgs, poses, K, feat, label_maps, strict=strict, windowed=windowed)
 
-    def reintegrate(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, strict=False):
+    def reintegrate(self, depth_imgs, rgb_imgs, old_poses, new_poses, K, strict=False, windowed=None):
         """What a user of ``refine_pose`` calls when a pose is corrected after its frame was fused: the frames leave the volume
         under ``old_poses`` and enter it again under ``new_poses``.  The backbones run ONCE."""
         feat, label_maps = self._frame_maps(depth_imgs, rgb_imgs, K)
-        self.reintegrate_features(depth_imgs, rgb_imgs, old_poses, new_poses, K, feat, label_maps, strict=strict)
+        self.reintegrate_features(depth_imgs, rgb_imgs, old_poses, new_poses, K, feat, label_maps, strict=strict, windowed=windowed)
 
     def stats(self):
         """dict of counters accumulated by the kernels (forces a device sync)."""

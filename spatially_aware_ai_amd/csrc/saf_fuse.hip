@@ -1214,6 +1214,36 @@ int saf_unfuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_
                    nullptr, false, true);
 }
 
+int saf_unfuse_path(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes) {
+  KVol kv;
+  if (make_kvol(vol, &kv) || n_frames <= 0 || !frames) return -1;
+  return unfuse_windowed(kv, frames, n_frames, workspace_bytes, read_knobs()) ? 1 : 0;
+}
+
+int saf_unfuse_frames_windowed(const saf_volume* vol, const saf_frame* frames, int32_t n_frames, void* workspace,
+                               size_t workspace_bytes, uint64_t* stats, void* stream) {
+  KVol kv;
+  int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
+  if (rc) return rc;
+  if (vol->feat_dtype != SAF_F32)
+    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames_windowed takes SAF_F32 volumes only (as saf_unfuse_frames)");
+  if (vol->accum_mode != SAF_RUNNING_MEAN)
+    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames_windowed takes SAF_RUNNING_MEAN volumes only (as saf_unfuse_frames)");
+  const Knobs kn = read_knobs();
+  if (n_frames == 0 || !unfuse_windowed(kv, frames, n_frames, workspace_bytes, kn))
+    return fail(SAF_E_UNSUPPORTED, "the windowed removal does not take this call (saf_unfuse_path): saf_unfuse_frames does");
+  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  if ((rc = latch_entry())) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // SAF_WIN_OVERLAP=0: every kernel on the caller's stream, as forward (fuse_many)
+  PipeRes* pr = kn.win_overlap ? pipe_acquire(kn) : nullptr;
+  if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, s, nullptr, kn, nullptr, false, true);
+  const WinOverlap ov = overlap_of(pr);
+  rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, s, &ov, kn, nullptr, false, true);
+  pipe_release(pr);
+  return rc;
+}
+
 int saf_unfuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspace, size_t workspace_bytes,
                      uint64_t* stats, void* stream) {
   if (!frame) return fail(SAF_E_INVALID, "frame is NULL");

@@ -365,7 +365,10 @@ int stream_close(void* workspace, size_t workspace_bytes, uint64_t* stats, hipSt
 // whose weight is still 0 when the call is over are zeroed by it, beside the last window's row kernel where the schedule allows.
 int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
                        uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const Knobs& kn,
-                       const WinSlabs* slabs = nullptr, bool recycled = false);
+                       const WinSlabs* slabs = nullptr, bool recycled = false, bool undo = false);
+// undo (saf_unfuse_frames_windowed): the same schedule with the backward classification and row kernel -- the frames leave the
+// volume window by window; only where unfuse_windowed says so (f32 running means, the order-free form).  (saf_window.hip)
+bool unfuse_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn);
 // saf_misc.hip (clear_rows): zero the feature rows of the voxels n in [0, kv.N) with weight[n] == 0 and -- masks may be NULL -- no
 // bit set in masks[p * mask_plane + n] for p < n_planes (the hit masks of a window whose row kernel may be running: it writes exactly
 // the rows with a bit set, this kernel only the others).

@@ -4,6 +4,8 @@
 // form (a row's samples summed in registers, one blend per row: section 4.6c; the default) or its frame-ordered form
 // (SAF_WIN_FORM=rows: bit-identical to the per-frame pipeline of saf_fuse.hip).  Selected by saf_fuse_frames for calls of 16
 // or more frames of one shape.  The host side schedules a call as a list of (sub-volume, window) units.
+// saf_unfuse_frames_windowed runs the same schedule BACKWARDS (template flag UNDO on the classification and on the order-free row
+// kernel of f32 running means): the frames of a window leave the volume with one read and one write per touched row.
 #include <chrono>
 #include <vector>
 
@@ -251,7 +253,10 @@ __device__ __forceinline__ Cam load_cam_scalar(const Cam& img, const float* pose
 }
 // `live` and `img` are wave-uniform (scalar registers): the frame loop is a scalar loop, a frame's depth pointer and camera
 // come by scalar loads, and the frames after the first are fetched behind the gathers of the frames before them.
-template <int KFU, bool SUM, bool VERIFY = false, bool TILED = false>
+// UNDO (saf_unfuse_frames_windowed): the same walk with the update turned round -- the frame's clamped sdf leaves the running mean
+// in the op order of sweep_kernel<UNDO> phase D (saf_fuse.hip); a tsdf-valid voxel whose count is already 0 is skipped, nothing
+// of it is written, and it is counted in nt_done (which the backward row kernel folds into stats[14]).
+template <int KFU, bool SUM, bool VERIFY = false, bool TILED = false, bool UNDO = false>
 __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa, const Cam& img, uint32_t nb,
                                                 const float (&xw)[4], const float (&yw)[4], const float (&zw)[4],
                                                 const bool (&inb)[4], float rtrunc, bool tsdf_aligned,
@@ -364,6 +369,22 @@ __device__ __forceinline__ void classify_voxels(const KVol& v, const ClsArgs& wa
         if (in_view && fabsf(sdf) <= 1.0f) mk4[j] |= 1u << fr[u];
         if (in_view && sdf > -1.0f) {
           const float t = sdf > 1.0f ? 1.0f : sdf;
+          if constexpr (UNDO) {
+            if (tw[j] == 0) {
+              ++nt_done;  // guard: nothing of this frame is in the voxel
+            } else {
+              const int wn = tw[j] - 1;
+              if (wn == 0) {
+                told[j] = 0.0f;  // back to the constructed state
+              } else {
+                const float rw = __builtin_amdgcn_rcpf((float)wn);
+                told[j] = told[j] * ((float)tw[j] * rw) - t * rw;
+              }
+              tw[j] = wn;
+              touched |= 1u << j;
+            }
+            continue;
+          }
           const int w1 = tw[j] + 1;
           if (SUM) {
             told[j] = told[j] + t;
@@ -521,11 +542,15 @@ __global__ __launch_bounds__(256) void depth_reduce_kernel(const float* __restri
   }
 }
 
-template <bool SUM, bool VERIFY = false, bool TILED = false>
+// UNDO = the backward classification (saf_unfuse_frames_windowed; f32 running means only, never with SUM or VERIFY): cull, projection,
+// depth gather, mask bit and the tsdf-valid test are the forward code; the launch's frames LEAVE the TSDF running mean in frame
+// order (classify_voxels<UNDO>).  Its shard counters carry the guard's skips (-> stats[14]); its cull shards are never folded.
+template <bool SUM, bool VERIFY = false, bool TILED = false, bool UNDO = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE))) void classify_bricks_kernel(
     KVol v, ClsArgs wa, const float* __restrict__ dmax, const float* __restrict__ tmax, int ts_log2, int tiles_x,
     uint32_t* __restrict__ hitmask,
     unsigned long long* __restrict__ stats, unsigned long long* __restrict__ cls_acc, WinTable* __restrict__ tab) {
+  static_assert(!UNDO || (!SUM && !VERIFY), "frames leave f32 running means only");
   __shared__ Cam s_cam[kClsFrames];
   __shared__ unsigned long long s_acc[4][2];
   __shared__ uint32_t s_cull[4][kCullWords];
@@ -672,7 +697,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAF_CLS_WPE
     img.rfh = wave_uniform(1.0f / img.fh);
     img.sfx = wave_uniform(img.fw / 2.0f);
     img.sfy = wave_uniform(img.fh / 2.0f);
-    classify_voxels<SAF_CLS_FU, SUM, VERIFY, TILED>(v, wa, img, nb, xw, yw, zw, inb, rtrunc, tsdf_aligned, live, mk4, nt_done, tsdf_rows_done);
+    classify_voxels<SAF_CLS_FU, SUM, VERIFY, TILED, UNDO>(v, wa, img, nb, xw, yw, zw, inb, rtrunc, tsdf_aligned, live, mk4, nt_done, tsdf_rows_done);
   }
   // every voxel of the grid gets its mask word (the row kernel reads them all); 16 bytes at once where the four lie in the grid
   // and the run is aligned (always, when nz is a multiple of 4)
@@ -933,7 +958,11 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
 
 // BF16: 16-bit rows (8 channels per 16 bytes); F16 (with BF16): their elements are IEEE half instead of bfloat16 -- the same
 // layout, loads, stores and fp32 arithmetic, another widening and another (nearest-even) narrowing (h16_lo / h16_hi / pack_h16).
-template <int CPL, bool SUM, bool BF16, bool OF, bool F16 = false>
+// UNDO (window_unfuse_kernel; the order-free f32 running mean only): the window's hits LEAVE the rows.  Per touched voxel of weight
+// w0 with k hits, k_eff = min(k, w0) of them, the first in frame order, are removed -- rgb hit by hit with unblend, labels minus one
+// per removed hit, weight w0 - k_eff -- and the other k - k_eff are the guard's skips (stats[13]).  Feature row: untouched where
+// w0 == 0, an exact zero row where k >= w0, else old + sum of samples x (-1 / w0), leaving as acc x (w0 x (1 / (w0 - k))).
+template <int CPL, bool SUM, bool BF16, bool OF, bool F16 = false, bool UNDO = false>
 __device__ __forceinline__ void
 fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
                  unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
@@ -941,6 +970,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                  int xcd_order) {
   using Cfg = WinCfg<CPL, OF, BF16>;
   constexpr int SR = Cfg::SR;
+  static_assert(!UNDO || (OF && !SUM && !BF16), "frames leave f32 running means through the order-free form only");
   // (s_setprio 1 / 3 here, ahead of the classification waves that share the SIMDs, changes nothing: 105.4 / 105.7 / 105.8 ms)
   // a bf16 sub-chunk also holds its raw rows in registers until they are widened: one tap group fewer in flight
   constexpr int P = OF ? Cfg::P
@@ -967,11 +997,15 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
       a += __shfl_xor(a, o);
       b += __shfl_xor(b, o);
     }
+    if constexpr (UNDO) {  // the backward classification's skipped tsdf-valid voxels; no other counter moves
+      if (tid == 0 && a) atomicAdd(&stats[14], a);
+    } else {
     if (tid == 0) {
       if (a) atomicAdd(&stats[1], a);
       if (b) atomicAdd(&stats[6], b);
     }
     fold_cull_shards(cls_acc, stats, tid);
+    }
   }
   static_assert(kWinThreads >= kWin, "one thread per frame loads the window's cameras");
   if (tid < wa.F) {
@@ -996,6 +1030,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
   kf.H = wa.H; kf.W = wa.W; kf.npy = wa.npy; kf.npx = wa.npx; kf.rgb_bilinear = wa.rgb_bilinear;
   kf.depth = nullptr; kf.pose = nullptr; kf.K = nullptr;
   unsigned long long hits_done = 0, rows_done = 0;
+  [[maybe_unused]] uint32_t guard_done = 0;  // UNDO, per lane: hits that found their voxel at weight 0
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   WT_DECL;
   // persistent grid (2 workgroups of 4 waves per CU, 71 KB of LDS each).  Pieces are handed out by an
@@ -1127,6 +1162,8 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
         const uint32_t hf = j < htot ? s_hf[j] : 0u;
         const uint32_t n = (uint32_t)__shfl((int)n_l, (int)(hf & 63u));
         int lbl = -1;  // the hit's panoptic class, -1: none
+        bool gone = true;  // UNDO: the hit is one of its voxel's first min(k, w0), the ones that leave
+        if constexpr (UNDO) gone = j - __shfl(prefix, (int)(hf & 63u)) < __shfl(w0, (int)(hf & 63u));
         if (j < htot) {
           const int fb = (int)(hf >> 22);
           int ix, iy, iz;
@@ -1154,7 +1191,11 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             const long long l = (long long)(pix >= 0 ? lraw : 0.f);
             const bool ok = l >= 0 && l < v.n_classes;
             lbl = ok ? (int)l : -1;
+            if constexpr (UNDO) {
+              if (!gone) lbl = -1;  // (a class that was dropped forward is skipped and not counted again)
+            } else {
             if (!ok && stats) atomicAdd(&stats[3], 1ull);
+            }
           }
         }
         if (v.labels && s_lab[0]) {
@@ -1168,13 +1209,47 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
           const unsigned long long stops = __ballot(head || lbl < 0);  // where a run cannot continue
           const unsigned long long above = lane == 63 ? 0ull : (stops >> (lane + 1));
           const int len = above ? __ffsll((long long)above) : 64 - lane;
+          if constexpr (UNDO) {
+            // minus the run's length, never below 0 -- what `len` clamped single decrements leave.  Several runs of one class and
+            // voxel (A, B, A) are different lanes on one address: a compare-and-swap loop, whose results compose in any order.
+            if (head) {
+              int* cnt = v.labels + (int64_t)n * v.n_classes + lbl;
+              int cur = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              while (cur > 0) {
+                const int seen = atomicCAS(cnt, cur, cur > len ? cur - len : 0);
+                if (seen == cur) break;
+                cur = seen;
+              }
+            }
+          } else {
           if (head) atomicAdd(v.labels + (int64_t)n * v.n_classes + lbl, len);
+          }
         }
       }
       wave_lds_sync();
       WT(2);
       // ---- lane-parallel over voxels: the rgb running mean over the voxel's hits in frame order, in
       //      registers (clipfusion.py:715-721); a = 1/(w+1), b = w*a of every hit take the samples' slots
+      if constexpr (UNDO) {
+        // the first k_eff = min(k, w0) hits leave in frame order (fuse_scalars_lane<true>'s a, b and unblend); the others found the
+        // voxel empty: the guard's skips.  A voxel that loses nothing is not written.
+        const int k_eff = active ? min(h, w0) : 0;
+        if (k_eff > 0) {
+          float* dst = v.rgb + (int64_t)n_l * 3;
+          float o0 = dst[0], o1 = dst[1], o2 = dst[2];
+          for (int r = 0; r < k_eff; ++r) {
+            const int j = prefix + r;
+            const int wi = w0 - r;
+            const float a = wi > 1 ? 1.0f / (float)(wi - 1) : 0.0f, b = (float)wi * a;
+            o0 = unblend(s_ha[j], o0, a, b);
+            o1 = unblend(s_hb[j], o1, a, b);
+            o2 = unblend(s_hs2[j], o2, a, b);
+          }
+          dst[0] = o0; dst[1] = o1; dst[2] = o2;
+          v.weight[n_l] = w0 - k_eff;
+        }
+        if (active) guard_done += (uint32_t)(h - k_eff);
+      } else
       if (active) {
         float* dst = v.rgb + (int64_t)n_l * 3;
         float o0 = dst[0], o1 = dst[1], o2 = dst[2];
@@ -1275,6 +1350,13 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             const Bilin w = bilinear_setup(hit ? s_hgx[sj] : 0.0f, hit ? s_hgy[sj] : 0.0f, half_px, half_py);
             rec.nw = w.nw; rec.ne = w.ne; rec.sw = w.sw; rec.se = w.se;
           }
+          if constexpr (UNDO) {
+            // the samples LEAVE: weighted by -1 / w0 where forward has +1 / w0.  (The hits of a row that empties, k >= w0, or that
+            // was empty, w0 == 0, add into an accumulator that is never stored.)
+            const int w0h = __shfl(w0, (int)(hfl & 63u));
+            const float rs = w0h == 0 ? 1.0f : -1.0f / (float)w0h;
+            rec.nw *= rs; rec.ne *= rs; rec.sw *= rs; rec.se *= rs;
+          } else
           if constexpr (OF && !SUM && !BF16) {
             // f32 running mean: the accumulator starts as the OLD row, unscaled (it is loaded straight into the registers and
             // first touched by whichever hit comes first), so every sample of a row is weighted by 1 / w0 instead -- lane-
@@ -1302,6 +1384,9 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
               low[w] = (uint32_t)w < fwd ? 0xffffffffu : ((uint32_t)w == fwd ? (1u << fbit) - 1u : 0u);
 #pragma unroll
             for (int r = 0; r < SR; ++r) {
+              if constexpr (UNDO) {  // not loaded: a row that is empty already (never read, never written) or that empties (zeros)
+                if (r < nrows && __builtin_amdgcn_readlane(h, i0 + r) >= __builtin_amdgcn_readlane(w0, i0 + r)) fresh |= 1u << r;
+              } else
               if (r < nrows && __builtin_amdgcn_readlane(w0, i0 + r) == 0) {
                 fresh |= 1u << r;
                 if (!BF16 && !OF) {
@@ -1459,6 +1544,23 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
         for (int r = 0; r < SR; ++r) {
           if (r < nrows) {
             const int64_t row = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)n_l, i0 + r) * DV;
+            if constexpr (UNDO) {  // (w0 old - the window's samples) / (w0 - k); zeros where the row empties; nothing where it was empty
+              const int k_r = __builtin_amdgcn_readlane(h, i0 + r), w0_r = __builtin_amdgcn_readlane(w0, i0 + r);
+              if (w0_r > 0) {
+                const bool empties = k_r >= w0_r;
+                const float fac = empties ? 0.0f : (float)w0_r * (1.0f / (float)(w0_r - k_r));
+                const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(feat + row, 0, v.D * 4, 0x00020000);
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) {
+                  // (exact +0 for an emptied row, whatever its accumulator holds: the voxel is back in its constructed state)
+                  const win_v2f lo = acc[r][2 * c] * (win_v2f){fac, fac}, hi = acc[r][2 * c + 1] * (win_v2f){fac, fac};
+                  acc[r][2 * c] = empties ? (win_v2f){0.f, 0.f} : lo;
+                  acc[r][2 * c + 1] = empties ? (win_v2f){0.f, 0.f} : hi;
+                  const float4 o = make_float4(acc[r][2 * c].x, acc[r][2 * c].y, acc[r][2 * c + 1].x, acc[r][2 * c + 1].y);
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(win_v4u, o), rr, lane * 16 + c * 1024, 0, SAF_WIN_OF_STPOL);
+                }
+              }
+            } else
             if constexpr (OF) {  // (w0 old + the window's samples) / (w0 + k), one rounding to bf16 per window
               // IN PLACE, and stored from the row's own registers through the row's buffer descriptor: through shared data or
               // address temporaries every row's stores would wait for the previous row's to leave (a store's registers may not
@@ -1523,6 +1625,11 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
     }
   }
   WT_FLUSH;
+  if constexpr (UNDO) {  // the guard's skips on the weight side; stats[0], [5] are statements about fusion and do not move
+    unsigned long long g = guard_done;
+    for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
+    if (stats && lane == 0 && g) atomicAdd(&stats[13], g);
+  } else
   if (stats && lane == 0) {
     if (hits_done) atomicAdd(&stats[0], hits_done);
     if (rows_done) atomicAdd(&stats[5], rows_done);  // rows read-modify-written by this window
@@ -1569,6 +1676,24 @@ fuse_window_kernel_of176_f16(KVol v, WinArgs wa, const WinTable* __restrict__ ta
                              const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
                              int xcd_order) {
   fuse_window_body<2, false, true, true, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+}
+
+// The backward row kernels (saf_unfuse_frames_windowed): fuse_window_body<CPL, SUM = false, BF16 = false, OF = true> under UNDO,
+// kernels of their own under the forward twins' register budgets and with their LDS layout (WinCfg<CPL, true>).
+template <int CPL>
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(SAF_WIN_OF_WPE, SAF_WIN_OF_WPE))) void
+window_unfuse_kernel(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
+                     unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
+                     const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
+                     int xcd_order) {
+  fuse_window_body<CPL, false, false, true, false, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+}
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
+window_unfuse_kernel_of176(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
+                           unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
+                           const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
+                           int xcd_order) {
+  fuse_window_body<2, false, false, true, false, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1623,6 +1748,15 @@ template <int CPL>
 WinFn pick_win(bool sum, int e16, bool of, size_t* lds) {
   *lds = of ? WinCfg<CPL, true>::total : WinCfg<CPL, false>::total;
   return of ? pick_win<CPL, true>(sum, e16) : pick_win<CPL, false>(sum, e16);
+}
+// the backward row kernel of a width (f32 running means, order-free form: unfuse_windowed)
+WinFn pick_unwin(int cpl, size_t* lds) {
+  switch (cpl) {
+    case 1: *lds = WinCfg<1, true>::total; return window_unfuse_kernel<1>;
+    case 2: *lds = WinCfg<2, true>::total; return window_unfuse_kernel_of176;
+    case 3: *lds = WinCfg<3, true>::total; return window_unfuse_kernel<3>;
+    default: *lds = WinCfg<4, true>::total; return window_unfuse_kernel<4>;
+  }
 }
 
 }  // namespace
@@ -1697,6 +1831,15 @@ FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, 
   return r;
 }
 
+// Whether the windowed removal (saf_unfuse_frames_windowed) takes a call: only the order-free form of the f32 running mean is built
+// backwards, and only where the caller did not ask for another form -- i.e. where the same call forward would take kPathSums with
+// SAF_WIN_FORM unset or "sums".  Everything else about the call (frames of one shape, 16 or more, the workspace) is fuse_route's.
+bool unfuse_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn) {
+  if (kv.e16 != 0 || kv.accum == SAF_SUM) return false;
+  if (kn.win_form != 0 && kn.win_form != 's') return false;
+  return fuse_route(kv, frames, n_frames, workspace_bytes, kn).path == kPathSums;
+}
+
 namespace {
 // What a call and a session derive alike from one (volume, frame shape, workspace): the workspace layout, the row kernel, the
 // depth-tile geometry and the knobs that are read per call.  Both drivers launch through it (win_view, launch_*, win_geom).
@@ -1707,12 +1850,14 @@ struct WinPlan {
   int ts_log2, tiles_x, n_tiles;  // depth tiles of the classification's occlusion cull
   int wlen;                       // frames per window
   bool tiled, sum, of, maps16, rgbl_on, brick_form;
+  bool undo;  // the frames leave the volume: the backward classification and row kernel (saf_unfuse_frames_windowed)
   size_t dpx, img_bytes16, win_lds, aux_bytes;
   WinFn fn;  // the row kernel (nullptr: the brick form)
   Knobs kn;  // the call's knobs
 };
-int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Knobs& kn, WinPlan* pl) {
+int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Knobs& kn, WinPlan* pl, bool undo = false) {
   pl->kn = kn;
+  pl->undo = undo;
   pl->H = kf0.H; pl->W = kf0.W; pl->npy = kf0.npy; pl->npx = kf0.npx; pl->rgb_bilinear = kf0.rgb_bilinear;
   const int P = pl->P = kf0.npy * kf0.npx;
   // Two layouts of the workspace: with room for the window's depth images re-laid-out in tiles (a workspace sized by
@@ -1745,6 +1890,12 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Kn
   pl->of = form == kPathSums;
   pl->fn = nullptr;
   pl->win_lds = 0;
+  if (undo && form != kPathSums) return fail(SAF_E_UNSUPPORTED, "windowed removal: the order-free row form only");
+  if (undo) {
+    pl->fn = pick_unwin(kv.D / 256, &pl->win_lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->win_lds);
+    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
+  } else
   if (!pl->brick_form) {
     switch (kv.D / 256) {
       case 1: pl->fn = pick_win<1>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
@@ -1886,6 +2037,7 @@ int launch_classify(const WinPlan& pl, const WinView& v, const TileView& tv, con
                                  : (sum ? classify_bricks_kernel<true, false, true> : classify_bricks_kernel<false, false, true>))
                        : (verify ? (sum ? classify_bricks_kernel<true, true, false> : classify_bricks_kernel<false, true, false>)
                                  : (sum ? classify_bricks_kernel<true, false, false> : classify_bricks_kernel<false, false, false>));
+  if (pl.undo) kfn = use_tiled ? classify_bricks_kernel<false, false, true, true> : classify_bricks_kernel<false, false, false, true>;
   // (the frames' largest depths, dmax, feed the bricks' frame cull)
   hipLaunchKernelGGL(kfn, dim3(win_geom(pl, kv).cls_wgs), dim3(256), 0, cs, kv, ca, tv.dmax_w + g.fb,
                      tv.tmax_w + (size_t)g.fb * kMaxDepthTiles, pl.ts_log2, pl.tiles_x, plane,
@@ -1970,7 +2122,7 @@ struct WinUnit {
 
 int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes,
                        uint64_t* stats, saf_profiler* prof, hipStream_t s, const WinOverlap* ov, const Knobs& kn, const WinSlabs* slabs,
-                       bool recycled) {
+                       bool recycled, bool undo) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   int rc = SAF_OK;
   KFrame kf0;
@@ -1980,7 +2132,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     if ((rc = make_kframe(&frames[i], &t))) return rc;
   }
   WinPlan pl;
-  if ((rc = win_plan(kv, kf0, workspace_bytes, kn, &pl))) return rc;
+  if ((rc = win_plan(kv, kf0, workspace_bytes, kn, &pl, undo))) return rc;
   int tile_window[kTileWindows];  // which window's tile maxima a slot of the tile region holds (-1: none)
   for (int k = 0; k < kTileWindows; ++k) tile_window[k] = -1;
   const int wlen = pl.wlen;
@@ -1993,7 +2145,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     for (int k = 0; k < slabs->n; ++k) {
       if ((rc = check_slab(kv, *slabs, k))) return rc;
       for (int w = 0; w < n_win; ++w)
-        units.push_back(WinUnit{slab_kvol(kv, slabs->x0[k], slabs->nx[k]), w * wlen, win_frames(w), k == 0, w + 1 == n_win ? k : -1, k * n_win + w});
+        units.push_back(WinUnit{slab_kvol(kv, slabs->x0[k], slabs->nx[k]), w * wlen, win_frames(w), k == 0 && !undo, w + 1 == n_win ? k : -1, k * n_win + w});
     }
   } else {
     // SAF_WIN_SLABS (default 1 = off): EVERY window slab by slab, window after window -- units of one size, so
@@ -2009,7 +2161,7 @@ int fuse_many_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames
     for (int w = 0; w < n_win; ++w) {
       const int n = w == 0 ? n0 : ns;
       for (int k = 0; k < n; ++k)
-        units.push_back(WinUnit{n == 1 ? kv : slab_kvol(kv, k * (kv.nx / n), kv.nx / n), w * wlen, win_frames(w), k == 0, -1, w});
+        units.push_back(WinUnit{n == 1 ? kv : slab_kvol(kv, k * (kv.nx / n), kv.nx / n), w * wlen, win_frames(w), k == 0 && !undo, -1, w});
     }
   }
   const int n_units = (int)units.size();
