@@ -594,8 +594,9 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
  * A fused volume carried into another box of the SAME lattice (additive under ABI 7; new capability, nothing to mirror in the
  * reference: its manager re-fuses every frame of a scan into a new grid when the scan grows, get_path(config, curr_ver, ...)).
  * `src` and `dst` are two boxes of one lattice -- same origin, same voxel size, corners that differ by whole voxels -- so the pass
- * is a copy and nothing is recomputed; resampling and coarsening are not offered (blending two volumes of
- * one lattice: saf_volume_absorb below).
+ * is a copy and nothing is recomputed (blending two volumes of one lattice: saf_volume_absorb below;
+ * coarsening by a whole factor on block boundaries of the lattice: saf_volume_coarsen below; resampling onto any other lattice
+ * -- rotated, a fractional factor, finer -- is not offered).
  *   mapping   destination voxel (x, y, z) corresponds to source voxel (x + off_x, y + off_y, z + off_z); the caller passes
  *             off = dst's index offset - src's.  The OVERLAP is the set of destination voxels whose source voxel lies inside
  *             `src`.  A destination voxel outside the overlap is not touched: every buffer keeps its bytes there.
@@ -655,6 +656,56 @@ int saf_volume_carry(const saf_volume* src, const saf_volume* dst, int32_t off_x
  */
 int saf_volume_absorb(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
                       uint64_t* counts, void* stream);
+
+/*
+ * A fused volume coarsened by a whole factor f = 2, 3 or 4 on BLOCK BOUNDARIES OF ITS LATTICE (additive under ABI 7; new
+ * capability, nothing to mirror in the reference, which pushes every frame through the backbones again into a coarser grid;
+ * DESIGN.md section 4.21).  A coarse voxel is the weighted mean of the f^3 fine voxels it covers: saf_volume_absorb's blend with
+ * up to f^3 sources instead of two.  `src` is only read; `dst` is another set of buffers (the pass works out of place only).
+ *   mapping   `src` holds its nx x ny x nz voxels from global index off = (off_x, off_y, off_z) of the lattice (origin, vs).  Global
+ *             coarse voxel I (per axis) covers the fine global indices f I .. f I + f - 1 -- a FLOOR division, so negative offsets
+ *             work and blocks are aligned to the lattice, not to the box.  The coarse lattice has voxel_size' = f vs and origin' =
+ *             origin + 0.5 (f - 1) vs, the centre of the block of global coarse index 0 (the caller computes it in float64 and
+ *             stores it as origin was stored); index_offset' = floor(off / f) and nvox' = ceil((off + n) / f) - floor(off / f) per
+ *             axis: `dst` must have exactly these sizes.  trunc does not change (TSDF values are in units of trunc).  Children of
+ *             an edge block that lie outside the fine box count as empty.  origin' depends on origin, vs and f only: two boxes of
+ *             one fine lattice coarsen to two boxes of one coarse lattice.  The pass does not inspect trunc or the axis tables.
+ *   per voxel  two independent sides, as in absorb: the feature side (driven by `weight`; it owns weight, the three rgb floats, the
+ *             feature row and, with n_classes > 0, the label histogram row) and the TSDF side (driven by `tsdf_weight`; it owns
+ *             tsdf_weight and tsdf).  Children are visited in ascending fine flat index (x slowest, z fastest); K = the number
+ *             of children with w_c > 0, W = their sum (int32; not checked for overflow: these are frame counts).
+ *   K == 0    the small fields of that side are written 0; the feature and label rows are NOT WRITTEN: the caller supplies a
+ *             destination whose weight-0 rows are zero, or owes it the deferred clear (saf_clear_unwritten_rows).
+ *   K == 1    a copy of that child's bytes (values, row, labels): w fl(1 / w) is not 1 for every w, so the copy is its own case,
+ *             as in absorb.
+ *   K >= 2    r = 1.0f / (float)W by IEEE division, c_k = (float)w_k * r, acc = x_1 * c_1 for the first contributing child, then
+ *             acc = acc + x_k * c_k in order: every product and every sum rounded on its own, no FMA.  For each rgb channel and each
+ *             feature channel, and for tsdf with the tsdf_weights.  16-bit rows (SAF_BF16, SAF_F16) are widened exactly,
+ *             accumulated in fp32 and narrowed ONCE, round to nearest even.  The label histogram is the int32 sum over the
+ *             contributing children only.  NaN and inf in contributing rows travel as IEEE arithmetic carries them.
+ *   counts    stored: weight' = max_c w_c and tsdf_weight' = max_c w_c, NOT the sum.  The blend uses every sample; the stored count
+ *             stands for "frames that saw this block", which lies between the max and the sum (one frame usually sees several
+ *             children of a block), and the max keeps a later frame's sample worth one frame in the running mean that goes on.
+ *   not read  the values and rows of a child with w_c == 0 (stale after a deferred clear, possibly NaN), and everything outside `src`.
+ *   bias      a block whose observed children all lie on one side of its centre gets a TSDF that is off by up to half a coarse
+ *             voxel (known, documented, not corrected); the mean of a linear field over all f^3 children is its value at the centre.
+ *   counts[]  device u64[4], ADDED to (may be NULL): [0] rows blended (K >= 2), [1] rows copied (K == 1), [2] tsdf voxels blended,
+ *             [3] tsdf voxels copied.  Integer atomics, one per wave and counter: exact whatever the scheduling.
+ * SAF_E_INVALID (on the host, nothing is launched) for everything saf_volume_carry refuses -- a NULL src / dst or volume buffer,
+ * non-positive sizes or feat_dim, a grid of 2^31 voxels or more, feat_dim, feat_dtype or n_classes that differ, any destination
+ * buffer whose byte range intersects the source buffer of the same name --, for a feature or label buffer that is not aligned to
+ * its element type, for a factor outside 2 .. 4 and for a `dst` whose nx, ny, nz are not the nvox' of `src` under the off passed.
+ * SAF_E_UNSUPPORTED if either accum_mode is SAF_SUM.
+ * One launch, carry's and absorb's shape: a wave takes 64 consecutive voxels of the flattened coarse box (z fastest: the children
+ * along z are adjacent); each lane computes its block's small fields; a ballot names the blocks with a row to write and the wave
+ * takes them one after the other: lane j looks up child j (f^3 <= 64), a ballot over their counts names the contributing
+ * children, and their indices and coefficients are read from those lanes; 16 bytes per lane where the row pitch and both bases
+ * allow it, else 4 or 2; the loads of up to 8 children are issued before their arithmetic.  No LDS, no scratch, no floating-point
+ * atomics.  Per call 8 N_src bytes of counts are read and 12 / 4 more per fine voxel with weight / tsdf_weight > 0, 28 N_dst bytes
+ * are written; per contributing child one row (feature + label bytes) is read, per coarse voxel with K >= 1 one is written.
+ */
+int saf_volume_coarsen(const saf_volume* src, const saf_volume* dst, int32_t factor, int32_t off_x, int32_t off_y, int32_t off_z,
+                       uint64_t* counts, void* stream);
 
 /*
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for

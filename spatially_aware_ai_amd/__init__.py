@@ -18,6 +18,7 @@ __all__ = [
     "lattice_box",
     "GridMove",
     "GridAbsorb",
+    "GridCoarsen",
     "label_components",
     "discover_objects",
     "evaluation",
@@ -37,7 +38,8 @@ __all__ = [
 
 
 def __getattr__(name):
-    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove", "GridAbsorb"):
+    if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove", "GridAbsorb",
+                "GridCoarsen"):
         from . import clipfusion as _m
 
         return getattr(_m, name)

@@ -10,6 +10,7 @@ Same names, arguments and error behaviour as the reference classes so that its c
   * ``scene_bounds``    -- the bounds arithmetic of clipfusion.py:1098-1106
   * ``lattice_box`` / ``move_grid`` -- not in the reference: a volume moved by whole voxels on its own lattice
   * ``absorb`` -- not in the reference: a second volume of the same lattice blended in by weights
+  * ``coarsen`` / ``coarse_lattice`` -- not in the reference: a volume coarsened by a whole factor on its lattice
 
 PyTorch is plumbing here (device memory, streams, the backbone GEMMs); the fusion loop and the
 query scan are the hand-written HIP kernels behind ``include/saf.h``.  There is no CPU
@@ -708,6 +709,92 @@ class _FusionVolumeMixin:
                           move=move, rows_blended=counts[0], rows_copied=counts[1], tsdf_blended=counts[2], tsdf_copied=counts[3],
                           rows_outside=before[0] - counts[0] - counts[1], tsdf_outside=before[1] - counts[2] - counts[3])
 
+    def coarsen(self, factor=2):
+        """Coarsen the volume IN PLACE by a whole ``factor`` (2, 3 or 4) on block boundaries of its lattice and keep fusing at the
+        coarse size: a coarse voxel is the weighted mean of the ``factor``^3 fine voxels it covers -- global coarse index I covers
+        the fine global indices ``factor * I .. factor * I + factor - 1`` (saf_volume_coarsen, include/saf.h).
+        Afterwards ``voxel_size`` is ``factor`` times what it was, ``origin`` is the centre of the block of global coarse index 0
+        (``coarse_lattice``: it depends on the old origin, voxel size and factor only, so two boxes of one lattice coarsen onto
+        one coarse lattice and can be ``absorb``ed), ``index_offset`` and ``nvox`` are the blocks the old box touches; ``trunc``
+        does not change.  The stored counts are the MAXIMA over a block's children, not the sums: a later frame's sample stays
+        worth one frame.  The module keeps its backbones, its queue and ``fuse_stats``; frames still queued behind ``integrate()``
+        are fused first; a deferred clear stays owed.
+
+        Frames fused before the call can no longer be taken out with ``deintegrate``: their samples are spread over other voxels
+        at other weights.  The module keeps no ledger of what it holds, so that is the caller's business, as after ``absorb`` on
+        16-bit volumes.
+
+        BOTH volumes are resident during the call.  ``voxel_obj_idx`` and ``objects_segmentation_color`` describe a labelling of
+        the fine grid and are deleted.  Returns a ``GridCoarsen``; its counters are device tensors, nothing is read back here.
+        ``SafError``, with the volume unchanged, for a module built with ``x_planes``, one that holds only reduce-scattered
+        stripes, a poisoned one, a ``SAF_SUM`` volume, and a factor that is not the int 2, 3 or 4."""
+        if self.x_planes is not None:
+            raise SafError("coarsen() needs a box of consecutive x-planes: this module was built with x_planes")
+        if getattr(self, "_shard_stripes", None) is not None:
+            raise SafError("this volume holds only its reduce-scattered voxel stripes of a merged job; all_gather it "
+                           "(distributed.gather_shards, or merge_volumes(..., gather=True)) before coarsening it")
+        self._check_poisoned()
+        if self.accum_mode != _abi.SAF_RUNNING_MEAN:
+            raise SafError("coarsen: running means only: a SAF_SUM volume belongs to the multi-rank job, whose merge adds its sums")
+        if isinstance(factor, bool) or not isinstance(factor, int) or factor not in (2, 3, 4):
+            raise SafError(f"coarsen: the factor must be the int 2, 3 or 4, got {factor!r}")
+        # the frames still queued belong to the fine grid; the session's state is sized by it and goes, as in move_grid.  A
+        # deferred clear stays owed: the pass never reads the row of a weight-0 voxel
+        self._flush_pending(final=True)
+        q = self.__dict__["_queue"]
+        q.wait(self)
+        q.close()
+        old = dict(self._buffers)
+        require_cuda(old["clip_feat"], "the fusion volume")
+        dev = old["tsdf"].device
+        old_off, old_nvox = self.index_offset, tuple(int(v) for v in self.nvox)
+        old_origin, old_vs = self.origin, self.voxel_size
+        new_origin, new_vs, new_off, new_nvox = coarse_lattice(old_origin, old_vs, old_off, old_nvox, factor)
+        n_new = new_nvox[0] * new_nvox[1] * new_nvox[2]
+        src = self._c_volume(for_fuse=True)
+        labels = old.get("labels_one_hot")
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            new = {"tsdf": torch.zeros(n_new, dtype=torch.float32, device=dev),
+                   "rgb": torch.zeros((n_new, 3), dtype=torch.float32, device=dev),
+                   "weight": torch.zeros(n_new, dtype=torch.int32, device=dev),
+                   "tsdf_weight": torch.zeros(n_new, dtype=torch.int32, device=dev),
+                   # not cleared here, as in move_grid: the rows of coarse voxels without a contributing child stay owed the
+                   # deferred clear
+                   "clip_feat": torch.empty((n_new, int(self.n_clip_feats)), dtype=old["clip_feat"].dtype, device=dev)}
+            if labels is not None:
+                new["labels_one_hot"] = torch.zeros((n_new, int(labels.shape[1])), dtype=torch.int32, device=dev)
+            ax = [t.to(dev) for t in _axis_tables(new_origin, new_vs, new_nvox, new_off)]
+            p = _abi.ptr
+            dst = _abi.SafVolume(new_nvox[0], new_nvox[1], new_nvox[2], src.feat_dim, src.n_classes, src.feat_dtype, src.accum_mode,
+                                 src.trunc, p(ax[0]), p(ax[1]), p(ax[2]), p(new["tsdf"]), p(new["tsdf_weight"]), p(new["weight"]),
+                                 p(new["rgb"]), p(new["clip_feat"]), p(new.get("labels_one_hot")))
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+            check(lib().saf_volume_coarsen(C.byref(src), C.byref(dst), factor, old_off[0], old_off[1], old_off[2], p(counts),
+                                           stream.cuda_stream), "saf_volume_coarsen")
+            for t in old.values():
+                t.record_stream(stream)  # (the old buffers are let go below; the pass reads them on this stream)
+        # the coarse box is installed (straight into _buffers: an assignment would pay the old volume's deferred clear first)
+        b = self._buffers
+        for name, t in new.items():
+            b[name] = t
+        b["axis_x"], b["axis_y"], b["axis_z"] = ax
+        if "xyz_world" in b:
+            b["xyz_world"] = _xyz_world(ax, new_nvox)
+        self.nvox = torch.as_tensor(new_nvox, dtype=self.nvox.dtype)
+        self.index_offset = new_off
+        self.voxel_size = new_vs
+        self.origin = new_origin
+        self.__dict__["_feat_stale"] = True
+        self._workspace = None  # (sized by the grid)
+        self.__dict__["_shard16"] = None
+        for name in ("voxel_obj_idx", "objects_segmentation_color"):
+            if getattr(self, name, None) is not None:
+                delattr(self, name)
+        return GridCoarsen(factor=factor, old_origin=old_origin, old_voxel_size=old_vs, old_index_offset=old_off, old_nvox=old_nvox,
+                           origin=new_origin, voxel_size=new_vs, index_offset=new_off, nvox=new_nvox,
+                           rows_blended=counts[0], rows_copied=counts[1], tsdf_blended=counts[2], tsdf_copied=counts[3])
+
     def integrate_features(self, depth_imgs, rgb_imgs, poses, K, clip_feat_img, label_maps=None):
         """``integrate`` with the backbone outputs supplied by the caller (fuse-only entry used by
         the benchmark and the parity tests)."""
@@ -1069,6 +1156,27 @@ class GridAbsorb:
     tsdf_copied: torch.Tensor
     rows_outside: torch.Tensor
     tsdf_outside: torch.Tensor
+
+
+@dataclass
+class GridCoarsen:
+    """What ``coarsen`` returns: the factor, and the lattice and box (``origin``, ``voxel_size``, index offset, voxels per axis)
+    before and after.  The four counters are 0-d int64 DEVICE tensors -- reading one synchronises: coarse voxels whose feature row
+    (TSDF value) is the blend of two or more fine voxels, and those that are the copy of a single one."""
+
+    factor: int
+    old_origin: object
+    old_voxel_size: float
+    old_index_offset: tuple
+    old_nvox: tuple
+    origin: object
+    voxel_size: float
+    index_offset: tuple
+    nvox: tuple
+    rows_blended: torch.Tensor
+    rows_copied: torch.Tensor
+    tsdf_blended: torch.Tensor
+    tsdf_copied: torch.Tensor
 
 
 @dataclass
@@ -1703,3 +1811,25 @@ def lattice_box(fusion, xyz, trunc_m=None, union=True, multiple=4):
     m = max(int(multiple), 1)
     n = (n + m - 1) // m * m
     return tuple(int(v) for v in lo), tuple(int(v) for v in n)
+
+
+def coarse_lattice(origin, voxel_size, index_offset, nvox, factor):
+    """What ``coarsen`` makes of a box of a lattice: (origin', voxel_size', index_offset', nvox').  Global coarse voxel I covers the
+    fine global indices ``factor * I .. factor * I + factor - 1`` (floor division: blocks are aligned to the lattice, not to the
+    box), so ``voxel_size' = factor * voxel_size``, ``origin' = origin + 0.5 * (factor - 1) * voxel_size`` -- the centre of the block
+    of global coarse index 0, computed in float64 and returned in the container and dtype ``origin`` came in --, ``index_offset' =
+    floor(off / factor)`` and ``nvox' = ceil((off + n) / factor) - floor(off / factor)`` per axis.  ``origin'`` does not depend on
+    the box: two boxes of one fine lattice give two boxes of one coarse lattice.  Host only."""
+    f = int(factor)
+    off = tuple(int(v) for v in index_offset)
+    n = tuple(int(v) for v in nvox)
+    new_off = tuple(o // f for o in off)  # (Python's // is the floor division)
+    new_n = tuple(-((-(o + k)) // f) - o // f for o, k in zip(off, n))
+    o64 = torch.as_tensor(origin).detach().cpu().to(torch.float64) + 0.5 * (f - 1) * float(voxel_size)
+    if torch.is_tensor(origin):
+        new_origin = o64.to(dtype=origin.dtype, device=origin.device)
+    elif isinstance(origin, np.ndarray):
+        new_origin = o64.numpy().astype(origin.dtype)
+    else:
+        new_origin = type(origin)(o64.tolist())
+    return new_origin, f * voxel_size, new_off, new_n

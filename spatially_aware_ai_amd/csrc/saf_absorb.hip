@@ -193,15 +193,9 @@ using namespace saf;
 extern "C" int saf_volume_absorb(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z,
                                  uint64_t* counts, void* stream) {
   if (int rc = check_pair("volume_absorb", src, dst, "the source is only read: two volumes, not one")) return rc;
-  const int64_t elem = src->feat_dtype == SAF_F32 ? 4 : 2;
-  const int64_t feat_bytes = feat_row_bytes(src), label_bytes = (int64_t)src->n_classes * 4;
   // values are computed with, not only copied: the rows are arrays of their element type
-  if (((uintptr_t)src->clip_feat | (uintptr_t)dst->clip_feat) % (uintptr_t)elem != 0 ||
-      (label_bytes && ((uintptr_t)src->labels_one_hot | (uintptr_t)dst->labels_one_hot) % 4 != 0))
-    return fail(SAF_E_INVALID, "volume_absorb: a feature or label buffer is not aligned to its element type");
-  if (src->accum_mode != SAF_RUNNING_MEAN || dst->accum_mode != SAF_RUNNING_MEAN)
-    return fail(SAF_E_UNSUPPORTED, "volume_absorb: running means only (accum_mode %d and %d): the sums of a multi-rank job are added by "
-                "the merge", (int)src->accum_mode, (int)dst->accum_mode);
+  if (int rc = check_computed_pair("volume_absorb", src, dst)) return rc;
+  const int64_t feat_bytes = feat_row_bytes(src), label_bytes = (int64_t)src->n_classes * 4;
   int32_t lo[3], ext[3];
   if (!pair_overlap(src, dst, off_x, off_y, off_z, lo, ext)) return SAF_OK;  // the boxes share no voxel: nothing to absorb
   AbsorbArgs a;

@@ -1,5 +1,6 @@
-// saf_pair.h -- what the passes over a PAIR of volumes of one lattice share (saf_carry.hip: the copy; saf_absorb.hip: the blend by
-// weights): the refusals both decide on the host, the overlap box, and the row copy of a whole wave.
+// saf_pair.h -- what the passes over a PAIR of volumes share (saf_carry.hip: the copy; saf_absorb.hip: the blend by weights, both on
+// one lattice; saf_coarsen.hip: the weighted mean over blocks of the lattice): the refusals they decide on the host, the overlap box,
+// and the row copy of a whole wave.
 #pragma once
 #include "saf_host.h"
 
@@ -58,6 +59,20 @@ inline int check_pair(const char* what, const saf_volume* src, const saf_volume*
       intersect(src->clip_feat, dst->clip_feat, ns * feat_bytes, nd * feat_bytes) ||
       (label_bytes && intersect(src->labels_one_hot, dst->labels_one_hot, ns * label_bytes, nd * label_bytes)))
     return fail(SAF_E_INVALID, "%s: a destination buffer overlaps its source (%s)", what, alone);
+  return SAF_OK;
+}
+
+// What the passes that COMPUTE with the rows (saf_absorb.hip, saf_coarsen.hip) refuse on top of check_pair: SAF_E_INVALID for a
+// feature or label buffer that is not aligned to its element type (the rows are arrays of that type, not bytes), SAF_E_UNSUPPORTED
+// for a volume that holds sums.
+inline int check_computed_pair(const char* what, const saf_volume* src, const saf_volume* dst) {
+  const int64_t elem = src->feat_dtype == SAF_F32 ? 4 : 2;
+  if (((uintptr_t)src->clip_feat | (uintptr_t)dst->clip_feat) % (uintptr_t)elem != 0 ||
+      (src->n_classes > 0 && ((uintptr_t)src->labels_one_hot | (uintptr_t)dst->labels_one_hot) % 4 != 0))
+    return fail(SAF_E_INVALID, "%s: a feature or label buffer is not aligned to its element type", what);
+  if (src->accum_mode != SAF_RUNNING_MEAN || dst->accum_mode != SAF_RUNNING_MEAN)
+    return fail(SAF_E_UNSUPPORTED, "%s: running means only (accum_mode %d and %d): the sums of a multi-rank job are added by "
+                "the merge", what, (int)src->accum_mode, (int)dst->accum_mode);
   return SAF_OK;
 }
 

@@ -9,7 +9,7 @@ what this module adds is the chain and a wall-clock split per stage, the counter
 performance statement ("within a few minutes after a user scans the environment", README.md:4).  ``extend_scene`` fuses a later
 scan version's new frames into the volume a reconstruction left (not in the reference, which fuses every version from its
 first frame); ``join_scenes`` puts two reconstructions of one lattice together (``reconstruct_scene(lattice_of=...)``,
-``fusion.absorb``).
+``fusion.absorb``); ``coarsen_scene`` takes a reconstruction to a whole multiple of its voxel size (``fusion.coarsen``).
 
 The Flask app, the datasets' decoders and the DGCNN in-situ learner stay the reference's.
 """
@@ -178,9 +178,10 @@ def _fuse_one_by_one(fusion, dataset, config, device, num_workers):
 
 
 def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, scan_version, out_dir, object_meshes,
-                  marching_cubes, python_lists, prev=None):
+                  marching_cubes, python_lists, prev=None, extra=None):
     """The stages behind the fusion loop (clip_seem_fusion.py:315-424, :563-607): labels, objects, the scene mesh, per-object
-    meshes, artefacts -- shared by ``reconstruct_scene`` and ``extend_scene``.  ``clk`` has just lapped the fusion.  ``prev``
+    meshes, artefacts -- shared by ``reconstruct_scene``, ``extend_scene``, ``join_scenes`` and ``coarsen_scene`` (``extra``: entries
+    it adds to ``scene_knowledge``).  ``clk`` has just lapped the fusion.  ``prev``
     (``_describe_version`` of the previous version, or None): the discovered objects take the previous version's identities
     before anything is built from their indices."""
     # ---- the volume's artefacts (save_files_and_broadcast, :566-581) start now, on a thread of their own: nothing below writes
@@ -212,6 +213,7 @@ def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, sca
     # ---- objects (flood_fill_3d, :341-348) and the attributes the manager sets from outside (:351-372)
     scene_knowledge, voxel_obj_idx = discover_objects(onehot_to_index, class_names, class_colors, arrays=not python_lists)
     scene_knowledge["scan_version"] = scan_version
+    scene_knowledge.update(extra or {})  # (what the caller knows about this version: coarsen_scene's grid)
     matches = None
     if prev is not None:
         clk.lap("objects")
@@ -427,5 +429,31 @@ def join_scenes(result, other, class_names, class_colors=None, out_dir=None, obj
     version = int(result.scene_knowledge.get("scan_version", 0)) + 1
     res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, other.xyz)), clk, class_names, class_colors, version,
                         out_dir, object_meshes, marching_cubes, python_lists, prev=prev)
+    res.seconds = clk.seconds
+    return res
+
+
+def coarsen_scene(result, factor, class_names, class_colors=None, out_dir=None, object_meshes=True, marching_cubes=None,
+                  python_lists=False):
+    """A reconstruction at ``factor`` (2, 3 or 4) times its voxel size: ``result.fusion.coarsen(factor)`` -- every coarse voxel the
+    weighted mean of the fine voxels it covers (saf_volume_coarsen), no frame goes through the backbones again -- and
+    the stages behind the fusion run again on the coarse volume, which keeps fusing at the coarse size (``extend_scene``) and can
+    be joined with a reconstruction fused at that size on the same coarse lattice (``join_scenes``).
+
+    Returns a new ``SceneResult`` around ``result.fusion`` -- ``result`` itself describes a volume the module no longer holds --;
+    ``origin`` and ``nvox`` are the coarse volume's, ``xyz`` is ``result``'s, ``scene_knowledge["scan_version"]`` counts on from
+    ``result``'s, ``scene_knowledge`` gains ``voxel_size``, ``nvox`` and ``index_offset`` of the coarse volume (and so does
+    ``scene_knowledge.json``), ``seconds`` gains ``coarsen``.  Objects are discovered anew from the coarse labels: an object keeps
+    no identity across a coarsening (the overlap of objects across two lattices is not defined here)."""
+    clk = _Clock()
+    clk.start()
+    fusion = result.fusion
+    fusion.coarsen(factor)
+    clk.lap("coarsen")
+    version = int(result.scene_knowledge.get("scan_version", 0)) + 1
+    grid = {"voxel_size": float(fusion.voxel_size), "nvox": [int(v) for v in fusion.nvox],
+            "index_offset": [int(v) for v in fusion.index_offset]}
+    res = _after_fusion(fusion, fusion.origin, fusion.nvox, result.xyz, clk, class_names, class_colors, version, out_dir, object_meshes,
+                        marching_cubes, python_lists, extra=grid)
     res.seconds = clk.seconds
     return res
