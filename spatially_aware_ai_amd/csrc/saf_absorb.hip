@@ -11,25 +11,8 @@ namespace saf {
 namespace {
 
 struct AbsorbArgs {
-  const float* s_tsdf;
-  const int32_t* s_tsdf_weight;
-  const int32_t* s_weight;
-  const float* s_rgb;
-  const unsigned char* s_feat;
-  const unsigned char* s_labels;  // NULL: no label histograms
-  float* d_tsdf;
-  int32_t* d_tsdf_weight;
-  int32_t* d_weight;
-  float* d_rgb;
-  unsigned char* d_feat;
-  unsigned char* d_labels;
-  unsigned long long* counts;  // NULL: not counted
-  int64_t feat_bytes, label_bytes;  // bytes per row
-  int32_t feat_unit, label_unit;    // bytes per lane and access: 16, 4 or 2 (labels: 16 or 4)
-  int32_t ex, ey, ez;               // the overlap box, in voxels
-  int32_t lx, ly, lz;               // its low corner in the destination
-  int32_t ox, oy, oz;               // destination index + o = source index
-  int32_t s_ny, s_nz, d_ny, d_nz;
+  PairRows r;
+  PairBox b;
 };
 
 // The two coefficients of a blend of counts ws, wd > 0: cs = ws * r, cd = wd * r, r = RN(1 / (float)(ws + wd)).
@@ -109,80 +92,65 @@ template <int KIND>
 __global__ __launch_bounds__(256) void absorb_kernel(const AbsorbArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
-  const int64_t n = (int64_t)a.ex * a.ey * a.ez;  // fewer than 2^31: the overlap lies inside both grids
-  const uint32_t ez = (uint32_t)a.ez, ey = (uint32_t)a.ey;
+  const int64_t n = a.b.voxels();
   unsigned long long n_blend = 0, n_copy = 0, n_tblend = 0, n_tcopy = 0;
   for (int64_t i0 = wave * 64; i0 < n; i0 += n_waves * 64) {
     const int64_t i = i0 + lane;
-    int32_t sv = 0, dv = 0;  // flat voxel indices (both grids hold fewer than 2^31 voxels)
+    int32_t sv = 0, dv = 0;  // flat voxel indices
     bool copy = false, blend = false, tcopy = false, tblend = false;
     Coef c{0.0f, 0.0f};
     if (i < n) {
-      const uint32_t q = (uint32_t)i / ez, z = (uint32_t)i - q * ez;
-      const uint32_t x = q / ey, y = q - x * ey;
-      const int32_t dx = a.lx + (int32_t)x, dy = a.ly + (int32_t)y, dz = a.lz + (int32_t)z;
-      dv = (dx * a.d_ny + dy) * a.d_nz + dz;
-      sv = ((dx + a.ox) * a.s_ny + (dy + a.oy)) * a.s_nz + (dz + a.oz);
-      const int32_t ws = a.s_weight[sv], tws = a.s_tsdf_weight[sv];
-      const int32_t wd = a.d_weight[dv], twd = a.d_tsdf_weight[dv];
+      const PairVoxel v = a.b.voxel(i);
+      sv = v.sv, dv = v.dv;
+      const int32_t ws = a.r.s_weight[sv], tws = a.r.s_tsdf_weight[sv];
+      const int32_t wd = a.r.d_weight[dv], twd = a.r.d_tsdf_weight[dv];
       // the TSDF side
       tcopy = tws > 0 && twd <= 0;
       tblend = tws > 0 && twd > 0;
       if (tcopy) {
-        a.d_tsdf[dv] = a.s_tsdf[sv];
-        a.d_tsdf_weight[dv] = tws;
+        a.r.d_tsdf[dv] = a.r.s_tsdf[sv];
+        a.r.d_tsdf_weight[dv] = tws;
       } else if (tblend) {
         const Coef t = coef(tws, twd);
-        a.d_tsdf[dv] = mix(a.s_tsdf[sv], a.d_tsdf[dv], t.cs, t.cd);
-        a.d_tsdf_weight[dv] = twd + tws;
+        a.r.d_tsdf[dv] = mix(a.r.s_tsdf[sv], a.r.d_tsdf[dv], t.cs, t.cd);
+        a.r.d_tsdf_weight[dv] = twd + tws;
       }
       // the feature side: weight and rgb here, the rows below
       copy = ws > 0 && wd <= 0;
       blend = ws > 0 && wd > 0;
-      const float* sc = a.s_rgb + (int64_t)sv * 3;
-      float* dc = a.d_rgb + (int64_t)dv * 3;
+      const float* sc = a.r.s_rgb + (int64_t)sv * 3;
+      float* dc = a.r.d_rgb + (int64_t)dv * 3;
       if (copy) {
         dc[0] = sc[0];
         dc[1] = sc[1];
         dc[2] = sc[2];
-        a.d_weight[dv] = ws;
+        a.r.d_weight[dv] = ws;
       } else if (blend) {
         c = coef(ws, wd);
         const float r0 = mix(sc[0], dc[0], c.cs, c.cd), r1 = mix(sc[1], dc[1], c.cs, c.cd), r2 = mix(sc[2], dc[2], c.cs, c.cd);
         dc[0] = r0;
         dc[1] = r1;
         dc[2] = r2;
-        a.d_weight[dv] = wd + ws;
+        a.r.d_weight[dv] = wd + ws;
       }
     }
-    unsigned long long mc = __ballot(copy), mb = __ballot(blend);
+    const unsigned long long mc = __ballot(copy);
+    unsigned long long mb = __ballot(blend);
     n_copy += __popcll(mc);
     n_blend += __popcll(mb);
     n_tcopy += __popcll(__ballot(tcopy));
     n_tblend += __popcll(__ballot(tblend));
-    while (mc) {
-      const int l = __builtin_ctzll(mc);
-      mc &= mc - 1;
-      const int64_t s = __shfl(sv, l), d = __shfl(dv, l);
-      copy_row(a.d_feat + d * a.feat_bytes, a.s_feat + s * a.feat_bytes, a.feat_bytes, a.feat_unit, lane);
-      if (a.s_labels) copy_row(a.d_labels + d * a.label_bytes, a.s_labels + s * a.label_bytes, a.label_bytes, a.label_unit, lane);
-    }
+    copy_rows(mc, sv, dv, lane, a.r);
     while (mb) {
       const int l = __builtin_ctzll(mb);
       mb &= mb - 1;
       const int64_t s = __shfl(sv, l), d = __shfl(dv, l);
       const float cs = __shfl(c.cs, l), cd = __shfl(c.cd, l);  // (the voxel's own lane computed them: the same bits)
-      blend_row<KIND>(a.d_feat + d * a.feat_bytes, a.s_feat + s * a.feat_bytes, a.feat_bytes, a.feat_unit, lane, cs, cd);
-      if (a.s_labels) add_row(a.d_labels + d * a.label_bytes, a.s_labels + s * a.label_bytes, a.label_bytes, a.label_unit, lane);
+      blend_row<KIND>(a.r.d_feat + d * a.r.feat_bytes, a.r.s_feat + s * a.r.feat_bytes, a.r.feat_bytes, a.r.feat_unit, lane, cs, cd);
+      if (a.r.s_labels) add_row(a.r.d_labels + d * a.r.label_bytes, a.r.s_labels + s * a.r.label_bytes, a.r.label_bytes, a.r.label_unit, lane);
     }
   }
-  // integer adds: the totals are exact whatever the order
-  if (a.counts && lane == 0) {
-    if (n_blend) atomicAdd(a.counts + 0, n_blend);
-    if (n_copy) atomicAdd(a.counts + 1, n_copy);
-    if (n_tblend) atomicAdd(a.counts + 2, n_tblend);
-    if (n_tcopy) atomicAdd(a.counts + 3, n_tcopy);
-  }
+  add_counts(a.r.counts, lane, n_blend, n_copy, n_tblend, n_tcopy);
 }
 
 }  // namespace
@@ -195,26 +163,11 @@ extern "C" int saf_volume_absorb(const saf_volume* src, const saf_volume* dst, i
   if (int rc = check_pair("volume_absorb", src, dst, "the source is only read: two volumes, not one")) return rc;
   // values are computed with, not only copied: the rows are arrays of their element type
   if (int rc = check_computed_pair("volume_absorb", src, dst)) return rc;
-  const int64_t feat_bytes = feat_row_bytes(src), label_bytes = (int64_t)src->n_classes * 4;
-  int32_t lo[3], ext[3];
-  if (!pair_overlap(src, dst, off_x, off_y, off_z, lo, ext)) return SAF_OK;  // the boxes share no voxel: nothing to absorb
   AbsorbArgs a;
-  a.s_tsdf = src->tsdf, a.s_tsdf_weight = src->tsdf_weight, a.s_weight = src->weight, a.s_rgb = src->rgb;
-  a.s_feat = static_cast<const unsigned char*>(src->clip_feat);
-  a.s_labels = label_bytes ? reinterpret_cast<const unsigned char*>(src->labels_one_hot) : nullptr;
-  a.d_tsdf = dst->tsdf, a.d_tsdf_weight = dst->tsdf_weight, a.d_weight = dst->weight, a.d_rgb = dst->rgb;
-  a.d_feat = static_cast<unsigned char*>(dst->clip_feat);
-  a.d_labels = label_bytes ? reinterpret_cast<unsigned char*>(dst->labels_one_hot) : nullptr;
-  a.counts = reinterpret_cast<unsigned long long*>(counts);
-  a.feat_bytes = feat_bytes, a.label_bytes = label_bytes;
-  a.feat_unit = copy_unit(feat_bytes, a.s_feat, a.d_feat);
-  a.label_unit = label_bytes ? copy_unit(label_bytes, a.s_labels, a.d_labels) : 4;
-  a.ex = ext[0], a.ey = ext[1], a.ez = ext[2];
-  a.lx = lo[0], a.ly = lo[1], a.lz = lo[2];
-  a.ox = off_x, a.oy = off_y, a.oz = off_z;
-  a.s_ny = src->ny, a.s_nz = src->nz, a.d_ny = dst->ny, a.d_nz = dst->nz;
+  if (!pair_overlap(src, dst, off_x, off_y, off_z, &a.b)) return SAF_OK;  // the boxes share no voxel: nothing to absorb
+  a.r = pair_rows(src, dst, counts);
   // (64 voxels per wave and step, 4 waves per workgroup)
-  const dim3 grid(grid_1d((int64_t)ext[0] * ext[1] * ext[2], 16));
+  const dim3 grid(grid_1d(a.b.voxels(), 16));
   return dispatch_ft(src->feat_dtype, [&](auto ft) {
     hipLaunchKernelGGL(absorb_kernel<decltype(ft)::value>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return check_launch("absorb_kernel");

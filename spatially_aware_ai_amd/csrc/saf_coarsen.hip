@@ -12,21 +12,7 @@ namespace saf {
 namespace {
 
 struct CoarsenArgs {
-  const float* s_tsdf;
-  const int32_t* s_tsdf_weight;
-  const int32_t* s_weight;
-  const float* s_rgb;
-  const unsigned char* s_feat;
-  const unsigned char* s_labels;  // NULL: no label histograms
-  float* d_tsdf;
-  int32_t* d_tsdf_weight;
-  int32_t* d_weight;
-  float* d_rgb;
-  unsigned char* d_feat;
-  unsigned char* d_labels;
-  unsigned long long* counts;  // NULL: not counted
-  int64_t feat_bytes, label_bytes;  // bytes per row
-  int32_t feat_unit, label_unit;    // bytes per lane and access: 16, 4 or 2 (labels: 16 or 4)
+  PairRows r;
   int32_t s_nx, s_ny, s_nz;         // the fine box
   int32_t d_nx, d_ny, d_nz;         // the coarse box
   int32_t bx, by, bz;               // the fine box's own index of child 0 of coarse voxel 0: f * floor(off / f) - off, in -(f - 1) .. 0
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(256) void coarsen_kernel(const CoarsenArgs a) {
           for (int cz = 0; cz < F; ++cz) {
             const int32_t pz = fz0 + cz;
             if ((uint32_t)pz >= (uint32_t)a.s_nz) continue;
-            const int32_t w = a.s_weight[base + pz], tw = a.s_tsdf_weight[base + pz];
+            const int32_t w = a.r.s_weight[base + pz], tw = a.r.s_tsdf_weight[base + pz];
             if (w > 0) ++kf, wsum += w, wmax = w > wmax ? w : wmax;
             if (tw > 0) ++kt, tsum += tw, tmax = tw > tmax ? tw : tmax;
           }
@@ -190,9 +176,9 @@ __global__ __launch_bounds__(256) void coarsen_kernel(const CoarsenArgs a) {
               const int32_t pz = fz0 + cz;
               if ((uint32_t)pz >= (uint32_t)a.s_nz) continue;
               const int32_t fv = base + pz;
-              const int32_t w = a.s_weight[fv], tw = a.s_tsdf_weight[fv];
+              const int32_t w = a.r.s_weight[fv], tw = a.r.s_tsdf_weight[fv];
               if (w > 0) {  // (the values of a child with count 0 are never read)
-                const float* sc = a.s_rgb + (int64_t)fv * 3;
+                const float* sc = a.r.s_rgb + (int64_t)fv * 3;
                 if (kf == 1) {
                   c0 = sc[0], c1 = sc[1], c2 = sc[2];
                 } else {
@@ -203,9 +189,9 @@ __global__ __launch_bounds__(256) void coarsen_kernel(const CoarsenArgs a) {
               }
               if (tw > 0) {
                 if (kt == 1) {
-                  t = a.s_tsdf[fv];
+                  t = a.r.s_tsdf[fv];
                 } else {
-                  t = step(t, a.s_tsdf[fv], (float)tw * rt, tfirst);
+                  t = step(t, a.r.s_tsdf[fv], (float)tw * rt, tfirst);
                   tfirst = false;
                 }
               }
@@ -213,11 +199,11 @@ __global__ __launch_bounds__(256) void coarsen_kernel(const CoarsenArgs a) {
           }
         }
       }
-      float* dc = a.d_rgb + i * 3;
+      float* dc = a.r.d_rgb + i * 3;
       dc[0] = c0, dc[1] = c1, dc[2] = c2;
-      a.d_weight[i] = wmax;
-      a.d_tsdf[i] = t;
-      a.d_tsdf_weight[i] = tmax;
+      a.r.d_weight[i] = wmax;
+      a.r.d_tsdf[i] = t;
+      a.r.d_tsdf_weight[i] = tmax;
     }
     unsigned long long rows = __ballot(kf > 0);
     n_copy += __popcll(__ballot(kf == 1));
@@ -231,41 +217,35 @@ __global__ __launch_bounds__(256) void coarsen_kernel(const CoarsenArgs a) {
       const int32_t px = bcast(fx0, l) + jx, py = bcast(fy0, l) + jy, pz = bcast(fz0, l) + jz;
       const bool ok = lane < F3 && (uint32_t)px < (uint32_t)a.s_nx && (uint32_t)py < (uint32_t)a.s_ny && (uint32_t)pz < (uint32_t)a.s_nz;
       const int32_t fi = ok ? (px * a.s_ny + py) * a.s_nz + pz : 0;
-      const int32_t wj = ok ? a.s_weight[fi] : 0;
+      const int32_t wj = ok ? a.r.s_weight[fi] : 0;
       const unsigned long long cm = __ballot(wj > 0);  // (as many bits as lane l counted: kf)
       const int64_t dv = i0 + l;
-      unsigned char* df = a.d_feat + dv * a.feat_bytes;
-      unsigned char* dl = a.s_labels ? a.d_labels + dv * a.label_bytes : nullptr;
+      unsigned char* df = a.r.d_feat + dv * a.r.feat_bytes;
+      unsigned char* dl = a.r.s_labels ? a.r.d_labels + dv * a.r.label_bytes : nullptr;
       if ((cm & (cm - 1)) == 0) {  // one contributing child: its bytes
         const int64_t sv = bcast(fi, __builtin_ctzll(cm));
-        copy_row(df, a.s_feat + sv * a.feat_bytes, a.feat_bytes, a.feat_unit, lane);
-        if (dl) copy_row(dl, a.s_labels + sv * a.label_bytes, a.label_bytes, a.label_unit, lane);
+        copy_row(df, a.r.s_feat + sv * a.r.feat_bytes, a.r.feat_bytes, a.r.feat_unit, lane);
+        if (dl) copy_row(dl, a.r.s_labels + sv * a.r.label_bytes, a.r.label_bytes, a.r.label_unit, lane);
       } else {
         const float cf = (float)wj * bcast(rf, l);
-        if (a.feat_unit == 16) {
-          combine_rows<KIND, 16>(df, a.s_feat, a.feat_bytes, lane, fi, cf, cm);
-        } else if (a.feat_unit == 4) {
-          combine_rows<KIND, 4>(df, a.s_feat, a.feat_bytes, lane, fi, cf, cm);
+        if (a.r.feat_unit == 16) {
+          combine_rows<KIND, 16>(df, a.r.s_feat, a.r.feat_bytes, lane, fi, cf, cm);
+        } else if (a.r.feat_unit == 4) {
+          combine_rows<KIND, 4>(df, a.r.s_feat, a.r.feat_bytes, lane, fi, cf, cm);
         } else if (KIND != SAF_F32) {  // (an f32 row is never taken 2 bytes at a time: the entry refuses it)
-          combine_rows<KIND, 2>(df, a.s_feat, a.feat_bytes, lane, fi, cf, cm);
+          combine_rows<KIND, 2>(df, a.r.s_feat, a.r.feat_bytes, lane, fi, cf, cm);
         }
         if (dl) {
-          if (a.label_unit == 16) {
-            combine_rows<kLabels, 16>(dl, a.s_labels, a.label_bytes, lane, fi, cf, cm);
+          if (a.r.label_unit == 16) {
+            combine_rows<kLabels, 16>(dl, a.r.s_labels, a.r.label_bytes, lane, fi, cf, cm);
           } else {
-            combine_rows<kLabels, 4>(dl, a.s_labels, a.label_bytes, lane, fi, cf, cm);
+            combine_rows<kLabels, 4>(dl, a.r.s_labels, a.r.label_bytes, lane, fi, cf, cm);
           }
         }
       }
     }
   }
-  // integer adds: the totals are exact whatever the order
-  if (a.counts && lane == 0) {
-    if (n_blend) atomicAdd(a.counts + 0, n_blend);
-    if (n_copy) atomicAdd(a.counts + 1, n_copy);
-    if (n_tblend) atomicAdd(a.counts + 2, n_tblend);
-    if (n_tcopy) atomicAdd(a.counts + 3, n_tcopy);
-  }
+  add_counts(a.r.counts, lane, n_blend, n_copy, n_tblend, n_tcopy);
 }
 
 // floor(a / f), f > 0
@@ -301,18 +281,8 @@ extern "C" int saf_volume_coarsen(const saf_volume* src, const saf_volume* dst, 
                   (int)src->nz, (int)off_x, (int)off_y, (int)off_z, (int)factor, (long long)(hi - lo));
     b[k] = (int32_t)(f * lo - off[k]);
   }
-  const int64_t feat_bytes = feat_row_bytes(src), label_bytes = (int64_t)src->n_classes * 4;
   CoarsenArgs a;
-  a.s_tsdf = src->tsdf, a.s_tsdf_weight = src->tsdf_weight, a.s_weight = src->weight, a.s_rgb = src->rgb;
-  a.s_feat = static_cast<const unsigned char*>(src->clip_feat);
-  a.s_labels = label_bytes ? reinterpret_cast<const unsigned char*>(src->labels_one_hot) : nullptr;
-  a.d_tsdf = dst->tsdf, a.d_tsdf_weight = dst->tsdf_weight, a.d_weight = dst->weight, a.d_rgb = dst->rgb;
-  a.d_feat = static_cast<unsigned char*>(dst->clip_feat);
-  a.d_labels = label_bytes ? reinterpret_cast<unsigned char*>(dst->labels_one_hot) : nullptr;
-  a.counts = reinterpret_cast<unsigned long long*>(counts);
-  a.feat_bytes = feat_bytes, a.label_bytes = label_bytes;
-  a.feat_unit = copy_unit(feat_bytes, a.s_feat, a.d_feat);
-  a.label_unit = label_bytes ? copy_unit(label_bytes, a.s_labels, a.d_labels) : 4;
+  a.r = pair_rows(src, dst, counts);
   a.s_nx = src->nx, a.s_ny = src->ny, a.s_nz = src->nz;
   a.d_nx = dst->nx, a.d_ny = dst->ny, a.d_nz = dst->nz;
   a.bx = b[0], a.by = b[1], a.bz = b[2];

@@ -1,6 +1,6 @@
 // saf_pair.h -- what the passes over a PAIR of volumes share (saf_carry.hip: the copy; saf_absorb.hip: the blend by weights, both on
-// one lattice; saf_coarsen.hip: the weighted mean over blocks of the lattice): the refusals they decide on the host, the overlap box,
-// and the row copy of a whole wave.
+// one lattice; saf_coarsen.hip: the weighted mean over blocks of the lattice): the refusals they decide on the host, the shared
+// halves of their kernel arguments (PairRows: the buffers; PairBox: the overlap box), and the row copies of a whole wave.
 #pragma once
 #include "saf_host.h"
 
@@ -20,6 +20,48 @@ __device__ __forceinline__ void copy_row(unsigned char* __restrict__ d, const un
   }
 }
 
+// The buffers of both volumes as a kernel reads them, the totals, and how a whole wave takes a row.
+struct PairRows {
+  const float* s_tsdf;
+  const int32_t* s_tsdf_weight;
+  const int32_t* s_weight;
+  const float* s_rgb;
+  const unsigned char* s_feat;
+  const unsigned char* s_labels;  // NULL: no label histograms
+  float* d_tsdf;
+  int32_t* d_tsdf_weight;
+  int32_t* d_weight;
+  float* d_rgb;
+  unsigned char* d_feat;
+  unsigned char* d_labels;
+  unsigned long long* counts;  // NULL: not counted
+  int64_t feat_bytes, label_bytes;  // bytes per row
+  int32_t feat_unit, label_unit;    // bytes per lane and access: 16, 4 or 2 (labels: 16 or 4)
+};
+
+// The whole wave copies the feature row and the label row of every voxel named in the ballot `m`, one after the other (bit l: the
+// voxel whose flat indices lane l holds in `sv` / `dv`).
+__device__ __forceinline__ void copy_rows(unsigned long long m, int32_t sv, int32_t dv, int lane, const PairRows& r) {
+  while (m) {
+    const int l = __builtin_ctzll(m);
+    m &= m - 1;
+    const int64_t s = __shfl(sv, l), d = __shfl(dv, l);
+    copy_row(r.d_feat + d * r.feat_bytes, r.s_feat + s * r.feat_bytes, r.feat_bytes, r.feat_unit, lane);
+    if (r.s_labels) copy_row(r.d_labels + d * r.label_bytes, r.s_labels + s * r.label_bytes, r.label_bytes, r.label_unit, lane);
+  }
+}
+
+// Lane 0 adds the wave's non-zero totals, two or four of them, to `counts` (integer adds: the totals are exact whatever the order).
+__device__ __forceinline__ void add_counts(unsigned long long* counts, int lane, unsigned long long t0, unsigned long long t1,
+                                           unsigned long long t2 = 0, unsigned long long t3 = 0) {
+  if (counts && lane == 0) {
+    if (t0) atomicAdd(counts + 0, t0);
+    if (t1) atomicAdd(counts + 1, t1);
+    if (t2) atomicAdd(counts + 2, t2);
+    if (t3) atomicAdd(counts + 3, t3);
+  }
+}
+
 // [p, p + bytes) of the two buffers of one name share a byte
 inline bool intersect(const void* s, const void* d, int64_t s_bytes, int64_t d_bytes) {
   const uintptr_t sp = (uintptr_t)s, dp = (uintptr_t)d;
@@ -33,6 +75,22 @@ inline int copy_unit(int64_t row_bytes, const void* s, const void* d) {
 }
 
 inline int64_t feat_row_bytes(const saf_volume* v) { return (int64_t)v->feat_dim * (v->feat_dtype == SAF_F32 ? 4 : 2); }
+
+// (of a pair that check_pair has taken)
+inline PairRows pair_rows(const saf_volume* src, const saf_volume* dst, uint64_t* counts) {
+  PairRows r;
+  r.feat_bytes = feat_row_bytes(src), r.label_bytes = (int64_t)src->n_classes * 4;
+  r.s_tsdf = src->tsdf, r.s_tsdf_weight = src->tsdf_weight, r.s_weight = src->weight, r.s_rgb = src->rgb;
+  r.s_feat = static_cast<const unsigned char*>(src->clip_feat);
+  r.s_labels = r.label_bytes ? reinterpret_cast<const unsigned char*>(src->labels_one_hot) : nullptr;
+  r.d_tsdf = dst->tsdf, r.d_tsdf_weight = dst->tsdf_weight, r.d_weight = dst->weight, r.d_rgb = dst->rgb;
+  r.d_feat = static_cast<unsigned char*>(dst->clip_feat);
+  r.d_labels = r.label_bytes ? reinterpret_cast<unsigned char*>(dst->labels_one_hot) : nullptr;
+  r.counts = reinterpret_cast<unsigned long long*>(counts);
+  r.feat_unit = copy_unit(r.feat_bytes, r.s_feat, r.d_feat);
+  r.label_unit = r.label_bytes ? copy_unit(r.label_bytes, r.s_labels, r.d_labels) : 4;
+  return r;
+}
 
 // SAF_E_INVALID for what no pass over a pair takes: a NULL volume or buffer, bad sizes, 2^31 voxels or more, an unknown feature
 // dtype, volumes that differ in feat_dim, feat_dtype or n_classes, a destination buffer that shares a byte with the source buffer
@@ -76,17 +134,42 @@ inline int check_computed_pair(const char* what, const saf_volume* src, const sa
   return SAF_OK;
 }
 
+struct PairVoxel {
+  int32_t sv, dv;  // one voxel's flat index in the source and in the destination (both grids hold fewer than 2^31 voxels)
+};
+
+// The box two volumes of one lattice share, as a kernel walks it.
+struct PairBox {
+  int32_t ex, ey, ez;  // the overlap box, in voxels
+  int32_t lx, ly, lz;  // its low corner in the destination
+  int32_t ox, oy, oz;  // destination index + o = source index
+  int32_t s_ny, s_nz, d_ny, d_nz;
+
+  // fewer than 2^31: the overlap lies inside both grids
+  __host__ __device__ int64_t voxels() const { return (int64_t)ex * ey * ez; }
+
+  // voxel `i` of the FLATTENED box (z fastest, as the volumes are laid out)
+  __device__ __forceinline__ PairVoxel voxel(int64_t i) const {
+    const uint32_t q = (uint32_t)i / (uint32_t)ez, z = (uint32_t)i - q * (uint32_t)ez;
+    const uint32_t x = q / (uint32_t)ey, y = q - x * (uint32_t)ey;
+    const int32_t dx = lx + (int32_t)x, dy = ly + (int32_t)y, dz = lz + (int32_t)z;
+    const int32_t dv = (dx * d_ny + dy) * d_nz + dz;
+    return PairVoxel{((dx + ox) * s_ny + (dy + oy)) * s_nz + (dz + oz), dv};
+  }
+};
+
 // The overlap in destination indices: 0 <= x < dst.n and 0 <= x + off < src.n, per axis (int64: off may be anything).  False: the
 // boxes share no voxel.
-inline bool pair_overlap(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z, int32_t lo[3],
-                         int32_t ext[3]) {
+inline bool pair_overlap(const saf_volume* src, const saf_volume* dst, int32_t off_x, int32_t off_y, int32_t off_z, PairBox* b) {
   const int64_t off[3] = {off_x, off_y, off_z}, sn[3] = {src->nx, src->ny, src->nz}, dn[3] = {dst->nx, dst->ny, dst->nz};
+  int32_t lo[3], ext[3];
   for (int k = 0; k < 3; ++k) {
     const int64_t l = off[k] < 0 ? -off[k] : 0, h = dn[k] < sn[k] - off[k] ? dn[k] : sn[k] - off[k];
     if (h <= l) return false;
     lo[k] = (int32_t)l;
     ext[k] = (int32_t)(h - l);
   }
+  *b = PairBox{ext[0], ext[1], ext[2], lo[0], lo[1], lo[2], off_x, off_y, off_z, src->ny, src->nz, dst->ny, dst->nz};
   return true;
 }
 
