@@ -30,7 +30,7 @@
 // tools/valu_probe.hip).  A sample is a convex combination of
 // map values, so with M = the largest magnitude of the slab's channels in the window's maps (chan_max_kernel) and k_max =
 // the most hits any row of the brick takes in this round, |sum| <= k_max M: every sample is scaled by the power of two
-// 2^(30 - ceil(log2 k_max) - ceil(log2 M)) (exact; folded into the bilinear weights), rounded to the nearest integer (the
+// 2^(30 - ceil(log2 k_max) - ceil(log2 M)) (exact; folded into the bilinear weights), rounded to the nearest integer, ties to even (the
 // only error: half a unit of M 2^-28 at k_max = 4, of M 2^-23 at 128 -- no more than the rounding of an fp32 running mean
 // of values near M) and added with ds_add_u32.  Integer adds commute: the result does not depend on the order in which
 // the walkers' adds arrive and is reproducible bit for bit.  A window whose maps hold a non-finite value (no number to
@@ -161,12 +161,11 @@ __device__ __forceinline__ int rfl(int x) { return __builtin_amdgcn_readfirstlan
 __device__ __forceinline__ float rl_f(float x, int l) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
 }
-// floor(x + 0.5) as an integer (one instruction; v_rndne + v_cvt would be two)
-__device__ __forceinline__ int cvt_rpi(float x) {
-  int q;
-  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(q) : "v"(x));
-  return q;
-}
+// x to the nearest integer, ties to even (v_rndne_f32 + v_cvt_i32_f32).  Not floor(x + 0.5) (v_cvt_rpi_i32_f32, one instruction
+// less): that sends every tie up, and ties are common -- at k_max = 64 a sample of magnitude M/4 .. M/2 has one fraction bit left
+// after scaling -- so the fixed-point sums of negated maps were not the negated sums, and every sum carried an upward bias that
+// k hits add up instead of averaging out (tests/test_feature_families_gpu.py, family `neg`).
+__device__ __forceinline__ int cvt_rne(float x) { return (int)__builtin_rintf(x); }
 
 __device__ __forceinline__ Cam cam_from(const float* __restrict__ c, const Cam& u) {
   Cam r = u;
@@ -292,7 +291,7 @@ __device__ __forceinline__ void walk_process(BrickLds<CPL>& L, const WalkCtx& cx
         for (int c = 0; c < CPL; ++c) {
           const float s = sv[c];
           if (FX) {
-            __hip_atomic_fetch_add(&L.acc[idx + c * 64], cvt_rpi(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(&L.acc[idx + c * 64], cvt_rne(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           } else {
             __hip_atomic_fetch_add(reinterpret_cast<float*>(&L.acc[idx + c * 64]), s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           }

@@ -96,16 +96,24 @@ class Removed:
     labels: np.ndarray    # [N, n_classes] votes, or None
 
 
-def removed_samples(oracle, grid, frames, dim, seem):
-    """Fuse each frame alone into an empty ``OracleVolume``; where its count is 1 the stored values are the frame's samples."""
-    n = int(np.prod([int(v) for v in grid.nvox]))
-    r = Removed(np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n), np.zeros((n, 3)), np.zeros((n, dim)), np.zeros(n),
-                np.zeros((n, 3)), np.zeros(n), np.zeros((n, 143), np.int64) if seem else None)
+def frames_alone(oracle, grid, frames, dim, seem):
+    """Fuse each frame ALONE into an empty ``OracleVolume`` and yield ``(frame, volume, hit_w, hit_t)``: where the volume's
+    count is 1 (``hit_w`` on the weight side, ``hit_t`` on the tsdf_weight side) its stored values are the frame's samples
+    (s * 1 + 0 * 0).  The loop ``removed_samples`` and tests/feature_family_reference.py share."""
     for f in frames:
         one = oracle.OracleVolume(grid.origin, grid.voxel_size, grid.nvox, grid.trunc, dim, 143 if seem else 0)
         one.integrate(f["depth"], f["rgb"], f["pose"], f["K"], f["feat"], [f["labels"].float()] if seem else None, rgb_bilinear=seem)
         hit_w, hit_t = one.weight.numpy() == 1, one.tsdf_weight.numpy() == 1
         assert int(one.weight.max()) <= 1 and int(one.tsdf_weight.max()) <= 1
+        yield f, one, hit_w, hit_t
+
+
+def removed_samples(oracle, grid, frames, dim, seem):
+    """Fuse each frame alone into an empty ``OracleVolume``; where its count is 1 the stored values are the frame's samples."""
+    n = int(np.prod([int(v) for v in grid.nvox]))
+    r = Removed(np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n), np.zeros((n, 3)), np.zeros((n, dim)), np.zeros(n),
+                np.zeros((n, 3)), np.zeros(n), np.zeros((n, 143), np.int64) if seem else None)
+    for _, one, hit_w, hit_t in frames_alone(oracle, grid, frames, dim, seem):
         r.k_w += hit_w
         r.k_t += hit_t
         r.s_tsdf += one.tsdf.numpy().astype(np.float64)  # (zero where the frame did not hit)
