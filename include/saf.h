@@ -596,7 +596,7 @@ int saf_merge_add_packed(void* dst, int64_t row_bytes, int32_t is_float, const i
  * `src` and `dst` are two boxes of one lattice -- same origin, same voxel size, corners that differ by whole voxels -- so the pass
  * is a copy and nothing is recomputed (blending two volumes of one lattice: saf_volume_absorb below;
  * coarsening by a whole factor on block boundaries of the lattice: saf_volume_coarsen below; resampling onto any other lattice
- * -- rotated, a fractional factor, finer -- is not offered).
+ * -- rotated, a fractional factor, finer -- under a rigid transform: saf_volume_resample below).
  *   mapping   destination voxel (x, y, z) corresponds to source voxel (x + off_x, y + off_y, z + off_z); the caller passes
  *             off = dst's index offset - src's.  The OVERLAP is the set of destination voxels whose source voxel lies inside
  *             `src`.  A destination voxel outside the overlap is not touched: every buffer keeps its bytes there.
@@ -706,6 +706,72 @@ int saf_volume_absorb(const saf_volume* src, const saf_volume* dst, int32_t off_
  */
 int saf_volume_coarsen(const saf_volume* src, const saf_volume* dst, int32_t factor, int32_t off_x, int32_t off_y, int32_t off_z,
                        uint64_t* counts, void* stream);
+
+/*
+ * A fused volume resampled onto ANY OTHER lattice under a rigid transform -- rotated, shifted by a fraction of a voxel, finer,
+ * coarser by any factor (additive under ABI 7; new capability, nothing to mirror in the reference, which pushes every frame
+ * through the backbones again into the other grid).  A PULL resample: every destination voxel looks up the
+ * eight source voxels around its own centre and blends the observed ones by their trilinear weights, renormalised.  `src` is only
+ * read; `dst` is another set of buffers (the pass works out of place only).
+ *   mapping   m12 (HOST memory, row-major 3 x 4, read during the call) takes a destination voxel's local index (x, y, z) to a
+ *             continuous local source index p.  The caller builds it in float64 and rounds it once to f32: from the centre
+ *             world_new = (i + off_dst) vs_dst + origin_dst, world_old = inv(T) world_new for the rigid 4 x 4 T = new_from_old, and
+ *             p = (world_old - origin_src) / vs_src - off_src.  On the device, per axis a,
+ *             p_a = ((m_a0 (float)x + m_a1 (float)y) + m_a2 (float)z) + m_a3: four roundings, no FMA.  If p_a < -1 or
+ *             p_a >= (float)n_a on any axis -- compared in float before any conversion -- the voxel has no corner.  Otherwise
+ *             i_a = floorf(p_a) and f_a = p_a - (float)i_a (f_a may round to 1.0 for a tiny negative p_a: harmless).  The pass
+ *             does not inspect trunc or the axis tables; trunc does not change (TSDF values are in units of trunc), so a T that
+ *             scales is the caller's to refuse.
+ *   corners   corner k = 4 dx + 2 dy + dz (ascending source flat index) is source voxel (i_x + dx, i_y + dy, i_z + dz); its
+ *             trilinear weight is t_k = (a_x * a_y) * a_z with a = f_a where the corner's bit is 1 and 1.0f - f_a where it is 0.
+ *   per voxel  two independent sides, as in absorb and coarsen: the feature side (driven by `weight`; it owns weight, the three rgb
+ *             floats, the feature row and, with n_classes > 0, the label histogram row) and the TSDF side (driven by `tsdf_weight`;
+ *             it owns tsdf_weight and tsdf).  On each side a corner CONTRIBUTES if it lies inside the source box, its count is
+ *             > 0 and t_k > 0.  K = the number of contributing corners, S = the f32 sum of their t_k in ascending k, starting
+ *             from the first contributing one.
+ *   gate      the side is observed at this voxel iff K >= 1 and S >= min_cover (0 < min_cover <= 1; 0.5 is the module's default):
+ *             without the gate one faint corner (t = 0.01) would carry its value a whole voxel outward and every surface would
+ *             grow a fringe.  Not observed: the small fields of that side are written 0; the feature and label rows are NOT
+ *             WRITTEN: the caller supplies a destination whose weight-0 rows are zero, or owes it the deferred clear
+ *             (saf_clear_unwritten_rows).
+ *   K == 1    (observed) a copy of that corner's bytes: values, row, labels.
+ *   K >= 2    (observed) r = 1.0f / S by IEEE division, c_k = t_k * r, acc = x_1 * c_1 for the first contributing corner, then
+ *             acc = acc + x_k * c_k in order: every product and every sum rounded on its own, no FMA.  For each rgb channel and
+ *             each feature channel, and for tsdf on its own side.  16-bit rows (SAF_BF16, SAF_F16) are widened exactly,
+ *             accumulated in fp32 and narrowed ONCE, round to nearest even.  The counts do NOT enter the coefficients: a count is
+ *             confidence, not position, and weighting by it would pull an interpolated TSDF towards the better-seen corner.
+ *   counts    stored: weight' = the maximum of the contributing corners' counts, and likewise tsdf_weight' (coarsen's rule and
+ *             coarsen's reason: a later frame's sample stays worth one frame).
+ *   labels    the label histogram row is COPIED from the contributing corner with the largest t_k, the lowest k on a tie -- not
+ *             summed, which would multiply a voxel's votes by up to eight.
+ *   not read  the values and rows of a corner that does not contribute (stale after a deferred clear, possibly NaN), and
+ *             everything outside `src`.
+ *   it follows  (a) with T the identity, equal lattices and a whole-voxel offset every observed voxel has one corner with t = 1,
+ *             and the result is saf_volume_carry's into a zeroed destination, byte for byte; (b) a field that is linear in space
+ *             is reproduced at the destination centres within rounding wherever all eight corners are observed: a plane's TSDF
+ *             stays that plane's TSDF under any rotation and any voxel size (measured: at most 0.125 of the bound derived from
+ *             the operation count in tests/resample_reference.py); (c) holes are not smeared: unobserved corners drop
+ *             out and the rest are renormalised.  Trilinear interpolation low-passes the features by up to one source voxel
+ *             (known, documented, not corrected).
+ *   counts[]  device u64[4], ADDED to (may be NULL): [0] rows blended (observed, K >= 2), [1] rows copied (observed, K == 1),
+ *             [2] tsdf voxels blended, [3] tsdf voxels copied.  Integer atomics, one per wave and counter.
+ * SAF_E_INVALID (on the host, nothing is launched) for everything saf_volume_carry refuses -- a NULL src / dst or volume buffer,
+ * non-positive sizes or feat_dim, a grid of 2^31 voxels or more, feat_dim, feat_dtype or n_classes that differ, any destination
+ * buffer whose byte range intersects the source buffer of the same name --, for a feature or label buffer that is not aligned to
+ * its element type, for a NULL m12 or one with an entry that is not finite, and for a min_cover outside (0, 1].
+ * SAF_E_UNSUPPORTED if either accum_mode is SAF_SUM.
+ * One launch, coarsen's shape: a wave takes 64 consecutive voxels of the flattened destination (z fastest); each lane computes its
+ * voxel's p, corners, t_k and both sides' small fields; a ballot names the voxels with a row to write and the wave takes them one
+ * after the other: the footprint, the contributing corners and r are read from the owning lane, the loads of all contributing
+ * rows are issued before their arithmetic, 16 bytes per lane where the row pitch and both bases allow it, else 4 or 2.  No LDS, no
+ * scratch, no floating-point atomics.  Per call up to 64 N_dst bytes of counts are read (8 per corner) and 12 / 4 more per
+ * contributing corner, 28 N_dst bytes are written; per contributing corner of an observed voxel one feature row is read, per
+ * observed voxel one label row is read and one row (feature + label bytes) is written.  Measured (DESIGN.md section 4.22;
+ * 256^3 x 512 f32 into 256^3, 79 % touched): as a copy 11.1 ms, 1.12 x saf_volume_carry's time; rotated by 20 degrees 30.2 ms with
+ * 7.1 rows read per row written, 3.07 x carry; the same arithmetic as torch gathers: 792 ms.
+ */
+int saf_volume_resample(const saf_volume* src, const saf_volume* dst, const float* m12, float min_cover, uint64_t* counts,
+                        void* stream);
 
 /*
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for

@@ -19,6 +19,7 @@ __all__ = [
     "GridMove",
     "GridAbsorb",
     "GridCoarsen",
+    "GridResample",
     "label_components",
     "discover_objects",
     "evaluation",
@@ -39,7 +40,7 @@ __all__ = [
 
 def __getattr__(name):
     if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove", "GridAbsorb",
-                "GridCoarsen"):
+                "GridCoarsen", "GridResample"):
         from . import clipfusion as _m
 
         return getattr(_m, name)

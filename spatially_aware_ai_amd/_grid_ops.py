@@ -1,6 +1,6 @@
 """A fused volume taken to another box or lattice and kept fusing (not in the reference): ``move_grid``, ``absorb``
-(4.20) and ``coarsen`` (4.21) as a mixin of ``clipfusion._FusionVolumeMixin``, what they return, the host arithmetic of boxes and
-lattices, and the steps the three share, once each.  ``clipfusion`` re-exports these names; nothing here imports ``clipfusion``."""
+(4.20), ``coarsen`` (4.21) and ``resample`` (4.22) as a mixin of ``clipfusion._FusionVolumeMixin``, what they return, the host
+arithmetic of boxes and lattices, and the steps the four share, once each.  ``clipfusion`` re-exports these names; nothing here imports ``clipfusion``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -134,8 +134,33 @@ class GridCoarsen:
     tsdf_copied: torch.Tensor
 
 
+@dataclass
+class GridResample:
+    """What ``resample`` returns: the lattice and box (``origin``, ``voxel_size``, index offset, voxels per axis) before and after,
+    the ``transform`` (4 x 4 float64 ``new_from_old``), the ``matrix`` ([3, 4] float32: a new voxel's local index to a continuous
+    local index of the old box, what the pass was given) and ``min_cover``.  The four counters are 0-d int64 DEVICE tensors --
+    reading one synchronises: new voxels whose feature row (TSDF value) is the blend of two or more old voxels, and those that
+    are the copy of a single one."""
+
+    old_origin: object
+    old_voxel_size: float
+    old_index_offset: tuple
+    old_nvox: tuple
+    origin: object
+    voxel_size: float
+    index_offset: tuple
+    nvox: tuple
+    transform: np.ndarray
+    matrix: np.ndarray
+    min_cover: float
+    rows_blended: torch.Tensor
+    rows_copied: torch.Tensor
+    tsdf_blended: torch.Tensor
+    tsdf_copied: torch.Tensor
+
+
 class _GridOpsMixin:
-    """``move_grid``, ``absorb`` and ``coarsen`` of a fusion module, on ``_FusionVolumeMixin``'s buffers, queue and ``_c_volume``."""
+    """``move_grid``, ``absorb``, ``coarsen`` and ``resample`` of a fusion module, on ``_FusionVolumeMixin``'s buffers, queue and ``_c_volume``."""
 
     def _refuse_unfit(self, call, before, who="this", pair=False):
         """``SafError`` for a module built with ``x_planes``, holding only stripes, or poisoned.  ``pair``: one of two, named ``who``."""
@@ -371,6 +396,95 @@ class _GridOpsMixin:
                            origin=new_origin, voxel_size=new_vs, index_offset=new_off, nvox=new_nvox,
                            rows_blended=counts[0], rows_copied=counts[1], tsdf_blended=counts[2], tsdf_copied=counts[3])
 
+    def resample(self, origin=None, voxel_size=None, index_offset=None, nvox=None, transform=None, lattice_of=None, min_cover=0.5,
+                 multiple=4):
+        """Resample the volume IN PLACE onto any other lattice -- another ``origin``, any ``voxel_size`` (finer, or coarser by any
+        factor), and a rigid ``transform`` (4 x 4 ``new_from_old``: a world point x of the frame the volume was fused in is
+        ``transform @ x`` in the new one; default the identity) -- and keep fusing there: every new voxel looks up the eight old
+        voxels around its own centre and blends the observed ones by their trilinear weights, renormalised; a voxel whose
+        observed corners cover less than ``min_cover`` of the trilinear weight stays empty, so that no surface grows a fringe
+        (saf_volume_resample, include/saf.h).  ``lattice_of``: another fusion module, or a ``SceneResult``, whose
+        ``origin`` and ``voxel_size`` are taken (then neither may be given) -- afterwards ``lattice_of.absorb(self)`` is accepted,
+        the two-headset flow with ``transform`` from ``refine_pose``.  ``origin`` / ``voxel_size`` default to the module's own.
+        ``index_offset`` and ``nvox``, the new box on the new lattice, are given together or come from ``resample_box`` (the box
+        around the transformed old box, ``nvox`` rounded up to a multiple of ``multiple``).  ``trunc`` does not change: TSDF
+        values are in units of it, which is why a transform that scales is refused.
+
+        The stored counts are the MAXIMA over the contributing corners; a label histogram is copied from the heaviest corner.
+        Trilinear interpolation low-passes the features by up to one old voxel.  Frames fused before the call can no longer be
+        taken out with ``deintegrate``, as after ``coarsen``; poses handed to ``integrate()`` afterwards are the caller's, in the
+        NEW frame.  The module keeps its backbones, its queue and ``fuse_stats``; frames still queued behind ``integrate()`` are
+        fused first; a deferred clear stays owed.
+
+        BOTH volumes are resident during the call.  ``voxel_obj_idx`` and ``objects_segmentation_color`` describe a labelling of
+        the old grid and are deleted.  Returns a ``GridResample``; its counters are device tensors, nothing is read back here.
+        ``SafError``, with the volume unchanged, for a module built with ``x_planes``, one that holds only reduce-scattered
+        stripes, a poisoned one, a ``SAF_SUM`` volume, a transform that is not 4 x 4, finite and rigid, a non-positive
+        ``voxel_size``, a box that is not three positive sizes at three indices or holds 2^31 voxels or more, and a ``min_cover``
+        outside (0, 1]."""
+        self._refuse_unfit("resample", "before resampling it")
+        if self.accum_mode != _abi.SAF_RUNNING_MEAN:
+            raise SafError("resample: running means only: a SAF_SUM volume belongs to the multi-rank job, whose merge adds its sums")
+        if lattice_of is not None:
+            if origin is not None or voxel_size is not None:
+                raise SafError("resample: lattice_of gives the origin and the voxel size; pass neither of them with it")
+            base = getattr(lattice_of, "fusion", lattice_of)
+            if not isinstance(base, _GridOpsMixin):
+                raise SafError(f"resample: lattice_of must be a fusion module or a SceneResult, got {type(lattice_of).__name__}")
+            origin, voxel_size = base.origin, base.voxel_size
+        new_origin = self.origin if origin is None else origin
+        new_vs = self.voxel_size if voxel_size is None else voxel_size
+        t64 = _rigid_transform(transform)
+        o64 = _origin64(new_origin)
+        try:
+            vs_ok = not isinstance(new_vs, bool) and np.isfinite(float(new_vs)) and float(new_vs) > 0
+        except (TypeError, ValueError):
+            vs_ok = False
+        if not vs_ok:
+            raise SafError(f"resample: the voxel size must be a positive number, got {new_vs!r}")
+        try:
+            cover_ok = not isinstance(min_cover, bool) and 0.0 < float(min_cover) <= 1.0
+        except (TypeError, ValueError):
+            cover_ok = False
+        if not cover_ok:
+            raise SafError(f"resample: min_cover must lie in (0, 1], got {min_cover!r}")
+        if (index_offset is None) != (nvox is None):
+            raise SafError("resample: index_offset and nvox are given together, or neither")
+        if nvox is None:
+            new_off, new_nvox = resample_box(self, o64, new_vs, t64, multiple=multiple)
+        else:
+            try:
+                new_off, new_nvox = tuple(int(v) for v in index_offset), tuple(int(v) for v in nvox)
+            except (TypeError, ValueError):
+                new_off, new_nvox = (), ()
+            if len(new_off) != 3 or len(new_nvox) != 3 or min(new_nvox) <= 0:
+                raise SafError(f"resample: nvox must be three positive sizes and index_offset three indices, got {nvox!r} at {index_offset!r}")
+        n_new = new_nvox[0] * new_nvox[1] * new_nvox[2]
+        if n_new >= 1 << 31:
+            raise SafError(f"resample: a box of {n_new} voxels (2^31 or more)")
+        self._retire_session()
+        old = dict(self._buffers)
+        dev = old["tsdf"].device
+        old_off, old_nvox = self.index_offset, tuple(int(v) for v in self.nvox)
+        old_origin, old_vs = self.origin, self.voxel_size
+        m12 = resample_matrix(old_origin, old_vs, old_off, o64, new_vs, new_off, t64)
+        src = self._c_volume(for_fuse=True)  # (refuses a volume that is not on the device: no CPU fallback)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            new, ax, dst = self._new_box(new_origin, new_vs, new_off, new_nvox)
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+            # (the matrix is host memory, read during the call)
+            check(lib().saf_volume_resample(C.byref(src), C.byref(dst), _abi.ptr(m12), float(min_cover), _abi.ptr(counts),
+                                            stream.cuda_stream), "saf_volume_resample")
+            for t in old.values():
+                t.record_stream(stream)  # (the old buffers are let go below; the pass reads them on this stream)
+        self._install_box(new, ax, new_nvox, new_off, origin=new_origin, voxel_size=new_vs)
+        self._drop_labelling()
+        return GridResample(old_origin=old_origin, old_voxel_size=old_vs, old_index_offset=old_off, old_nvox=old_nvox,
+                            origin=new_origin, voxel_size=new_vs, index_offset=new_off, nvox=new_nvox, transform=t64, matrix=m12,
+                            min_cover=float(min_cover), rows_blended=counts[0], rows_copied=counts[1], tsdf_blended=counts[2],
+                            tsdf_copied=counts[3])
+
 
 def lattice_box(fusion, xyz, trunc_m=None, union=True, multiple=4):
     """The box of ``fusion``'s own lattice for the sparse cloud ``xyz`` -- what ``move_grid`` takes: (index_offset, nvox), tuples
@@ -414,3 +528,72 @@ def coarse_lattice(origin, voxel_size, index_offset, nvox, factor):
     else:
         new_origin = type(origin)(o64.tolist())
     return new_origin, f * voxel_size, new_off, new_n
+
+
+def _origin64(origin):
+    """A lattice's origin as three float64."""
+    o = torch.as_tensor(origin).detach().cpu().to(torch.float64).reshape(-1).numpy()
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise SafError(f"resample: the origin must be three finite coordinates, got {origin!r}")
+    return o
+
+
+def _rigid_transform(transform):
+    """``transform`` (None: the identity) as a 4 x 4 float64 array; ``SafError`` unless it is 4 x 4, finite and rigid: a last row of
+    0 0 0 1, max |R^T R - I| <= 1e-6 and det R > 0, decided in float64 (a scale would change what a TSDF value means: TSDF values
+    are in units of ``trunc``, which stays)."""
+    if transform is None:
+        return np.eye(4)
+    try:
+        t = transform.detach().cpu().to(torch.float64).numpy() if torch.is_tensor(transform) else np.asarray(transform, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SafError(f"resample: the transform must be a 4 x 4 matrix, got {type(transform).__name__}") from None
+    if t.shape != (4, 4) or not np.isfinite(t).all():
+        raise SafError(f"resample: the transform must be a finite 4 x 4 matrix (new_from_old), got shape {tuple(t.shape)}")
+    r = t[:3, :3]
+    if not np.array_equal(t[3], np.array([0.0, 0.0, 0.0, 1.0])) or float(np.abs(r.T @ r - np.eye(3)).max()) > 1e-6 or \
+            float(np.linalg.det(r)) <= 0:
+        raise SafError("resample: the transform is not rigid (last row 0 0 0 1, max |R^T R - I| <= 1e-6, det R > 0): scale, shear and "
+                       "reflections are refused")
+    return np.array(t, dtype=np.float64)
+
+
+def resample_matrix(src_origin, src_vs, src_off, dst_origin, dst_vs, dst_off, transform=None):
+    """The [3, 4] float32 matrix ``saf_volume_resample`` takes: a destination voxel's LOCAL index i (its own box, from 0) to the
+    continuous local index p of the source box.  From the centre ``world_new = (i + dst_off) * dst_vs + dst_origin``:
+    ``world_old = inv(transform) @ world_new`` (``transform``: 4 x 4 rigid ``new_from_old``; None: the identity) and
+    ``p = (world_old - src_origin) / src_vs - src_off`` -- composed in float64 and rounded ONCE to float32.  Host only."""
+    t = np.eye(4) if transform is None else (transform.detach().cpu().to(torch.float64).numpy() if torch.is_tensor(transform)
+                                             else np.asarray(transform, dtype=np.float64))
+    so, do = _origin64(src_origin), _origin64(dst_origin)
+    s_vs, d_vs = float(src_vs), float(dst_vs)
+    s_off, d_off = np.asarray([int(v) for v in src_off], dtype=np.float64), np.asarray([int(v) for v in dst_off], dtype=np.float64)
+    inv = np.linalg.inv(t)
+    m = np.empty((3, 4), dtype=np.float64)
+    m[:, :3] = inv[:3, :3] * (d_vs / s_vs)
+    # (the whole-voxel part apart from the origins' part: with the identity on one lattice the column is dst_off - src_off exactly,
+    #  every p is a whole number and the pass is a copy)
+    m[:, 3] = (m[:, :3] @ d_off + (inv[:3, :3] @ do + inv[:3, 3] - so) / s_vs) - s_off
+    return np.ascontiguousarray(m.astype(np.float32))
+
+
+def resample_box(fusion, origin, voxel_size, transform=None, multiple=4):
+    """The box of the lattice (``origin``, ``voxel_size``) around ``fusion``'s current box under ``transform`` (4 x 4 rigid
+    ``new_from_old``; None: the identity) -- what ``resample`` takes when no box is given: (index_offset, nvox), tuples of ints.
+    The eight corners of the current box (the centres of its corner voxels: beyond them there is nothing to interpolate) are
+    transformed and snapped OUTWARD to the lattice in float64 as ``lattice_box`` snaps -- the lattice index of a coordinate c is
+    (c - origin) / voxel_size; floor for the low corner, ceil for the high one --, and ``nvox`` is rounded up per axis, at the
+    high end, to a multiple of ``multiple`` (1: as snapped).  Offsets may be negative.  Host only."""
+    t = _rigid_transform(transform)
+    o_new, vs_new = _origin64(origin), float(voxel_size)
+    o_old, vs_old = _origin64(fusion.origin), float(fusion.voxel_size)
+    off = np.asarray(fusion.index_offset, dtype=np.float64)
+    n = np.asarray([int(v) for v in fusion.nvox], dtype=np.float64)
+    corners = np.array([[off[a] + (n[a] - 1) * ((k >> (2 - a)) & 1) for a in range(3)] for k in range(8)])
+    # (the whole-voxel part apart from the origins' part, as in resample_matrix: on the own lattice the box is the own box exactly)
+    idx = corners @ (t[:3, :3] * (vs_old / vs_new)).T + (t[:3, :3] @ o_old + t[:3, 3] - o_new) / vs_new
+    lo = np.floor(idx.min(axis=0)).astype(np.int64)
+    hi = np.ceil(idx.max(axis=0)).astype(np.int64)
+    m = max(int(multiple), 1)
+    size = (hi - lo + 1 + m - 1) // m * m
+    return tuple(int(v) for v in lo), tuple(int(v) for v in size)

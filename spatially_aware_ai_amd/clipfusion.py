@@ -11,7 +11,8 @@ Same names, arguments and error behaviour as the reference classes so that its c
   * ``lattice_box`` / ``move_grid`` -- not in the reference: a volume moved by whole voxels on its own lattice
   * ``absorb`` -- not in the reference: a second volume of the same lattice blended in by weights
   * ``coarsen`` / ``coarse_lattice`` -- not in the reference: a volume coarsened by a whole factor on its lattice (DESIGN 4.21);
-    these three live in ``_grid_ops.py``
+  * ``resample`` / ``resample_matrix`` / ``resample_box`` -- not in the reference: a volume resampled onto any other lattice under a
+    rigid transform; these four live in ``_grid_ops.py``
 
 PyTorch is plumbing here (device memory, streams, the backbone GEMMs); the fusion loop and the
 query scan are the hand-written HIP kernels behind ``include/saf.h``.  There is no CPU
@@ -30,8 +31,8 @@ import torch.nn.functional as F
 
 from . import _abi
 from ._frame_queue import FrameQueue, StagingRing
-from ._grid_ops import (_DT, GridAbsorb, GridCoarsen, GridMove, _axis_tables, _GridOpsMixin, _volume_struct,  # noqa: F401
-                        _xyz_world, coarse_lattice, lattice_box)
+from ._grid_ops import (_DT, GridAbsorb, GridCoarsen, GridMove, GridResample, _axis_tables, _GridOpsMixin,  # noqa: F401
+                        _volume_struct, _xyz_world, coarse_lattice, lattice_box, resample_box, resample_matrix)
 from ._lib import SafError, check, current_stream_ptr, lib, require_cuda
 
 _FRAME_WORDS = C.sizeof(_abi.SafFrame) // 8
@@ -52,7 +53,7 @@ _VOLUME_BUFFERS = frozenset(("tsdf", "rgb", "clip_feat", "weight", "tsdf_weight"
 
 
 class _FusionVolumeMixin(_GridOpsMixin):
-    """Buffers, workspace and the C-ABI call shared by both fusion modules (``move_grid``, ``absorb`` and ``coarsen``: _grid_ops.py)."""
+    """Buffers, workspace and the C-ABI call shared by both fusion modules (``move_grid``, ``absorb``, ``coarsen`` and ``resample``: _grid_ops.py)."""
 
     def _init_volume(self, origin, voxel_size, nvox, trunc, feat_dim, n_classes=0, keep_xyz_world=True,
                      feat_dtype=torch.float32, index_offset=(0, 0, 0), x_planes=None, device=None):

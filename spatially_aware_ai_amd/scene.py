@@ -9,7 +9,8 @@ what this module adds is the chain and a wall-clock split per stage, the counter
 performance statement ("within a few minutes after a user scans the environment", README.md:4).  ``extend_scene`` fuses a later
 scan version's new frames into the volume a reconstruction left (not in the reference, which fuses every version from its
 first frame); ``join_scenes`` puts two reconstructions of one lattice together (``reconstruct_scene(lattice_of=...)``,
-``fusion.absorb``); ``coarsen_scene`` takes a reconstruction to a whole multiple of its voxel size (``fusion.coarsen``).
+``fusion.absorb``); ``coarsen_scene`` takes a reconstruction to a whole multiple of its voxel size (``fusion.coarsen``), ``resample_scene`` to any other
+lattice under a rigid transform (``fusion.resample``).
 
 The Flask app, the datasets' decoders and the DGCNN in-situ learner stay the reference's.
 """
@@ -180,7 +181,7 @@ def _fuse_one_by_one(fusion, dataset, config, device, num_workers):
 def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, scan_version, out_dir, object_meshes,
                   marching_cubes, python_lists, prev=None, extra=None):
     """The stages behind the fusion loop (clip_seem_fusion.py:315-424, :563-607): labels, objects, the scene mesh, per-object
-    meshes, artefacts -- shared by ``reconstruct_scene``, ``extend_scene``, ``join_scenes`` and ``coarsen_scene`` (``extra``: entries
+    meshes, artefacts -- shared by ``reconstruct_scene``, ``extend_scene``, ``join_scenes``, ``coarsen_scene`` and ``resample_scene`` (``extra``: entries
     it adds to ``scene_knowledge``).  ``clk`` has just lapped the fusion.  ``prev``
     (``_describe_version`` of the previous version, or None): the discovered objects take the previous version's identities
     before anything is built from their indices."""
@@ -454,6 +455,42 @@ def coarsen_scene(result, factor, class_names, class_colors=None, out_dir=None, 
     grid = {"voxel_size": float(fusion.voxel_size), "nvox": [int(v) for v in fusion.nvox],
             "index_offset": [int(v) for v in fusion.index_offset]}
     res = _after_fusion(fusion, fusion.origin, fusion.nvox, result.xyz, clk, class_names, class_colors, version, out_dir, object_meshes,
+                        marching_cubes, python_lists, extra=grid)
+    res.seconds = clk.seconds
+    return res
+
+
+def resample_scene(result, class_names, class_colors=None, lattice_of=None, transform=None, voxel_size=None, origin=None,
+                   index_offset=None, nvox=None, min_cover=0.5, multiple=4, out_dir=None, object_meshes=True, marching_cubes=None,
+                   python_lists=False):
+    """A reconstruction on another lattice, in another frame: ``result.fusion.resample(...)`` -- every new voxel the trilinear blend
+    of the observed old voxels around its centre (saf_volume_resample), no frame goes through the backbones again --
+    and the stages behind the fusion run again on the new volume, which keeps fusing there (``extend_scene``, with poses in the
+    NEW frame).  ``lattice_of`` (a ``SceneResult`` or a fusion module), ``transform`` (4 x 4 rigid ``new_from_old``),
+    ``voxel_size``, ``origin``, ``index_offset`` / ``nvox``, ``min_cover`` and ``multiple`` are ``resample``'s.  Two headsets, or
+    two sessions, that scanned one room in two world frames: ``resample_scene(other, class_names, lattice_of=result, transform=T)``
+    with ``T`` from ``refine_pose``, then ``join_scenes(result, other, class_names)``.
+
+    Returns a new ``SceneResult`` around ``result.fusion`` -- ``result`` itself describes a volume the module no longer holds --;
+    ``origin`` and ``nvox`` are the new volume's, ``xyz`` is ``result``'s cloud taken through ``transform``,
+    ``scene_knowledge["scan_version"]`` counts on from ``result``'s, ``scene_knowledge`` gains ``voxel_size``, ``nvox`` and
+    ``index_offset`` of the new volume (and so does ``scene_knowledge.json``), ``seconds`` gains ``resample``.  Objects are
+    discovered anew from the new labels: an object keeps no identity across a resampling (the overlap of objects across two
+    lattices is not defined here)."""
+    clk = _Clock()
+    clk.start()
+    fusion = result.fusion
+    rec = fusion.resample(origin=origin, voxel_size=voxel_size, index_offset=index_offset, nvox=nvox, transform=transform,
+                          lattice_of=lattice_of, min_cover=min_cover, multiple=multiple)
+    clk.lap("resample")
+    xyz = result.xyz
+    if transform is not None and xyz is not None:
+        t = torch.as_tensor(rec.transform)
+        xyz = (xyz.to(torch.float64) @ t[:3, :3].T.to(xyz.device) + t[:3, 3].to(xyz.device)).to(xyz.dtype)
+    version = int(result.scene_knowledge.get("scan_version", 0)) + 1
+    grid = {"voxel_size": float(fusion.voxel_size), "nvox": [int(v) for v in fusion.nvox],
+            "index_offset": [int(v) for v in fusion.index_offset]}
+    res = _after_fusion(fusion, fusion.origin, fusion.nvox, xyz, clk, class_names, class_colors, version, out_dir, object_meshes,
                         marching_cubes, python_lists, extra=grid)
     res.seconds = clk.seconds
     return res
