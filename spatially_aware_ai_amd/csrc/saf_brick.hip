@@ -364,7 +364,7 @@ struct BrickPool {
 // pool.split == 0) or the bricks of the overflow list (pool.split == 3: a small second launch behind the walk of the pool's
 // segments).  The walk of the pool's segments (pool.split == 2) is compiled WITHOUT it: with the build code inlined the walk
 // kernel spilled 23-95 registers at its cap of 128.
-template <int CPL, bool SUM, bool BF16, bool BUILD, bool REBUILD = true>
+template <int CPL, RowKind K, bool BUILD, bool REBUILD = true>
 // (round 5: the walk instantiations that carry the build code -- the small launch over the overflow list, and SAF_BRICK_SPLIT=0 --
 //  may use the registers of two waves per SIMD instead of four: they spilled 6-96 VGPRs at the cap of 128.  Their workgroups are
 //  independent -- work is handed out by counters -- so fewer of them resident at once only lengthens those rare launches.)
@@ -373,6 +373,8 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
     unsigned long long* __restrict__ stats, unsigned int* __restrict__ ctr, const uint32_t* __restrict__ hitmask,
     uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc, const uint32_t* __restrict__ cmax,
     const float* __restrict__ cams, BrickPool pool) {
+  constexpr RowTraits RT = row_traits(K);
+  static_assert(!RT.half && !RT.undo, "the brick form takes f32 and bf16 rows, forwards (brick_form_applies)");
   using Lds = typename std::conditional<BUILD, BuildLds, BrickLds<CPL>>::type;
   constexpr int kNT = BUILD ? kBuildThreads : kBThreads;
   constexpr int kNHit = BUILD ? kBuildThreads : kHitThreads;  // threads that build hit records
@@ -467,7 +469,7 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
       //      the movers' row pieces, the walkers' two tap batches -- are never live together).
       if (wave >= kWalkers) {
         // A mover's 16-byte piece: PPR pieces per row slab, RPI rows per iteration, the movers take rows alternately.
-        constexpr int kEB = BF16 ? 2 : 4;                 // bytes per stored channel
+        constexpr int kEB = RT.esz;                       // bytes per stored channel
         constexpr int kPPR = kSlabCh * kEB / 16;          // pieces per row slab (4 .. 64)
         constexpr int kRPI = 64 / kPPR;                   // rows per iteration and mover (1 .. 16)
         constexpr int kMI = ((kBV + kMovers - 1) / kMovers + kRPI - 1) / kRPI;  // iterations
@@ -513,7 +515,7 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
               }
               float4* gp = feat + (int64_t)L.rows[cur].rown[mr] * row_vecs + (int64_t)p * kPPR + m_pc;
               float4 o;
-              if constexpr (BF16) {
+              if constexpr (RT.rows16) {
                 const uint32_t ox = __builtin_bit_cast(uint32_t, old[i].x), oy = __builtin_bit_cast(uint32_t, old[i].y);
                 const uint32_t oz = __builtin_bit_cast(uint32_t, old[i].z), ow = __builtin_bit_cast(uint32_t, old[i].w);
                 o.x = __builtin_bit_cast(float, pack_bf16(bf16_lo(ox) * b + sm[0], bf16_hi(ox) * b + sm[1]));
@@ -931,15 +933,15 @@ __global__ __launch_bounds__(BUILD ? kBuildThreads : kBThreads) __attribute__((a
             const int slot = (int)L.off[f] - base + rank_in_frame(&L.mf[f * 2], tid);
             const int wi = w_cur + r;
             const float a = 1.0f / (float)(wi + 1), b = (float)wi * a;
-            o0 = blend(stage[slot * 3], o0, a, b, SUM);
-            o1 = blend(stage[slot * 3 + 1], o1, a, b, SUM);
-            o2 = blend(stage[slot * 3 + 2], o2, a, b, SUM);
+            o0 = blend(stage[slot * 3], o0, a, b, RT.sum);
+            o1 = blend(stage[slot * 3 + 1], o1, a, b, RT.sum);
+            o2 = blend(stage[slot * 3 + 2], o2, a, b, RT.sum);
             ++r;
           }
         }
-        const float a = SUM ? 1.0f : 1.0f / (float)(w_cur + k_v);
+        const float a = RT.sum ? 1.0f : 1.0f / (float)(w_cur + k_v);
         L.rows[cur].rowA[row] = a;
-        L.rows[cur].rowB[row] = SUM ? 1.0f : (float)w_cur * a;
+        L.rows[cur].rowB[row] = RT.sum ? 1.0f : (float)w_cur * a;
         w_cur += k_v;
       }
       lds_barrier();
@@ -1099,10 +1101,18 @@ __global__ __launch_bounds__(128) void cam_table_kernel(const WinTable* __restri
 size_t cmax_words(int D) { return (size_t)D + (size_t)D / 64 + 1; }
 size_t cmax_bytes(int D) { return (cmax_words(D) * sizeof(uint32_t) + 255) & ~(size_t)255; }
 
-template <int CPL, bool REBUILD>
-BrickFn pick_brick(bool sum, bool bf16) {
-  if (bf16) return sum ? fuse_brick_kernel<CPL, true, true, false, REBUILD> : fuse_brick_kernel<CPL, false, true, false, REBUILD>;
-  return sum ? fuse_brick_kernel<CPL, true, false, false, REBUILD> : fuse_brick_kernel<CPL, false, false, false, REBUILD>;
+// The walk kernel of a slab width and a kind; the BUILD kernel (CPL = 1) depends on neither the rows' element type nor their width:
+// the f32 kind of the same accumulation rule serves.  nullptr: a volume the brick form does not take (brick_form_applies).
+template <int CPL, bool BUILD, bool REBUILD>
+BrickFn pick_brick(const KVol& kv) {
+  const std::optional<RowKind> kind = row_kind_of(kv, false);
+  if (!kind) return nullptr;
+  return dispatch_row_kind(*kind, [](auto k) -> BrickFn {
+    constexpr RowTraits RT = row_traits(decltype(k)::value);
+    if constexpr (RT.half || RT.undo) return nullptr;
+    else if constexpr (BUILD) return fuse_brick_kernel<CPL, RT.sum ? RowKind::SumF32 : RowKind::MeanF32, true>;
+    else return fuse_brick_kernel<CPL, decltype(k)::value, false, REBUILD>;
+  });
 }
 
 uint32_t brick_count(const KVol& kv) {
@@ -1189,9 +1199,8 @@ int launch_brick_build(const KVol& kv, const WinArgs& wa, const WinTable* tab, s
   if (hipMemsetAsync(pool.ctl, 0, sizeof(BrickCtl), s) != hipSuccess) return fail(SAF_E_HIP, "hipMemsetAsync(brick pool control)");
   hipLaunchKernelGGL(cam_table_kernel, dim3(1), dim3(128), 0, s, tab, wa.F, const_cast<float*>(cams));
   const uint32_t grid = 8u * build_wgs_per_xcd(kv);
-  const bool sum = kv.accum == SAF_SUM;
-  // (the build does not depend on the feature dtype or width: one instantiation per accumulation mode)
-  BrickFn fn = sum ? fuse_brick_kernel<1, true, false, true> : fuse_brick_kernel<1, false, false, true>;
+  BrickFn fn = pick_brick<1, true, true>(kv);
+  if (!fn) return fail(SAF_E_UNSUPPORTED, "brick form: no kernel for this volume");  // (fuse_route sends none here)
   hipLaunchKernelGGL(fn, dim3(grid), dim3(kBuildThreads), sizeof(BuildLds), s, kv, wa, tab, nullptr, (uint32_t)img_bytes, stats, nullptr,
                      hitmask, mask_plane, nullptr, nullptr, cams, pool);
   return check_launch("fuse_brick_kernel (build)");
@@ -1209,18 +1218,18 @@ int launch_fuse_bricks(const KVol& kv, const WinArgs& wa, const WinTable* tab, c
   hipLaunchKernelGGL(chan_max_kernel, dim3((kv.D + 255) / 256, (wa.F + 7) / 8), dim3(256), 0, s, map_imgs,
                      (int)(img_bytes / sizeof(float)), kv.D, wa.npy * wa.npx, wa.F, cmax);
   if (!split) hipLaunchKernelGGL(cam_table_kernel, dim3(1), dim3(128), 0, s, tab, wa.F, const_cast<float*>(cams));
-  const bool sum = kv.accum == SAF_SUM, bf16 = kv.e16 == kE16Bf16;
   // behind a build kernel: the walk of the pool's segments (no build code in it), then the overflow list, if any, by a small
   // launch of the instantiation that can build; without a build kernel that instantiation does everything
   BrickFn fn, fn_re;
   size_t lds;
   if (kv.D % 256 == 0) {
-    fn = pick_brick<4, false>(sum, bf16); fn_re = pick_brick<4, true>(sum, bf16); lds = sizeof(BrickLds<4>);
+    fn = pick_brick<4, false, false>(kv); fn_re = pick_brick<4, false, true>(kv); lds = sizeof(BrickLds<4>);
   } else if (kv.D % 128 == 0) {
-    fn = pick_brick<2, false>(sum, bf16); fn_re = pick_brick<2, true>(sum, bf16); lds = sizeof(BrickLds<2>);
+    fn = pick_brick<2, false, false>(kv); fn_re = pick_brick<2, false, true>(kv); lds = sizeof(BrickLds<2>);
   } else {
-    fn = pick_brick<1, false>(sum, bf16); fn_re = pick_brick<1, true>(sum, bf16); lds = sizeof(BrickLds<1>);
+    fn = pick_brick<1, false, false>(kv); fn_re = pick_brick<1, false, true>(kv); lds = sizeof(BrickLds<1>);
   }
+  if (!fn || !fn_re) return fail(SAF_E_UNSUPPORTED, "brick form: no kernel for this volume");  // (as the build)
   for (BrickFn f : {fn, fn_re}) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", lds, hipGetErrorString(e));

@@ -21,8 +21,9 @@
 // spirit and checked bit-for-bit against it (saf_common.h); the device building blocks shared with the
 // windowed path live in saf_fuse_dev.h.
 //
-// saf_unfuse_frames runs the same pipeline BACKWARDS (template flag UNDO on the three kernels): a fused frame is taken out of
-// the running means exactly where it went in -- same sets, same samples, the blend turned round.
+// saf_unfuse_frames runs the same pipeline BACKWARDS (UNDO on the sweep and the generic kernel, RowKind::UndoF32 on the row
+// kernel): a fused frame is taken out of the running means exactly where it went in -- same sets, same samples, the blend turned
+// round.
 #include <mutex>
 
 #include "saf_window_dev.h"
@@ -337,6 +338,10 @@ __device__ __forceinline__ unsigned long long sweep_blocks_done(const unsigned l
 // SAF_E_HIP instead of leaving a silently incomplete volume behind (stats[4] counts the workgroups as before).
 __device__ int* g_async_latch = nullptr;
 
+// Block until the sweep of this frame has published all its blocks (device-side dependency: no
+// event packet sits between consecutive fuse kernels on the caller's stream).  The sweep never
+// waits on anything and always fits beside a fuse workgroup, so this cannot deadlock; the spin is
+// bounded anyway (~2 s of the 100 MHz wall clock) and reports through stats[4].
 __device__ __forceinline__ bool wait_for_sweep(const unsigned long long* __restrict__ sweep_done,
                                                unsigned long long target, unsigned long long* __restrict__ stats) {
   __shared__ int s_ok;
@@ -564,13 +569,12 @@ __device__ __forceinline__ RowCtx fetch_row(int src, uint32_t n_l, float a_l, fl
 // counted waits: lanes whose chunk index would fall past the row re-do the last chunk (identical
 // value to the same address), and lane groups past the end of a batch re-do the batch's last
 // row inside the SAME wave instruction as its owner (same loads, same stores).
-// BF16: the feature volume holds bfloat16 (a 16-byte lane access = 8 channels = two map chunks);
-// samples are blended in fp32 exactly as for the fp32 volume and rounded to nearest-even once per
-// update.  F16 (with BF16): the 16-bit elements are IEEE half instead -- same layout, same fp32 blend, one nearest-even
-// conversion per update (h16_lo / h16_hi / pack_h16, saf_common.h).
-// UNDO (f32 running means only): the frame is taken out again.  A row's case travels in the broadcast `a`: -1 = guard (the
-// voxel's count is 0: nothing is stored), 0 = the count returns to 0 (exact zeros are stored), else 1 / new_weight.
-template <int CPL, int R, bool G64, bool LDS_MAP, bool SUM, bool BF16, bool F16 = false, bool UNDO = false>
+// K (RowKind, saf_fuse_dev.h; RT = its traits).  RT.rows16: the feature volume holds 16-bit elements (a 16-byte lane access =
+// 8 channels = two map chunks); samples are blended in fp32 exactly as for the fp32 volume and rounded to nearest-even once per
+// update -- to bfloat16, or with RT.half to IEEE half: same layout, same fp32 blend (h16_lo / h16_hi / pack_h16, saf_common.h).
+// RT.undo: the frame is taken out again.  A row's case travels in the broadcast `a`: -1 = guard (the voxel's count is 0: nothing
+// is stored), 0 = the count returns to 0 (exact zeros are stored), else 1 / new_weight.
+template <int CPL, int R, bool G64, bool LDS_MAP, RowKind K>
 __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame f,
                                                                   const unsigned long long* __restrict__ counts,
                                                                   const uint32_t* __restrict__ lists,
@@ -579,6 +583,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
                                                                   unsigned long long* __restrict__ stats,
                                                                   const unsigned long long* __restrict__ sweep_done,
                                                                   unsigned long long sweep_target) {
+  constexpr RowTraits RT = row_traits(K);
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   const int tid = threadIdx.x;
   const int DV = v.D >> 2;
@@ -595,15 +600,14 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
   if (!wait_for_sweep(sweep_done, sweep_target, stats)) return;  // lists + counters are published
   const Cam cam = load_cam(f.pose, f.K, f.W, f.H);
   const float half_px = (float)f.npx / 2.0f, half_py = (float)f.npy / 2.0f;
-  constexpr bool sum = SUM;
-  static_assert(!UNDO || (!SUM && !BF16), "frames are taken out of f32 running means only");
-  add_frame_stats<UNDO>(counts, stats);
+  constexpr bool sum = RT.sum;
+  add_frame_stats<RT.undo>(counts, stats);
 
   const int G = G64 ? 64 : (1 << g_log2);
   const int lane = tid & 63, wave = tid >> 6;
   const int slot = G64 ? 0 : (lane >> g_log2), gl = lane & (G - 1);
   const int epw = G64 ? 1 : (64 >> g_log2);  // rows per wave step
-  constexpr int KV = BF16 ? 2 : 1;  // map chunks (4 channels each) per 16-byte row unit
+  constexpr int KV = RT.rows16 ? 2 : 1;  // map chunks (4 channels each) per 16-byte row unit
   const int DU = DV / KV;           // 16-byte units per row
   int chs[CPL], mbs[CPL][KV];
 #pragma unroll
@@ -636,7 +640,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
       const Proj p = project(cam, v.ax[ix], v.ay[iy], v.az[iz]);
       const int w0 = v.weight[n_l];
       // a = 1 / new_weight ; b = weight * a                        clipfusion.py:716-717
-      if constexpr (UNDO)
+      if constexpr (RT.undo)
         a_l = w0 <= 0 ? -1.0f : (w0 > 1 ? 1.0f / (float)(w0 - 1) : 0.0f);
       else
         a_l = 1.0f / (float)(w0 + 1);
@@ -648,9 +652,9 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
       // tap cell, clamped to [-1, size] (everything outside is zero padding anyway)
       const int x0 = (int)fminf(fmaxf(xw, -1.0f), (float)f.npx), y0 = (int)fminf(fmaxf(yn, -1.0f), (float)f.npy);
       xy_l = (x0 + 1) | ((y0 + 1) << 16);
-      if (!UNDO || w0 > 0) fuse_scalars_lane<UNDO>(v, f, cam, n_l, p.gx, p.gy, w0, a_l, b_l, stats);
+      if (!RT.undo || w0 > 0) fuse_scalars_lane<RT.undo>(v, f, cam, n_l, p.gx, p.gy, w0, a_l, b_l, stats);
     }
-    if constexpr (UNDO) {  // the batch's guarded voxels, one atomic per wave
+    if constexpr (RT.undo) {  // the batch's guarded voxels, one atomic per wave
       const unsigned long long skipped = __ballot(a_l < 0.0f);
       if (stats && lane == 0 && skipped) atomicAdd(&stats[13], (unsigned long long)__popcll(skipped));
     }
@@ -666,23 +670,23 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rows_kernel(KVol v, KFrame 
 #define SAF_STORE(ctx_, old_)                                                                          \
   _Pragma("unroll") for (int c = 0; c < CPL; ++c) {                                                    \
     float4 out_;                                                                                       \
-    if (BF16) {                                                                                        \
+    if (RT.rows16) {                                                                                   \
       const uint32_t w0_ = __builtin_bit_cast(uint32_t, old_[c].x), w1_ = __builtin_bit_cast(uint32_t, old_[c].y); \
       const uint32_t w2_ = __builtin_bit_cast(uint32_t, old_[c].z), w3_ = __builtin_bit_cast(uint32_t, old_[c].w); \
-      const float4 n0_ = blend(SAF_TAPS(c, 0, ctx_), make_float4(h16_lo<F16>(w0_), h16_hi<F16>(w0_), h16_lo<F16>(w1_), h16_hi<F16>(w1_)), \
+      const float4 n0_ = blend(SAF_TAPS(c, 0, ctx_), make_float4(h16_lo<RT.half>(w0_), h16_hi<RT.half>(w0_), h16_lo<RT.half>(w1_), h16_hi<RT.half>(w1_)), \
                                (ctx_).a, (ctx_).b, sum);                                               \
-      const float4 n1_ = blend(SAF_TAPS(c, KV - 1, ctx_), make_float4(h16_lo<F16>(w2_), h16_hi<F16>(w2_), h16_lo<F16>(w3_), h16_hi<F16>(w3_)), \
+      const float4 n1_ = blend(SAF_TAPS(c, KV - 1, ctx_), make_float4(h16_lo<RT.half>(w2_), h16_hi<RT.half>(w2_), h16_lo<RT.half>(w3_), h16_hi<RT.half>(w3_)), \
                                (ctx_).a, (ctx_).b, sum);                                               \
-      out_.x = __builtin_bit_cast(float, pack_h16<F16>(n0_.x, n0_.y));                                     \
-      out_.y = __builtin_bit_cast(float, pack_h16<F16>(n0_.z, n0_.w));                                     \
-      out_.z = __builtin_bit_cast(float, pack_h16<F16>(n1_.x, n1_.y));                                     \
-      out_.w = __builtin_bit_cast(float, pack_h16<F16>(n1_.z, n1_.w));                                     \
-    } else if (UNDO) {                                                                                 \
+      out_.x = __builtin_bit_cast(float, pack_h16<RT.half>(n0_.x, n0_.y));                             \
+      out_.y = __builtin_bit_cast(float, pack_h16<RT.half>(n0_.z, n0_.w));                             \
+      out_.z = __builtin_bit_cast(float, pack_h16<RT.half>(n1_.x, n1_.y));                             \
+      out_.w = __builtin_bit_cast(float, pack_h16<RT.half>(n1_.z, n1_.w));                             \
+    } else if (RT.undo) {                                                                              \
       out_ = unblend(SAF_TAPS(c, 0, ctx_), old_[c], (ctx_).a, (ctx_).b);                               \
     } else {                                                                                           \
       out_ = blend(SAF_TAPS(c, 0, ctx_), old_[c], (ctx_).a, (ctx_).b, sum);                            \
     }                                                                                                  \
-    if (!UNDO || (ctx_).a >= 0.0f) st_stream(&feat[(int64_t)(ctx_).n * DU + chs[c]], out_);            \
+    if (!RT.undo || (ctx_).a >= 0.0f) st_stream(&feat[(int64_t)(ctx_).n * DU + chs[c]], out_);         \
   }
     int i0 = 0;
     if (steps >= R) {
@@ -731,29 +735,16 @@ FuseFn pick_lds(bool lds, bool undo) {
   return lds ? fuse_kernel<VEC, CPL, U, true> : fuse_kernel<VEC, CPL, U, false>;
 }
 
-template <int CPL, int R, bool SUM, bool BF16>
-FuseFn pick_rows3(bool g64, bool lds) {
-  if (g64)
-    return lds ? fuse_rows_kernel<CPL, R, true, true, SUM, BF16> : fuse_rows_kernel<CPL, R, true, false, SUM, BF16>;
-  return lds ? fuse_rows_kernel<CPL, R, false, true, SUM, BF16> : fuse_rows_kernel<CPL, R, false, false, SUM, BF16>;
-}
-template <int CPL, int R>
-FuseFn pick_rows_f16(bool g64, bool lds) {  // fp16 volumes: running mean only (make_kvol)
-  if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, false, true, true> : fuse_rows_kernel<CPL, R, true, false, false, true, true>;
-  return lds ? fuse_rows_kernel<CPL, R, false, true, false, true, true> : fuse_rows_kernel<CPL, R, false, false, false, true, true>;
-}
-template <int CPL, int R>
-FuseFn pick_rows_undo(bool g64, bool lds) {  // saf_unfuse_frames: f32 running means only
-  if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, false, false, false, true> : fuse_rows_kernel<CPL, R, true, false, false, false, false, true>;
-  return lds ? fuse_rows_kernel<CPL, R, false, true, false, false, false, true> : fuse_rows_kernel<CPL, R, false, false, false, false, false, true>;
-}
-// e16: the volume's 16-bit element type (KVol::e16); fp16 volumes have no SAF_SUM (make_kvol)
-template <int CPL, int R>
-FuseFn pick_rows(bool g64, bool lds, bool sum, int e16, bool undo = false) {
-  if (undo) return pick_rows_undo<CPL, R>(g64, lds);
-  if (e16 == kE16Half) return pick_rows_f16<CPL, R>(g64, lds);
-  if (e16) return sum ? pick_rows3<CPL, R, true, true>(g64, lds) : pick_rows3<CPL, R, false, true>(g64, lds);
-  return sum ? pick_rows3<CPL, R, true, false>(g64, lds) : pick_rows3<CPL, R, false, false>(g64, lds);
+// The row kernel of a width and a kind.  R, the rows in flight per lane group: 4 / 4 / 2 / 2 for 1 .. 4 chunks per lane, 8 for one
+// chunk of a 16-bit row.
+template <int CPL>
+FuseFn pick_rows(RowKind kind, bool g64, bool lds) {
+  return dispatch_row_kind(kind, [&](auto k) -> FuseFn {
+    constexpr RowKind K = decltype(k)::value;
+    constexpr int R = CPL == 1 ? (row_traits(K).rows16 ? 8 : 4) : (CPL == 2 ? 4 : 2);
+    if (g64) return lds ? fuse_rows_kernel<CPL, R, true, true, K> : fuse_rows_kernel<CPL, R, true, false, K>;
+    return lds ? fuse_rows_kernel<CPL, R, false, true, K> : fuse_rows_kernel<CPL, R, false, false, K>;
+  });
 }
 
 int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float* feat_map,
@@ -761,7 +752,9 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
                 const unsigned long long* sweep_done, unsigned long long sweep_target, bool shared_cus, const Knobs& kn,
                 hipStream_t s, bool undo = false) {
   const int D = kv.D, P = kf.npy * kf.npx;
-  const bool rows16 = kv.e16 != 0;  // 16-bit rows (bf16 or fp16): 8 channels per 16-byte unit
+  const std::optional<RowKind> kind = row_kind_of(kv, undo);
+  if (!kind) return fail(SAF_E_UNSUPPORTED, "per-frame pipeline: no row kernel for this volume");  // (the entry points refuse these)
+  const bool rows16 = row_traits(*kind).rows16;  // 8 channels per 16-byte unit
   const int VEC = (D % 4 == 0) ? 4 : 1;
   const int DV = D / VEC;
   const int units = rows16 ? D / 8 : DV;  // 16-byte row units (vector path)
@@ -770,24 +763,15 @@ int launch_fuse(const KVol& kv, const KFrame& kf, const WsLayout& w, const float
   const int G = 1 << g_log2;
   const int cpl = (units + G - 1) / G;
   const bool lds = w.lds_map;
-  const bool sum = kv.accum == SAF_SUM;
   FuseFn fn;
-  if (rows16) {
-    if (D % 8 != 0 || cpl > 4) return fail(SAF_E_UNSUPPORTED, "a bf16 / fp16 volume needs feat_dim %% 8 == 0 and <= 2048");
+  if (rows16 && (D % 8 != 0 || cpl > 4)) return fail(SAF_E_UNSUPPORTED, "a bf16 / fp16 volume needs feat_dim %% 8 == 0 and <= 2048");
+  if (rows16 || (VEC == 4 && cpl >= 1 && cpl <= 4)) {
     const bool g64 = G == 64;
     switch (cpl) {
-      case 1: fn = pick_rows<1, 8>(g64, lds, sum, kv.e16); break;
-      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kv.e16); break;
-      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kv.e16); break;
-      default: fn = pick_rows<4, 2>(g64, lds, sum, kv.e16); break;
-    }
-  } else if (VEC == 4 && cpl >= 1 && cpl <= 4) {
-    const bool g64 = G == 64;
-    switch (cpl) {
-      case 1: fn = pick_rows<1, 4>(g64, lds, sum, kE16None, undo); break;
-      case 2: fn = pick_rows<2, 4>(g64, lds, sum, kE16None, undo); break;
-      case 3: fn = pick_rows<3, 2>(g64, lds, sum, kE16None, undo); break;
-      default: fn = pick_rows<4, 2>(g64, lds, sum, kE16None, undo); break;
+      case 1: fn = pick_rows<1>(*kind, g64, lds); break;
+      case 2: fn = pick_rows<2>(*kind, g64, lds); break;
+      case 3: fn = pick_rows<3>(*kind, g64, lds); break;
+      default: fn = pick_rows<4>(*kind, g64, lds); break;
     }
   } else if (VEC == 4) {
     fn = pick_lds<4, 0, 1>(lds, undo);
@@ -824,7 +808,9 @@ int make_kvol(const saf_volume* vol, KVol* kv) {
     return fail(SAF_E_UNSUPPORTED, "a bf16 / fp16 volume needs feat_dim %% 8 == 0 and a 16-byte aligned buffer");
   if (vol->accum_mode != SAF_RUNNING_MEAN && vol->accum_mode != SAF_SUM)
     return fail(SAF_E_INVALID, "bad accum_mode %d", vol->accum_mode);
-  if (vol->feat_dtype == SAF_F16 && vol->accum_mode == SAF_SUM)
+  kv->accum = vol->accum_mode;
+  kv->e16 = vol->feat_dtype == SAF_BF16 ? kE16Bf16 : (vol->feat_dtype == SAF_F16 ? kE16Half : kE16None);
+  if (!row_kind_of(*kv, false))  // (the one dtype and mode without a forward kind)
     return fail(SAF_E_UNSUPPORTED, "SAF_SUM into an fp16 volume is not supported: sums over many frames leave fp16's range (65504) "
                                    "and saf_merge_finalize takes fp32 sums only -- accumulate in SAF_F32");
   if (!vol->axis_x || !vol->axis_y || !vol->axis_z || !vol->tsdf || !vol->tsdf_weight || !vol->weight || !vol->rgb ||
@@ -832,13 +818,10 @@ int make_kvol(const saf_volume* vol, KVol* kv) {
     return fail(SAF_E_INVALID, "volume has a NULL buffer");
   if (!(vol->trunc > 0.0f)) return fail(SAF_E_INVALID, "trunc must be positive");
   if (vol->feat_dim % 4 == 0 && ((uintptr_t)vol->clip_feat & 15)) return fail(SAF_E_INVALID, "clip_feat must be 16-byte aligned");
-  if (vol->n_classes < 0 || (vol->n_classes > 0 && !vol->labels_one_hot && false))
-    return fail(SAF_E_INVALID, "bad n_classes");
+  if (vol->n_classes < 0) return fail(SAF_E_INVALID, "bad n_classes");
   kv->nx = vol->nx; kv->ny = vol->ny; kv->nz = vol->nz;
   kv->D = vol->feat_dim;
   kv->n_classes = vol->labels_one_hot ? vol->n_classes : 0;
-  kv->accum = vol->accum_mode;
-  kv->e16 = vol->feat_dtype == SAF_BF16 ? kE16Bf16 : (vol->feat_dtype == SAF_F16 ? kE16Half : kE16None);
   kv->N = (uint32_t)N;
   kv->trunc = vol->trunc;
   kv->ax = vol->axis_x; kv->ay = vol->axis_y; kv->az = vol->axis_z;
@@ -857,12 +840,17 @@ struct FrameJob {
   const float* feat_map;
 };
 
+int check_ws_aligned(const void* workspace) {
+  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  return SAF_OK;
+}
+
 int make_job(const KVol& kv, const saf_frame* frame, void* workspace, size_t workspace_bytes, FrameJob* job) {
   int rc = make_kframe(frame, &job->kf);
   if (rc) return rc;
   job->feat_map = frame->feat_map;
   job->w = ws_layout(kv.N, kv.D, job->kf.npy * job->kf.npx);
-  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  if ((rc = check_ws_aligned(workspace))) return rc;
   if (workspace_bytes < job->w.total)
     return fail(SAF_E_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, job->w.total);
   return SAF_OK;
@@ -1021,6 +1009,25 @@ int latch_entry() {
     if (e_ != hipSuccess) { rc = fail(SAF_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); goto done; } \
   } while (0)
 
+// The windowed path of a call (forward: fuse_many; undo: saf_unfuse_frames_windowed), its classification on a pooled stream beside
+// its row kernels (a call of one window overlaps too: its first window is classified slab by slab beside its own row kernels).
+// SAF_WIN_OVERLAP=0, or no stream to be had: every kernel on the caller's stream (same-process A/Bs).
+int run_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* workspace, size_t workspace_bytes, uint64_t* stats,
+                 saf_profiler* prof, hipStream_t s, const Knobs& kn, const WinSlabs* slabs, bool recycled, bool undo) {
+  PipeRes* pr = kn.win_overlap ? pipe_acquire(kn) : nullptr;
+  if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, nullptr, kn, slabs, recycled, undo);
+  const WinOverlap ov = overlap_of(pr);
+  const int rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, &ov, kn, slabs, recycled, undo);
+  pipe_release(pr);
+  return rc;
+}
+
+// saf_unfuse_frames and _windowed: only the f32 running mean has a backward kind (row_kind_of); each entry says so in its own words.
+int unfuse_refusal(const KVol& kv, const char* not_f32, const char* not_mean) {
+  if (row_kind_of(kv, true)) return SAF_OK;
+  return fail(SAF_E_UNSUPPORTED, "%s", kv.e16 ? not_f32 : not_mean);
+}
+
 // Frames in order.  A single frame runs sweep -> fuse on the caller's stream.  For two or more
 // frames the sweeps (VALU-bound; they touch only the TSDF buffers and their own list buffer) are
 // queued back to back on an auxiliary stream and may run up to kListBuffers frames ahead, while the
@@ -1034,8 +1041,8 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
               uint64_t* stats, saf_profiler* prof, hipStream_t s, const Knobs& kn, const WinSlabs* slabs = nullptr, bool recycled = false,
               bool undo = false) {
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  int rc = SAF_OK;
-  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  int rc = check_ws_aligned(workspace);
+  if (rc) return rc;
   // undo (saf_unfuse_frames: no slabs, not recycled): always the per-frame pipeline below, its kernels run backwards
   const bool windowed = !undo && fuse_route(kv, frames, n_frames, workspace_bytes, kn).path != kPathPerFrame;
   if (recycled && !windowed) {
@@ -1051,16 +1058,7 @@ int fuse_many(const KVol& kv, const saf_frame* frames, int32_t n_frames, void* w
     }
     recycled = false;
   }
-  if (windowed) {
-    // SAF_WIN_OVERLAP=0: every kernel of the windowed path on the caller's stream (same-process A/Bs)
-    // (a call of one window overlaps too: its first window is classified slab by slab beside its own row kernels)
-    PipeRes* pr = kn.win_overlap ? pipe_acquire(kn) : nullptr;
-    if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, nullptr, kn, slabs, recycled);
-    const WinOverlap ov = overlap_of(pr);
-    rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, &ov, kn, slabs, recycled);
-    pipe_release(pr);
-    return rc;
-  }
+  if (windowed) return run_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, prof, s, kn, slabs, recycled, false);
   if (slabs && slabs->n > 0) {  // the per-frame pipeline, slab after slab (every (slab, frame) pair counts as a frame in stats[2])
     for (int k = 0; k < slabs->n; ++k) {
       if ((rc = check_slab(kv, *slabs, k))) return rc;
@@ -1203,11 +1201,10 @@ int saf_unfuse_frames(const saf_volume* vol, const saf_frame* frames, int32_t n_
   KVol kv;
   int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
   if (rc) return rc;
-  if (vol->feat_dtype != SAF_F32)
-    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames takes SAF_F32 volumes only: a stored bf16 / fp16 mean carries 2^-9 / 2^-12 "
-                                   "relative rounding, which taking a frame out multiplies by about the voxel's count");
-  if (vol->accum_mode != SAF_RUNNING_MEAN)
-    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames takes SAF_RUNNING_MEAN volumes only (sums belong to the multi-rank job)");
+  if ((rc = unfuse_refusal(kv, "saf_unfuse_frames takes SAF_F32 volumes only: a stored bf16 / fp16 mean carries 2^-9 / 2^-12 "
+                               "relative rounding, which taking a frame out multiplies by about the voxel's count",
+                           "saf_unfuse_frames takes SAF_RUNNING_MEAN volumes only (sums belong to the multi-rank job)")))
+    return rc;
   if (n_frames == 0) return SAF_OK;
   if ((rc = latch_entry())) return rc;
   return fuse_many(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, static_cast<hipStream_t>(stream), read_knobs(),
@@ -1225,23 +1222,15 @@ int saf_unfuse_frames_windowed(const saf_volume* vol, const saf_frame* frames, i
   KVol kv;
   int rc = fuse_entry(vol, frames, n_frames, 0, &kv);
   if (rc) return rc;
-  if (vol->feat_dtype != SAF_F32)
-    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames_windowed takes SAF_F32 volumes only (as saf_unfuse_frames)");
-  if (vol->accum_mode != SAF_RUNNING_MEAN)
-    return fail(SAF_E_UNSUPPORTED, "saf_unfuse_frames_windowed takes SAF_RUNNING_MEAN volumes only (as saf_unfuse_frames)");
+  if ((rc = unfuse_refusal(kv, "saf_unfuse_frames_windowed takes SAF_F32 volumes only (as saf_unfuse_frames)",
+                           "saf_unfuse_frames_windowed takes SAF_RUNNING_MEAN volumes only (as saf_unfuse_frames)")))
+    return rc;
   const Knobs kn = read_knobs();
   if (n_frames == 0 || !unfuse_windowed(kv, frames, n_frames, workspace_bytes, kn))
     return fail(SAF_E_UNSUPPORTED, "the windowed removal does not take this call (saf_unfuse_path): saf_unfuse_frames does");
-  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  if ((rc = check_ws_aligned(workspace))) return rc;
   if ((rc = latch_entry())) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // SAF_WIN_OVERLAP=0: every kernel on the caller's stream, as forward (fuse_many)
-  PipeRes* pr = kn.win_overlap ? pipe_acquire(kn) : nullptr;
-  if (!pr) return fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, s, nullptr, kn, nullptr, false, true);
-  const WinOverlap ov = overlap_of(pr);
-  rc = fuse_many_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, s, &ov, kn, nullptr, false, true);
-  pipe_release(pr);
-  return rc;
+  return run_windowed(kv, frames, n_frames, workspace, workspace_bytes, stats, nullptr, static_cast<hipStream_t>(stream), kn, nullptr, false, true);
 }
 
 int saf_unfuse_frame(const saf_volume* vol, const saf_frame* frame, void* workspace, size_t workspace_bytes,
@@ -1282,7 +1271,7 @@ int saf_fuse_session_push(saf_fuse_session* ss, const saf_volume* vol, const saf
   KVol kv;
   int rc = fuse_entry(vol, frames, n_frames, 1, &kv);
   if (rc) return rc;
-  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  if ((rc = check_ws_aligned(workspace))) return rc;
   const Knobs kn = read_knobs();
   if (!fuse_route(kv, frames, n_frames, workspace_bytes, kn).session)
     return fail(SAF_E_UNSUPPORTED, "a streaming session takes what the windowed row forms take on two streams, in windows of %d frames (saf_fuse_session_ok)", SAF_WINDOW_FRAMES);
@@ -1302,7 +1291,7 @@ int saf_fuse_session_prepare(saf_fuse_session* ss, const saf_volume* vol, const 
   KVol kv;
   int rc = fuse_entry(vol, frames, n_frames, 1, &kv);
   if (rc) return rc;
-  if (!workspace || ((uintptr_t)workspace & 255)) return fail(SAF_E_INVALID, "workspace must be 256-byte aligned");
+  if ((rc = check_ws_aligned(workspace))) return rc;
   const Knobs kn = read_knobs();
   if (!fuse_route(kv, frames, n_frames, workspace_bytes, kn).session)
     return fail(SAF_E_UNSUPPORTED, "saf_fuse_session_prepare: not a shape or a setting a session takes (saf_fuse_session_ok)");

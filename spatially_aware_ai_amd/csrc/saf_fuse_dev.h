@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <optional>
+
 #include "saf_common.h"
 #include "saf_host.h"
 
@@ -42,6 +44,43 @@ struct KVol {
   int* labels;
   FastDiv div_nz, div_ny;
 };
+
+// The row kernels' one compile-time choice -- the rows' element type x the accumulation rule x the direction --, with exactly the
+// kinds that are built.  A seventh is added HERE: an enumerator, its answers in row_traits, its volumes in row_kind_of, its case
+// in dispatch_row_kind; the kernels and pickers below then see it.
+enum class RowKind { MeanF32, SumF32, MeanBf16, SumBf16, MeanF16, UndoF32 };
+struct RowTraits {
+  bool sum;     // sums (SAF_SUM), not running means
+  bool rows16;  // 16-bit rows: a 16-byte unit holds 8 channels ...
+  bool half;    // ... of IEEE half, not bfloat16
+  bool undo;    // the kernel runs backwards: the frames leave the rows
+  int esz;      // bytes per stored channel
+};
+constexpr RowTraits row_traits(RowKind k) {
+  const bool rows16 = k == RowKind::MeanBf16 || k == RowKind::SumBf16 || k == RowKind::MeanF16;
+  return {k == RowKind::SumF32 || k == RowKind::SumBf16, rows16, k == RowKind::MeanF16, k == RowKind::UndoF32, rows16 ? 2 : 4};
+}
+// The kind of a volume's rows in a direction, or none: fp16 rows hold no sums, and only the f32 running mean is built backwards.
+// The ONE mapping of (e16, accum, undo) to kernels: every picker and every refusal of a combination asks it.
+inline std::optional<RowKind> row_kind_of(const KVol& kv, bool undo) {
+  const bool sum = kv.accum == SAF_SUM;
+  if (undo) return (kv.e16 || sum) ? std::nullopt : std::optional<RowKind>(RowKind::UndoF32);
+  if (kv.e16 == kE16Half) return sum ? std::nullopt : std::optional<RowKind>(RowKind::MeanF16);
+  if (kv.e16) return sum ? RowKind::SumBf16 : RowKind::MeanBf16;
+  return sum ? RowKind::SumF32 : RowKind::MeanF32;
+}
+// One template argument from a run-time kind, as dispatch_dtype (saf_host.h): f(std::integral_constant<RowKind, K>{}).
+template <typename F>
+auto dispatch_row_kind(RowKind k, F&& f) {
+  switch (k) {
+    case RowKind::SumF32: return f(std::integral_constant<RowKind, RowKind::SumF32>{});
+    case RowKind::MeanBf16: return f(std::integral_constant<RowKind, RowKind::MeanBf16>{});
+    case RowKind::SumBf16: return f(std::integral_constant<RowKind, RowKind::SumBf16>{});
+    case RowKind::MeanF16: return f(std::integral_constant<RowKind, RowKind::MeanF16>{});
+    case RowKind::UndoF32: return f(std::integral_constant<RowKind, RowKind::UndoF32>{});
+    default: return f(std::integral_constant<RowKind, RowKind::MeanF32>{});
+  }
+}
 
 struct KFrame {
   int H, W, npy, npx, rgb_bilinear;
@@ -189,10 +228,6 @@ __device__ __forceinline__ void fuse_scalars(const KVol& v, const KFrame& f, con
   }
 }
 
-// Block until the sweep of this frame has published all its blocks (device-side dependency: no
-// event packet sits between consecutive fuse kernels on the caller's stream).  The sweep never
-// waits on anything and always fits beside a fuse workgroup, so this cannot deadlock; the spin is
-// bounded anyway (~2 s of the 100 MHz wall clock) and reports through stats[4].
 // rgb / weight / label side of one valid voxel handled entirely by ONE lane (the lane-parallel
 // part of fuse_rows_kernel): the three channel loads are issued together, then blended and stored.
 // The frame's rgb sample for one valid voxel (nearest in ClipFusion, bilinear in ClipSeemFusion); returns the

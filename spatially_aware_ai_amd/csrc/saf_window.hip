@@ -4,7 +4,7 @@
 // form (a row's samples summed in registers, one blend per row: section 4.6c; the default) or its frame-ordered form
 // (SAF_WIN_FORM=rows: bit-identical to the per-frame pipeline of saf_fuse.hip).  Selected by saf_fuse_frames for calls of 16
 // or more frames of one shape.  The host side schedules a call as a list of (sub-volume, window) units.
-// saf_unfuse_frames_windowed runs the same schedule BACKWARDS (template flag UNDO on the classification and on the order-free row
+// saf_unfuse_frames_windowed runs the same schedule BACKWARDS (UNDO on the classification, RowKind::UndoF32 on the order-free row
 // kernel of f32 running means): the frames of a window leave the volume with one read and one write per touched row.
 #include <chrono>
 #include <vector>
@@ -181,9 +181,9 @@ constexpr int kUnitVox = kPiece >> SAF_WIN_SPLIT_LOG2;  // voxels of a unit of w
                                // SIMD room for TWO classification waves of 80, with six (184 each) for one; config 3's job 66.0 -> 65.2 ms, the f32 kernel
                                // (168 registers with six rows) loses with five: 75.1 -> 75.8 (profiles/r06/config3_rgbl_ab.txt)
 #endif
-template <int CPL, bool OF = false, bool BF16 = false>
+template <int CPL, bool OF = false, bool ROWS16 = false>  // ROWS16: RowTraits::rows16 of the kernel's kind
 struct WinCfg {
-  static constexpr int SR = OF ? (CPL == 1 ? 8 : (CPL == 2 ? (BF16 ? SAF_WIN_OF_SR2_BF16 : SAF_WIN_OF_SR2) : (CPL == 3 ? 3 : 2)))
+  static constexpr int SR = OF ? (CPL == 1 ? 8 : (CPL == 2 ? (ROWS16 ? SAF_WIN_OF_SR2_BF16 : SAF_WIN_OF_SR2) : (CPL == 3 ? 3 : 2)))
                                : (CPL == 1 ? 8 : (CPL == 2 ? SAF_WIN_SR2 : 3));  // rows of a sub-chunk (LDS resident / register sums)
   static constexpr int P = OF ? (CPL == 1 ? 4 : (CPL == 2 ? SAF_WIN_OF_P2 : 1))
                               : (CPL == 1 ? 6 : (CPL == 2 ? SAF_WIN_P2 : 2));  // tap groups in flight
@@ -729,9 +729,9 @@ __device__ __forceinline__ float4 win_tap_load(__amdgpu_buffer_rsrc_t maps, uint
 }
 // Channel chunk c of a lane (a float4 of the D-channel map row).  f32 volume: lane + 64 c.  bf16 volume:
 // a lane's 16-byte row unit holds 8 channels = chunks 2 (lane + 64 (c / 2)) + c % 2.
-template <bool BF16>
+template <bool ROWS16>
 __device__ __forceinline__ constexpr int win_chunk_off(int c) {
-  return BF16 ? (c >> 1) * 128 + (c & 1) : c * 64;
+  return ROWS16 ? (c >> 1) * 128 + (c & 1) : c * 64;
 }
 // bf16 volume: the rows of a sub-chunk travel through registers (16 bytes = 8 channels per lane and unit)
 // and are widened into the f32 LDS rows once they have landed.
@@ -766,9 +766,10 @@ __device__ __forceinline__ WinGroupOffs win_group_offsets(const WinCtx<CPL>& cx,
 // NB groups (runs of lanes hl[u] .. hl[u + 1] - 1 of hits in group order): request the four map rows of every group, then
 // blend group after group into the LDS rows (the waits are counted: group u is processed while the rows of groups
 // u+1.. are still in flight).
-template <int NB, int CPL, bool SUM, bool BF16, int SR, bool F16>
+template <int NB, int CPL, RowKind K, int SR>
 __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)[NB + 1], bool first, const WinGroupOffs& go,
-                                          const WinHit& rec, const WinRaw<SR, BF16 ? CPL / 2 : 1>& raw) {
+                                          const WinHit& rec, const WinRaw<SR, row_traits(K).rows16 ? CPL / 2 : 1>& raw) {
+  constexpr RowTraits RT = row_traits(K);
   float4 tp[NB][4][CPL];
 #pragma unroll
   for (int u = 0; u < NB; ++u) {
@@ -777,10 +778,10 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
     // per-group address arithmetic off the scalar unit)
     const int o_nw = __builtin_amdgcn_readlane(go.nw, hl[u]), o_ne = __builtin_amdgcn_readlane(go.ne, hl[u]);
     const int o_sw = __builtin_amdgcn_readlane(go.sw, hl[u]), o_se = __builtin_amdgcn_readlane(go.se, hl[u]);
-    const uint32_t lane_off = (uint32_t)(BF16 ? 2 * cx.lane : cx.lane) * 16u;
+    const uint32_t lane_off = (uint32_t)(RT.rows16 ? 2 * cx.lane : cx.lane) * 16u;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-      const uint32_t off = lane_off + (uint32_t)win_chunk_off<BF16>(c) * 16u;
+      const uint32_t off = lane_off + (uint32_t)win_chunk_off<RT.rows16>(c) * 16u;
       tp[u][0][c] = win_tap_load(cx.maps, (uint32_t)o_nw + off);
       tp[u][1][c] = win_tap_load(cx.maps, (uint32_t)o_ne + off);
       tp[u][2][c] = win_tap_load(cx.maps, (uint32_t)o_sw + off);
@@ -791,7 +792,7 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
     // the BUILTIN, not inline asm: the compiler's wait-count pass must see that the LDS-DMA has been
     // waited for, or it drains vmcnt before every later LDS read (each row's store waited for the last)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt untouched
-    if (BF16) {
+    if (RT.rows16) {
       constexpr int UPL = CPL / 2;
 #pragma unroll
       for (int r = 0; r < SR; ++r) {
@@ -799,8 +800,8 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
 #pragma unroll
           for (int k = 0; k < UPL; ++k) {
             const uint4 w = raw.u[r * UPL + k];
-            cx.rows[(r * CPL + 2 * k) * 64 + cx.lane] = make_float4(h16_lo<F16>(w.x), h16_hi<F16>(w.x), h16_lo<F16>(w.y), h16_hi<F16>(w.y));
-            cx.rows[(r * CPL + 2 * k + 1) * 64 + cx.lane] = make_float4(h16_lo<F16>(w.z), h16_hi<F16>(w.z), h16_lo<F16>(w.w), h16_hi<F16>(w.w));
+            cx.rows[(r * CPL + 2 * k) * 64 + cx.lane] = make_float4(h16_lo<RT.half>(w.x), h16_hi<RT.half>(w.x), h16_lo<RT.half>(w.y), h16_hi<RT.half>(w.y));
+            cx.rows[(r * CPL + 2 * k + 1) * 64 + cx.lane] = make_float4(h16_lo<RT.half>(w.z), h16_hi<RT.half>(w.z), h16_lo<RT.half>(w.w), h16_hi<RT.half>(w.w));
           }
         }
       }
@@ -823,10 +824,10 @@ __device__ __forceinline__ void win_batch(const WinCtx<CPL>& cx, const int (&hl)
       for (int c = 0; c < CPL; ++c) {
         float4* rp = cx.rows + (r * CPL + c) * 64 + cx.lane;
         const float4 sv = lerp_taps(tp[u][0][c], tp[u][1][c], tp[u][2][c], tp[u][3][c], w);
-        float4 nv = blend(sv, *rp, a, b, SUM);
-        if (BF16) {  // the per-frame path stores bf16 (fp16) after every hit: round to nearest even, keep as f32
-          const uint32_t p01 = pack_h16<F16>(nv.x, nv.y), p23 = pack_h16<F16>(nv.z, nv.w);  // two hardware conversions
-          nv.x = h16_lo<F16>(p01); nv.y = h16_hi<F16>(p01); nv.z = h16_lo<F16>(p23); nv.w = h16_hi<F16>(p23);
+        float4 nv = blend(sv, *rp, a, b, RT.sum);
+        if (RT.rows16) {  // the per-frame path stores bf16 (fp16) after every hit: round to nearest even, keep as f32
+          const uint32_t p01 = pack_h16<RT.half>(nv.x, nv.y), p23 = pack_h16<RT.half>(nv.z, nv.w);  // two hardware conversions
+          nv.x = h16_lo<RT.half>(p01); nv.y = h16_hi<RT.half>(p01); nv.z = h16_lo<RT.half>(p23); nv.w = h16_hi<RT.half>(p23);
         }
         *rp = nv;
       }
@@ -861,11 +862,12 @@ __device__ __forceinline__ void of_add_row(win_v2f (&a)[2 * CPL], const float4 (
 // So the loops are turned inside out: for every group u and every row R of the sub-chunk (both unrolled), the lanes
 // rm[R] & [hl[u], hl[u + 1]) are that row's hits of that group -- usually none or one -- and each body adds into acc[R]
 // from tp[u] in place.  Within a row the hits stay in (frame, lane) order: the sum is reproducible.
-template <int NB, int CPL, bool SUM, bool BF16, int SR, bool F16>
+template <int NB, int CPL, RowKind K, int SR>
 __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&hl)[NB + 1], int nb, const WinGroupOffs& go,
                                              const WinHit& rec, const unsigned long long (&rm)[SR],
                                              win_v2f (&acc)[SR][2 * CPL]) {
-  if constexpr (BF16) {  // bf16 map images: one 16-byte load per tap and unit of 8 channels, widened in the FMA operands
+  constexpr RowTraits RT = row_traits(K);
+  if constexpr (RT.rows16) {  // bf16 map images: one 16-byte load per tap and unit of 8 channels, widened in the FMA operands
     constexpr int UPL = CPL / 2;
     uint4 tq[NB][4][UPL];
 #pragma unroll
@@ -902,10 +904,10 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
             for (int t = 0; t < 4; ++t) {
               const uint4 w = tq[u][t][k];
               const win_v2f ww = {wt[t], wt[t]};
-              acc[R][4 * k + 0] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.x), h16_hi<F16>(w.x)}, ww, acc[R][4 * k + 0]);
-              acc[R][4 * k + 1] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.y), h16_hi<F16>(w.y)}, ww, acc[R][4 * k + 1]);
-              acc[R][4 * k + 2] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.z), h16_hi<F16>(w.z)}, ww, acc[R][4 * k + 2]);
-              acc[R][4 * k + 3] = __builtin_elementwise_fma((win_v2f){h16_lo<F16>(w.w), h16_hi<F16>(w.w)}, ww, acc[R][4 * k + 3]);
+              acc[R][4 * k + 0] = __builtin_elementwise_fma((win_v2f){h16_lo<RT.half>(w.x), h16_hi<RT.half>(w.x)}, ww, acc[R][4 * k + 0]);
+              acc[R][4 * k + 1] = __builtin_elementwise_fma((win_v2f){h16_lo<RT.half>(w.y), h16_hi<RT.half>(w.y)}, ww, acc[R][4 * k + 1]);
+              acc[R][4 * k + 2] = __builtin_elementwise_fma((win_v2f){h16_lo<RT.half>(w.z), h16_hi<RT.half>(w.z)}, ww, acc[R][4 * k + 2]);
+              acc[R][4 * k + 3] = __builtin_elementwise_fma((win_v2f){h16_lo<RT.half>(w.w), h16_hi<RT.half>(w.w)}, ww, acc[R][4 * k + 3]);
             }
           }
         }
@@ -923,10 +925,10 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
     const int o_ne = real ? __builtin_amdgcn_readlane(go.ne, hu) : (int)(kTapOutside + 0x10000u * (4 * u + 1));
     const int o_sw = real ? __builtin_amdgcn_readlane(go.sw, hu) : (int)(kTapOutside + 0x10000u * (4 * u + 2));
     const int o_se = real ? __builtin_amdgcn_readlane(go.se, hu) : (int)(kTapOutside + 0x10000u * (4 * u + 3));
-    const uint32_t lane_off = (uint32_t)(BF16 ? 2 * cx.lane : cx.lane) * 16u;
+    const uint32_t lane_off = (uint32_t)(RT.rows16 ? 2 * cx.lane : cx.lane) * 16u;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-      const uint32_t off = lane_off + (uint32_t)win_chunk_off<BF16>(c) * 16u;
+      const uint32_t off = lane_off + (uint32_t)win_chunk_off<RT.rows16>(c) * 16u;
       tp[u][0][c] = win_tap_load(cx.maps, (uint32_t)o_nw + off);
       tp[u][1][c] = win_tap_load(cx.maps, (uint32_t)o_ne + off);
       tp[u][2][c] = win_tap_load(cx.maps, (uint32_t)o_sw + off);
@@ -956,25 +958,26 @@ __device__ __forceinline__ void win_batch_of(const WinCtx<CPL>& cx, const int (&
 
 
 
-// BF16: 16-bit rows (8 channels per 16 bytes); F16 (with BF16): their elements are IEEE half instead of bfloat16 -- the same
-// layout, loads, stores and fp32 arithmetic, another widening and another (nearest-even) narrowing (h16_lo / h16_hi / pack_h16).
-// UNDO (window_unfuse_kernel; the order-free f32 running mean only): the window's hits LEAVE the rows.  Per touched voxel of weight
+// K (RowKind, saf_fuse_dev.h; RT = its traits).  RT.rows16: 16-bit rows (8 channels per 16 bytes), of bfloat16 or, with RT.half, of
+// IEEE half -- the same layout, loads, stores and fp32 arithmetic, another widening and another (nearest-even) narrowing (h16_lo /
+// h16_hi / pack_h16).  RT.undo (window_unfuse_kernel; the order-free form only): the window's hits LEAVE the rows.  Per touched voxel of weight
 // w0 with k hits, k_eff = min(k, w0) of them, the first in frame order, are removed -- rgb hit by hit with unblend, labels minus one
 // per removed hit, weight w0 - k_eff -- and the other k - k_eff are the guard's skips (stats[13]).  Feature row: untouched where
 // w0 == 0, an exact zero row where k >= w0, else old + sum of samples x (-1 / w0), leaving as acc x (w0 x (1 / (w0 - k))).
-template <int CPL, bool SUM, bool BF16, bool OF, bool F16 = false, bool UNDO = false>
+template <int CPL, RowKind K, bool OF>
 __device__ __forceinline__ void
 fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
                  unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
                  const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
                  int xcd_order) {
-  using Cfg = WinCfg<CPL, OF, BF16>;
+  constexpr RowTraits RT = row_traits(K);
+  using Cfg = WinCfg<CPL, OF, RT.rows16>;
   constexpr int SR = Cfg::SR;
-  static_assert(!UNDO || (OF && !SUM && !BF16), "frames leave f32 running means through the order-free form only");
+  static_assert(!RT.undo || OF, "frames leave the rows through the order-free form only");
   // (s_setprio 1 / 3 here, ahead of the classification waves that share the SIMDs, changes nothing: 105.4 / 105.7 / 105.8 ms)
   // a bf16 sub-chunk also holds its raw rows in registers until they are widened: one tap group fewer in flight
   constexpr int P = OF ? Cfg::P
-                       : (BF16 && Cfg::P > 2 ? Cfg::P - 1 : (BF16 && CPL == 4 ? 1 : Cfg::P));  // (bf16, D = 1024: two groups of 64 tap registers in flight spilled)
+                       : (RT.rows16 && Cfg::P > 2 ? Cfg::P - 1 : (RT.rows16 && CPL == 4 ? 1 : Cfg::P));  // (bf16, D = 1024: two groups of 64 tap registers in flight spilled)
   extern __shared__ __align__(16) unsigned char s_dyn[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float4* rows = reinterpret_cast<float4*>(s_dyn + Cfg::rows_off) + (size_t)wave * SR * CPL * 64;
@@ -997,7 +1000,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
       a += __shfl_xor(a, o);
       b += __shfl_xor(b, o);
     }
-    if constexpr (UNDO) {  // the backward classification's skipped tsdf-valid voxels; no other counter moves
+    if constexpr (RT.undo) {  // the backward classification's skipped tsdf-valid voxels; no other counter moves
       if (tid == 0 && a) atomicAdd(&stats[14], a);
     } else {
     if (tid == 0) {
@@ -1015,13 +1018,13 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
   }
   __syncthreads();
   const int DV = v.D >> 2;
-  const int DVM = (BF16 && OF) ? v.D >> 3 : v.D >> 2;  // 16-byte vectors of a MAP row (bf16 map images in the order-free form of a bf16 volume)
+  const int DVM = (RT.rows16 && OF) ? v.D >> 3 : v.D >> 2;  // 16-byte vectors of a MAP row (bf16 map images in the order-free form of a bf16 volume)
   const float half_px = (float)wa.npx / 2.0f, half_py = (float)wa.npy / 2.0f;
   const int zero_row = wa.npx * wa.npy;
   int chs[CPL];
 #pragma unroll
   for (int c = 0; c < CPL; ++c) chs[c] = lane + c * 64;
-  constexpr int UPL = BF16 ? CPL / 2 : 1;  // 16-byte units of a bf16 row per lane
+  constexpr int UPL = RT.rows16 ? CPL / 2 : 1;  // 16-byte units of a bf16 row per lane
   float4* feat = reinterpret_cast<float4*>(v.feat);
   float4* featb = reinterpret_cast<float4*>(v.feat);  // bf16 volume: D / 8 units of 16 bytes per row
   const __amdgpu_buffer_rsrc_t maps_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -1030,7 +1033,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
   kf.H = wa.H; kf.W = wa.W; kf.npy = wa.npy; kf.npx = wa.npx; kf.rgb_bilinear = wa.rgb_bilinear;
   kf.depth = nullptr; kf.pose = nullptr; kf.K = nullptr;
   unsigned long long hits_done = 0, rows_done = 0;
-  [[maybe_unused]] uint32_t guard_done = 0;  // UNDO, per lane: hits that found their voxel at weight 0
+  [[maybe_unused]] uint32_t guard_done = 0;  // RT.undo, per lane: hits that found their voxel at weight 0
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   WT_DECL;
   // persistent grid (2 workgroups of 4 waves per CU, 71 KB of LDS each).  Pieces are handed out by an
@@ -1162,8 +1165,8 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
         const uint32_t hf = j < htot ? s_hf[j] : 0u;
         const uint32_t n = (uint32_t)__shfl((int)n_l, (int)(hf & 63u));
         int lbl = -1;  // the hit's panoptic class, -1: none
-        bool gone = true;  // UNDO: the hit is one of its voxel's first min(k, w0), the ones that leave
-        if constexpr (UNDO) gone = j - __shfl(prefix, (int)(hf & 63u)) < __shfl(w0, (int)(hf & 63u));
+        bool gone = true;  // RT.undo: the hit is one of its voxel's first min(k, w0), the ones that leave
+        if constexpr (RT.undo) gone = j - __shfl(prefix, (int)(hf & 63u)) < __shfl(w0, (int)(hf & 63u));
         if (j < htot) {
           const int fb = (int)(hf >> 22);
           int ix, iy, iz;
@@ -1191,7 +1194,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             const long long l = (long long)(pix >= 0 ? lraw : 0.f);
             const bool ok = l >= 0 && l < v.n_classes;
             lbl = ok ? (int)l : -1;
-            if constexpr (UNDO) {
+            if constexpr (RT.undo) {
               if (!gone) lbl = -1;  // (a class that was dropped forward is skipped and not counted again)
             } else {
             if (!ok && stats) atomicAdd(&stats[3], 1ull);
@@ -1209,7 +1212,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
           const unsigned long long stops = __ballot(head || lbl < 0);  // where a run cannot continue
           const unsigned long long above = lane == 63 ? 0ull : (stops >> (lane + 1));
           const int len = above ? __ffsll((long long)above) : 64 - lane;
-          if constexpr (UNDO) {
+          if constexpr (RT.undo) {
             // minus the run's length, never below 0 -- what `len` clamped single decrements leave.  Several runs of one class and
             // voxel (A, B, A) are different lanes on one address: a compare-and-swap loop, whose results compose in any order.
             if (head) {
@@ -1230,7 +1233,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
       WT(2);
       // ---- lane-parallel over voxels: the rgb running mean over the voxel's hits in frame order, in
       //      registers (clipfusion.py:715-721); a = 1/(w+1), b = w*a of every hit take the samples' slots
-      if constexpr (UNDO) {
+      if constexpr (RT.undo) {
         // the first k_eff = min(k, w0) hits leave in frame order (fuse_scalars_lane<true>'s a, b and unblend); the others found the
         // voxel empty: the guard's skips.  A voxel that loses nothing is not written.
         const int k_eff = active ? min(h, w0) : 0;
@@ -1257,9 +1260,9 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
           const int j = prefix + r;
           const int wi = w0 + r;
           const float a = 1.0f / (float)(wi + 1), b = (float)wi * a;
-          o0 = blend(s_ha[j], o0, a, b, SUM);
-          o1 = blend(s_hb[j], o1, a, b, SUM);
-          o2 = blend(s_hs2[j], o2, a, b, SUM);
+          o0 = blend(s_ha[j], o0, a, b, RT.sum);
+          o1 = blend(s_hb[j], o1, a, b, RT.sum);
+          o2 = blend(s_hs2[j], o2, a, b, RT.sum);
           s_ha[j] = a;
           s_hb[j] = b;
         }
@@ -1350,14 +1353,14 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             const Bilin w = bilinear_setup(hit ? s_hgx[sj] : 0.0f, hit ? s_hgy[sj] : 0.0f, half_px, half_py);
             rec.nw = w.nw; rec.ne = w.ne; rec.sw = w.sw; rec.se = w.se;
           }
-          if constexpr (UNDO) {
+          if constexpr (RT.undo) {
             // the samples LEAVE: weighted by -1 / w0 where forward has +1 / w0.  (The hits of a row that empties, k >= w0, or that
             // was empty, w0 == 0, add into an accumulator that is never stored.)
             const int w0h = __shfl(w0, (int)(hfl & 63u));
             const float rs = w0h == 0 ? 1.0f : -1.0f / (float)w0h;
             rec.nw *= rs; rec.ne *= rs; rec.sw *= rs; rec.se *= rs;
           } else
-          if constexpr (OF && !SUM && !BF16) {
+          if constexpr (OF && !RT.sum && !RT.rows16) {
             // f32 running mean: the accumulator starts as the OLD row, unscaled (it is loaded straight into the registers and
             // first touched by whichever hit comes first), so every sample of a row is weighted by 1 / w0 instead -- lane-
             // parallel, on the hit's four tap weights -- and the row leaves as acc x w0 / (w0 + k).  A fresh row (w0 = 0)
@@ -1384,12 +1387,12 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
               low[w] = (uint32_t)w < fwd ? 0xffffffffu : ((uint32_t)w == fwd ? (1u << fbit) - 1u : 0u);
 #pragma unroll
             for (int r = 0; r < SR; ++r) {
-              if constexpr (UNDO) {  // not loaded: a row that is empty already (never read, never written) or that empties (zeros)
+              if constexpr (RT.undo) {  // not loaded: a row that is empty already (never read, never written) or that empties (zeros)
                 if (r < nrows && __builtin_amdgcn_readlane(h, i0 + r) >= __builtin_amdgcn_readlane(w0, i0 + r)) fresh |= 1u << r;
               } else
               if (r < nrows && __builtin_amdgcn_readlane(w0, i0 + r) == 0) {
                 fresh |= 1u << r;
-                if (!BF16 && !OF) {
+                if (!RT.rows16 && !OF) {
 #pragma unroll
                   for (int c = 0; c < CPL; ++c) rows[(r * CPL + c) * 64 + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
@@ -1424,11 +1427,11 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
 #pragma unroll
               for (int r = 0; r < SR; ++r) {
                 // bf16: the accumulator holds the samples only, the old row waits in `raw`; f32: a fresh or absent row starts at 0
-                if (BF16 || r >= nrows || (fresh & (1u << r))) {
+                if (RT.rows16 || r >= nrows || (fresh & (1u << r))) {
 #pragma unroll
                   for (int c = 0; c < 2 * CPL; ++c) acc[r][c] = (win_v2f){0.f, 0.f};
                 }
-                if (BF16 && (r >= nrows || (fresh & (1u << r)))) {
+                if (RT.rows16 && (r >= nrows || (fresh & (1u << r)))) {
 #pragma unroll
                   for (int k = 0; k < UPL; ++k) raw.u[r * UPL + k] = make_uint4(0u, 0u, 0u, 0u);
                 }
@@ -1439,11 +1442,11 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
               if (r < nrows) {
                 const int64_t row = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)n_l, i0 + r) * DV;
                 if (fresh & (1u << r)) {
-                  if (BF16 && !OF) {
+                  if (RT.rows16 && !OF) {
 #pragma unroll
                     for (int k = 0; k < UPL; ++k) raw.u[r * UPL + k] = make_uint4(0u, 0u, 0u, 0u);
                   }
-                } else if (BF16) {
+                } else if (RT.rows16) {
 #pragma unroll
                   for (int k = 0; k < UPL; ++k) {
                     const float4 t = ld_stream(featb + (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)n_l, i0 + r) * (DV / 2) +
@@ -1519,15 +1522,15 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
             if constexpr (OF) {
               // ONE instantiation: a batch with fewer than P groups has empty groups at its end (hl[u] = hl[u + 1] = n_pass), whose
               // taps are "outside the map" -- no memory request -- and whose hit loops find no lane
-              win_batch_of<P, CPL, SUM, BF16, SR, F16>(cx, hl, nb, go, srt, rm, acc);
+              win_batch_of<P, CPL, K, SR>(cx, hl, nb, go, srt, rm, acc);
             } else {
             switch (nb) {
-                case 1: { const int h1[2] = {hl[0], hl[1]}; win_batch<1, CPL, SUM, BF16, SR, F16>(cx, h1, first, go, srt, raw); break; }
-                case 2: if constexpr (P >= 2) { const int h2[3] = {hl[0], hl[1], hl[2]}; win_batch<2, CPL, SUM, BF16, SR, F16>(cx, h2, first, go, srt, raw); } break;
-                case 3: if constexpr (P >= 3) { const int h3[4] = {hl[0], hl[1], hl[2], hl[3]}; win_batch<3, CPL, SUM, BF16, SR, F16>(cx, h3, first, go, srt, raw); } break;
-                case 4: if constexpr (P >= 4) { const int h4[5] = {hl[0], hl[1], hl[2], hl[3], hl[4]}; win_batch<4, CPL, SUM, BF16, SR, F16>(cx, h4, first, go, srt, raw); } break;
-                case 5: if constexpr (P >= 5) { const int h5[6] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5]}; win_batch<5, CPL, SUM, BF16, SR, F16>(cx, h5, first, go, srt, raw); } break;
-                default: if constexpr (P >= 6) { const int h6[7] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5], hl[6]}; win_batch<6, CPL, SUM, BF16, SR, F16>(cx, h6, first, go, srt, raw); } break;
+                case 1: { const int h1[2] = {hl[0], hl[1]}; win_batch<1, CPL, K, SR>(cx, h1, first, go, srt, raw); break; }
+                case 2: if constexpr (P >= 2) { const int h2[3] = {hl[0], hl[1], hl[2]}; win_batch<2, CPL, K, SR>(cx, h2, first, go, srt, raw); } break;
+                case 3: if constexpr (P >= 3) { const int h3[4] = {hl[0], hl[1], hl[2], hl[3]}; win_batch<3, CPL, K, SR>(cx, h3, first, go, srt, raw); } break;
+                case 4: if constexpr (P >= 4) { const int h4[5] = {hl[0], hl[1], hl[2], hl[3], hl[4]}; win_batch<4, CPL, K, SR>(cx, h4, first, go, srt, raw); } break;
+                case 5: if constexpr (P >= 5) { const int h5[6] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5]}; win_batch<5, CPL, K, SR>(cx, h5, first, go, srt, raw); } break;
+                default: if constexpr (P >= 6) { const int h6[7] = {hl[0], hl[1], hl[2], hl[3], hl[4], hl[5], hl[6]}; win_batch<6, CPL, K, SR>(cx, h6, first, go, srt, raw); } break;
               }
             }
             first = false;
@@ -1544,7 +1547,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
         for (int r = 0; r < SR; ++r) {
           if (r < nrows) {
             const int64_t row = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)n_l, i0 + r) * DV;
-            if constexpr (UNDO) {  // (w0 old - the window's samples) / (w0 - k); zeros where the row empties; nothing where it was empty
+            if constexpr (RT.undo) {  // (w0 old - the window's samples) / (w0 - k); zeros where the row empties; nothing where it was empty
               const int k_r = __builtin_amdgcn_readlane(h, i0 + r), w0_r = __builtin_amdgcn_readlane(w0, i0 + r);
               if (w0_r > 0) {
                 const bool empties = k_r >= w0_r;
@@ -1570,18 +1573,18 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
               const int k_r = __builtin_amdgcn_readlane(h, i0 + r), w0_r = __builtin_amdgcn_readlane(w0, i0 + r);
               const float inv = 1.0f / (float)(w0_r + k_r);
               // f32: acc = old + (sum of samples) / w0 (or the plain sum for a fresh row); bf16: acc = the sum of samples
-              const float fac = SUM ? 1.0f : ((BF16 || w0_r == 0) ? inv : (float)w0_r * inv);
-              if (BF16) {
-                const float f = SUM ? 1.0f : (float)w0_r;
+              const float fac = RT.sum ? 1.0f : ((RT.rows16 || w0_r == 0) ? inv : (float)w0_r * inv);
+              if (RT.rows16) {
+                const float f = RT.sum ? 1.0f : (float)w0_r;
 #pragma unroll
                 for (int k = 0; k < UPL; ++k) {
-                  const uint4 w = raw.u[r * UPL + k];  // + w0 x old (SUM: + old), then the mean, packed into the same registers
+                  const uint4 w = raw.u[r * UPL + k];  // + w0 x old (RT.sum: + old), then the mean, packed into the same registers
                   const win_v2f a0 = acc[r][4 * k], a1 = acc[r][4 * k + 1], a2 = acc[r][4 * k + 2], a3 = acc[r][4 * k + 3];
                   uint4 q;
-                  q.x = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.x), f, a0.x) * fac, __builtin_fmaf(h16_hi<F16>(w.x), f, a0.y) * fac);
-                  q.y = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.y), f, a1.x) * fac, __builtin_fmaf(h16_hi<F16>(w.y), f, a1.y) * fac);
-                  q.z = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.z), f, a2.x) * fac, __builtin_fmaf(h16_hi<F16>(w.z), f, a2.y) * fac);
-                  q.w = pack_h16<F16>(__builtin_fmaf(h16_lo<F16>(w.w), f, a3.x) * fac, __builtin_fmaf(h16_hi<F16>(w.w), f, a3.y) * fac);
+                  q.x = pack_h16<RT.half>(__builtin_fmaf(h16_lo<RT.half>(w.x), f, a0.x) * fac, __builtin_fmaf(h16_hi<RT.half>(w.x), f, a0.y) * fac);
+                  q.y = pack_h16<RT.half>(__builtin_fmaf(h16_lo<RT.half>(w.y), f, a1.x) * fac, __builtin_fmaf(h16_hi<RT.half>(w.y), f, a1.y) * fac);
+                  q.z = pack_h16<RT.half>(__builtin_fmaf(h16_lo<RT.half>(w.z), f, a2.x) * fac, __builtin_fmaf(h16_hi<RT.half>(w.z), f, a2.y) * fac);
+                  q.w = pack_h16<RT.half>(__builtin_fmaf(h16_lo<RT.half>(w.w), f, a3.x) * fac, __builtin_fmaf(h16_hi<RT.half>(w.w), f, a3.y) * fac);
                   raw.u[r * UPL + k] = q;
                   st_stream(featb + (row / 2) + lane + k * 64, make_float4(__builtin_bit_cast(float, q.x), __builtin_bit_cast(float, q.y),
                                                                            __builtin_bit_cast(float, q.z), __builtin_bit_cast(float, q.w)));
@@ -1590,7 +1593,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                 const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(feat + row, 0, v.D * 4, 0x00020000);
 #pragma unroll
                 for (int c = 0; c < CPL; ++c) {
-                  if (!SUM) {
+                  if (!RT.sum) {
                     acc[r][2 * c] = acc[r][2 * c] * (win_v2f){fac, fac};
                     acc[r][2 * c + 1] = acc[r][2 * c + 1] * (win_v2f){fac, fac};
                   }
@@ -1598,15 +1601,15 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
                   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(win_v4u, o), rr, lane * 16 + c * 1024, 0, SAF_WIN_OF_STPOL);
                 }
               }
-            } else if (BF16) {
+            } else if (RT.rows16) {
 #pragma unroll
               for (int k = 0; k < UPL; ++k) {
                 const float4 lo = rows[(r * CPL + 2 * k) * 64 + lane], hi = rows[(r * CPL + 2 * k + 1) * 64 + lane];
                 float4 o;  // the LDS values are bf16- (fp16-) exact already: the packing is lossless
-                o.x = __builtin_bit_cast(float, pack_h16<F16>(lo.x, lo.y));
-                o.y = __builtin_bit_cast(float, pack_h16<F16>(lo.z, lo.w));
-                o.z = __builtin_bit_cast(float, pack_h16<F16>(hi.x, hi.y));
-                o.w = __builtin_bit_cast(float, pack_h16<F16>(hi.z, hi.w));
+                o.x = __builtin_bit_cast(float, pack_h16<RT.half>(lo.x, lo.y));
+                o.y = __builtin_bit_cast(float, pack_h16<RT.half>(lo.z, lo.w));
+                o.z = __builtin_bit_cast(float, pack_h16<RT.half>(hi.x, hi.y));
+                o.w = __builtin_bit_cast(float, pack_h16<RT.half>(hi.z, hi.w));
                 st_stream(featb + (row / 2) + lane + k * 64, o);
               }
             } else {
@@ -1625,7 +1628,7 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
     }
   }
   WT_FLUSH;
-  if constexpr (UNDO) {  // the guard's skips on the weight side; stats[0], [5] are statements about fusion and do not move
+  if constexpr (RT.undo) {  // the guard's skips on the weight side; stats[0], [5] are statements about fusion and do not move
     unsigned long long g = guard_done;
     for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
     if (stats && lane == 0 && g) atomicAdd(&stats[13], g);
@@ -1638,63 +1641,37 @@ fuse_window_body(const KVol& v, const WinArgs& wa, const WinTable* __restrict__ 
 
 // The kernels proper.  Registers are handed out in blocks of eight and a SIMD has 512: two row waves of up to 176 leave room for TWO
 // classification waves of 80 beside them, two of 177 (= 184) for one.  The order-free D = 512 kernels -- the benchmark's -- are
-// therefore capped at 176 (amdgpu_num_vgpr takes no template-dependent value: hence two wrappers around one body); the bf16 one
-// had crept to 177 in round 5, and config 3's classification beside it lost its second wave per SIMD.
+// therefore capped at 176 (amdgpu_num_vgpr takes no template-dependent value: hence a wrapper of their own around the one body);
+// the bf16 one had crept to 177 in round 5, and config 3's classification beside it lost its second wave per SIMD (DESIGN.md
+// section 4.1g).  The backward kind (saf_unfuse_frames_windowed) has the same pair under names of its own, with its forward
+// twins' register budgets and LDS layout: a kernel trace tells a removal from a fusion.
 constexpr int kWinOfVgprs = 176;
-template <int CPL, bool SUM, bool BF16, bool OF>
+#define SAF_WIN_KERNEL_ARGS                                                                                                        \
+  KVol v, WinArgs wa, const WinTable *__restrict__ tab, const float *__restrict__ map_imgs, int img_vecs,                          \
+      unsigned long long *__restrict__ stats, unsigned int *__restrict__ piece_ctr, const uint32_t *__restrict__ hitmask,          \
+      uint32_t mask_plane, const unsigned long long *__restrict__ cls_acc, int xcd_order
+#define SAF_WIN_BODY(CPL_, K_, OF_) \
+  fuse_window_body<CPL_, K_, OF_>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order)
+template <int CPL, RowKind K, bool OF>
 __global__ __launch_bounds__(kWinThreads)
 __attribute__((amdgpu_waves_per_eu(OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE, OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE))) void
-fuse_window_kernel(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                   unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                   const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                   int xcd_order) {
-  fuse_window_body<CPL, SUM, BF16, OF>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+fuse_window_kernel(SAF_WIN_KERNEL_ARGS) {
+  SAF_WIN_BODY(CPL, K, OF);
 }
-template <int CPL, bool SUM, bool BF16>
-__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
-fuse_window_kernel_of176(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                         unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                         const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                         int xcd_order) {
-  fuse_window_body<CPL, SUM, BF16, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+template <RowKind K>
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void fuse_window_kernel_of176(SAF_WIN_KERNEL_ARGS) {
+  SAF_WIN_BODY(2, K, true);
 }
-
-// fp16 volumes (running mean only: make_kvol refuses SAF_SUM): the bf16 instantiations' body with F16 set, under the same
-// register budgets.  Kernels of their own, so that the f32 / bf16 kernels keep their names and their code.
-template <int CPL, bool OF>
-__global__ __launch_bounds__(kWinThreads)
-__attribute__((amdgpu_waves_per_eu(OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE, OF ? SAF_WIN_OF_WPE : SAF_WIN_WPE))) void
-fuse_window_kernel_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                       unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                       const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                       int xcd_order) {
-  fuse_window_body<CPL, false, true, OF, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
-}
-__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
-fuse_window_kernel_of176_f16(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                             unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                             const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                             int xcd_order) {
-  fuse_window_body<2, false, true, true, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
-}
-
-// The backward row kernels (saf_unfuse_frames_windowed): fuse_window_body<CPL, SUM = false, BF16 = false, OF = true> under UNDO,
-// kernels of their own under the forward twins' register budgets and with their LDS layout (WinCfg<CPL, true>).
 template <int CPL>
 __global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(SAF_WIN_OF_WPE, SAF_WIN_OF_WPE))) void
-window_unfuse_kernel(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                     unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                     const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                     int xcd_order) {
-  fuse_window_body<CPL, false, false, true, false, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+window_unfuse_kernel(SAF_WIN_KERNEL_ARGS) {
+  SAF_WIN_BODY(CPL, RowKind::UndoF32, true);
 }
-__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void
-window_unfuse_kernel_of176(KVol v, WinArgs wa, const WinTable* __restrict__ tab, const float* __restrict__ map_imgs, int img_vecs,
-                           unsigned long long* __restrict__ stats, unsigned int* __restrict__ piece_ctr,
-                           const uint32_t* __restrict__ hitmask, uint32_t mask_plane, const unsigned long long* __restrict__ cls_acc,
-                           int xcd_order) {
-  fuse_window_body<2, false, false, true, false, true>(v, wa, tab, map_imgs, img_vecs, stats, piece_ctr, hitmask, mask_plane, cls_acc, xcd_order);
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_num_vgpr(kWinOfVgprs))) void window_unfuse_kernel_of176(SAF_WIN_KERNEL_ARGS) {
+  SAF_WIN_BODY(2, RowKind::UndoF32, true);
 }
+#undef SAF_WIN_KERNEL_ARGS
+#undef SAF_WIN_BODY
 
 // ---------------------------------------------------------------------------------------------
 // Windowed (voxel-major) path of saf_fuse_frames: see fuse_window_kernel.
@@ -1724,38 +1701,28 @@ WinLayout win_layout(int64_t n_vox, int D, int P, bool bricks = false, size_t de
 
 using WinFn = void (*)(KVol, WinArgs, const WinTable*, const float*, int, unsigned long long*, unsigned int*, const uint32_t*,
                        uint32_t, const unsigned long long*, int);
+// The row kernel of a width, a form and a kind, and its LDS; nullptr where none is built: a lane's 16-byte unit of a 16-bit row is
+// 8 channels (an even CPL), and the frames leave the rows through the order-free form only.
 template <int CPL, bool OF>
-WinFn pick_win(bool sum, int e16) {
-  const bool rows16 = e16 != 0;  // 16-bit rows: the kernels' BF16 parameter (bfloat16 unless F16 says half)
-  if (e16 == kE16Half) {
-    if (CPL % 2 != 0 || sum) return nullptr;
-    constexpr int C2 = CPL % 2 == 0 ? CPL : 2;
-    if (OF && CPL == 2) return fuse_window_kernel_of176_f16;
-    return fuse_window_kernel_f16<C2, OF>;
-  }
-  if (OF && CPL == 2) {  // the benchmark's kernels: within 176 registers (see fuse_window_kernel_of176)
-    if (rows16) return sum ? fuse_window_kernel_of176<2, true, true> : fuse_window_kernel_of176<2, false, true>;
-    return sum ? fuse_window_kernel_of176<2, true, false> : fuse_window_kernel_of176<2, false, false>;
-  }
-  if (rows16) {
-    if (CPL % 2 != 0) return nullptr;
-    constexpr int C2 = CPL % 2 == 0 ? CPL : 2;
-    return sum ? fuse_window_kernel<C2, true, true, OF> : fuse_window_kernel<C2, false, true, OF>;
-  }
-  return sum ? fuse_window_kernel<CPL, true, false, OF> : fuse_window_kernel<CPL, false, false, OF>;
+WinFn pick_win(RowKind kind, size_t* lds) {
+  *lds = WinCfg<CPL, OF>::total;  // (the same for every kind)
+  return dispatch_row_kind(kind, [](auto k) -> WinFn {
+    constexpr RowKind K = decltype(k)::value;
+    constexpr RowTraits RT = row_traits(K);
+    constexpr bool of176 = OF && CPL == 2;  // the benchmark's kernels: within 176 registers
+    if constexpr ((RT.rows16 && CPL % 2 != 0) || (RT.undo && !OF)) return nullptr;
+    else if constexpr (RT.undo && of176) return window_unfuse_kernel_of176;
+    else if constexpr (RT.undo) return window_unfuse_kernel<CPL>;
+    else if constexpr (of176) return fuse_window_kernel_of176<K>;
+    else return fuse_window_kernel<CPL, K, OF>;
+  });
 }
-template <int CPL>
-WinFn pick_win(bool sum, int e16, bool of, size_t* lds) {
-  *lds = of ? WinCfg<CPL, true>::total : WinCfg<CPL, false>::total;
-  return of ? pick_win<CPL, true>(sum, e16) : pick_win<CPL, false>(sum, e16);
-}
-// the backward row kernel of a width (f32 running means, order-free form: unfuse_windowed)
-WinFn pick_unwin(int cpl, size_t* lds) {
+WinFn pick_win(int cpl, bool of, RowKind kind, size_t* lds) {
   switch (cpl) {
-    case 1: *lds = WinCfg<1, true>::total; return window_unfuse_kernel<1>;
-    case 2: *lds = WinCfg<2, true>::total; return window_unfuse_kernel_of176;
-    case 3: *lds = WinCfg<3, true>::total; return window_unfuse_kernel<3>;
-    default: *lds = WinCfg<4, true>::total; return window_unfuse_kernel<4>;
+    case 1: return of ? pick_win<1, true>(kind, lds) : pick_win<1, false>(kind, lds);
+    case 2: return of ? pick_win<2, true>(kind, lds) : pick_win<2, false>(kind, lds);
+    case 3: return of ? pick_win<3, true>(kind, lds) : pick_win<3, false>(kind, lds);
+    default: return of ? pick_win<4, true>(kind, lds) : pick_win<4, false>(kind, lds);
   }
 }
 
@@ -1835,7 +1802,7 @@ FuseRoute fuse_route(const KVol& kv, const saf_frame* frames, int32_t n_frames, 
 // backwards, and only where the caller did not ask for another form -- i.e. where the same call forward would take kPathSums with
 // SAF_WIN_FORM unset or "sums".  Everything else about the call (frames of one shape, 16 or more, the workspace) is fuse_route's.
 bool unfuse_windowed(const KVol& kv, const saf_frame* frames, int32_t n_frames, size_t workspace_bytes, const Knobs& kn) {
-  if (kv.e16 != 0 || kv.accum == SAF_SUM) return false;
+  if (!row_kind_of(kv, true)) return false;
   if (kn.win_form != 0 && kn.win_form != 's') return false;
   return fuse_route(kv, frames, n_frames, workspace_bytes, kn).path == kPathSums;
 }
@@ -1891,25 +1858,16 @@ int win_plan(const KVol& kv, const KFrame& kf0, size_t workspace_bytes, const Kn
   pl->fn = nullptr;
   pl->win_lds = 0;
   if (undo && form != kPathSums) return fail(SAF_E_UNSUPPORTED, "windowed removal: the order-free row form only");
-  if (undo) {
-    pl->fn = pick_unwin(kv.D / 256, &pl->win_lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl->win_lds);
-    if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
-  } else
-  if (!pl->brick_form) {
-    switch (kv.D / 256) {
-      case 1: pl->fn = pick_win<1>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
-      case 2: pl->fn = pick_win<2>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
-      case 3: pl->fn = pick_win<3>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
-      default: pl->fn = pick_win<4>(pl->sum, kv.e16, pl->of, &pl->win_lds); break;
-    }
+  if (!pl->brick_form) {  // (the removal's form, kPathSums, is a row form)
+    const std::optional<RowKind> kind = row_kind_of(kv, undo);
+    if (kind) pl->fn = pick_win(kv.D / 256, pl->of, *kind, &pl->win_lds);
     if (!pl->fn) return fail(SAF_E_UNSUPPORTED, "windowed path: no row kernel for this width");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pl->fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)pl->win_lds);
     if (e != hipSuccess) return fail(SAF_E_HIP, "hipFuncSetAttribute(LDS=%zu): %s", pl->win_lds, hipGetErrorString(e));
   }
-  // bf16 / fp16 volume in the order-free form: the window's map images are kept in the volume's type (what the kernel's BF16 && OF
-  // instantiations read)
+  // bf16 / fp16 volume in the order-free form: the window's map images are kept in the volume's type (what the order-free
+  // kernels of the 16-bit kinds read)
   pl->maps16 = !pl->brick_form && pl->of && kv.e16 != 0;
   pl->img_bytes16 = ((size_t)kv.D * (P + 1) * 2 + 255) & ~(size_t)255;
   if (pl->maps16) pl->img_vecs = (int)(pl->img_bytes16 / sizeof(float4));

@@ -24,7 +24,7 @@ def kind(name):
         return "rows"
     if "classify_bricks" in name or "classify_window" in name:
         return "classify"
-    if "fuse_brick" in name:  # fuse_brick_kernel<CPL, SUM, BF16, BUILD>: the last template argument tells the two kernels apart
+    if "fuse_brick" in name:  # fuse_brick_kernel<CPL, K, BUILD, REBUILD>: the last template argument tells the two kernels apart
         return "build" if name.split(">(")[0].rstrip().endswith("true") else "walk"
     return None
 out = {}
