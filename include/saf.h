@@ -774,6 +774,59 @@ int saf_volume_resample(const saf_volume* src, const saf_volume* dst, const floa
                         void* stream);
 
 /*
+ * Free-space carving: fused voxels that later frames SEE THROUGH are taken out of the volume again (additive under ABI 7; new
+ * capability: the reference's integrate moves such a voxel's TSDF towards +1, clipfusion.py:678-679, and leaves its weight,
+ * colour, features and label histogram alone, so an object that was carried out of the room stays in the volume for ever;
+ * DESIGN.md section 4.23).  Two passes: saf_free_space_observe gathers the evidence, saf_volume_carve acts on it.
+ *
+ * saf_free_space_observe: for every voxel with weight > 0 and every frame of the call, the reference's classification of the voxel
+ * centre (clipfusion.py:647-679) -- the projection, the nearest depth tap with zeros outside the image, sdf = (depth - z) / trunc,
+ * in_view = |grid| <= 1 on both axes and z > 0, valid = in_view and |sdf| <= 1, tsdf_valid = in_view and sdf > -1: the operations
+ * of the fuse path, whose decisions are pinned to the oracle's bit for bit -- and then
+ *   seen[n] += the number of frames with tsdf_valid && !valid   (sdf > 1: the frame measured a surface BEHIND the voxel)
+ *   hit[n]  += the number of frames with valid                  (the frame supports a surface at the voxel)
+ * The counts are ADDED: a scan's frames may come over several calls, in any split and any order, with identical results.  The
+ * entries of voxels with weight == 0 are neither read nor written.  The pass reads `weight`, `trunc` and the axis tables and
+ * nothing else of the volume -- no feature row: a volume whose deferred clear is still owed is fine.  Depth values are taken as the
+ * fuse path takes them: NaN gives neither count, +inf gives `seen`, and 0 or a negative value is a surface at or behind the camera
+ * -- neither count for a voxel deeper than trunc, a hit for one nearer than that, exactly as the frame would be fused.
+ *   depth [B,H,W], poses [B,4,4] (camera to world), K [B,3,3]: device f32, contiguous; seen, hit: device int32[nx ny nz].
+ * One launch: a wave owns 64 consecutive voxels of the flattened grid (z fastest) and is their only writer (no atomics); a wave
+ * with no touched voxel leaves at once; the frame loop is wave-uniform, a frame's pose and K are read through uniform addresses;
+ * the counts stay in registers over the frames, then one load / add / store per touched voxel.  4 N bytes of weights are read,
+ * per touched voxel and frame in view one depth tap, per touched voxel 16 bytes of evidence are read and written.
+ *
+ * saf_volume_carve: a voxel is carved iff weight > 0 && seen >= min_views && hit <= max_support.  A carved voxel becomes what a
+ * fresh volume holds: weight, tsdf_weight, tsdf, the three rgb floats, the whole feature row and (n_classes > 0) the whole label
+ * histogram row are set to zero bytes, so that fusing further frames gives, on a carved voxel, exactly what a fresh volume would
+ * hold.  Every other byte of the volume is untouched; the evidence is only read, and of untouched voxels not even that.
+ *   carved    device u8[N] (may be NULL): written 1 or 0 for EVERY voxel.
+ *   counts[]  device u64[4], ADDED to (may be NULL): [0] voxels with weight > 0, [1] voxels carved, [2] voxels kept because
+ *             hit > max_support although seen >= min_views, [3] voxels kept with 0 < seen < min_views.  Integer atomics, one per
+ *             wave and counter.
+ * One launch, saf_volume_carry's shape: each lane decides and zeroes its voxel's small fields, a ballot names the carved voxels
+ * and the wave zeroes their rows one after the other, 16 bytes per lane where the row pitch and the base allow it, else 4 or 2.
+ * No LDS, no scratch, no floating-point atomics.
+ *
+ * Both return SAF_E_INVALID on the host, with nothing launched, for a NULL volume, a NULL buffer they use (observe: weight, the
+ * axis tables, depth, poses, K, seen, hit; carve: the six volume buffers, seen, hit), non-positive sizes (voxels per axis, batch,
+ * height, width, feat_dim; a trunc that is not positive and finite), a grid of 2^31 voxels or more, an image of more than 2^31 - 1
+ * pixels, min_views < 1, max_support < 0, an unknown feat_dtype, and a buffer that is not aligned to its element type; and
+ * SAF_E_UNSUPPORTED for a SAF_SUM volume.
+ * Left out: a margin beyond trunc (it would need its own float statement of sdf; the caller erodes the depth and asks for more
+ * views instead), any policy that decides WHEN to carve, and taking carved frames out later (saf_unfuse_frames skips and counts a
+ * voxel whose count is 0, as it always did).
+ * Measured (256^3 x 512 f32; the coherent scene, 17 % touched / a 79 % touched volume): 128 frames of
+ * 640 x 480 observed in 3.41 / 19.16 ms, against 376 ms for the reference's per-frame projection and masks in torch; the carve of
+ * 0.59 M / 2.01 M voxels in 0.59 / 0.92 ms, 0.19 x / 0.09 x saf_volume_carry's time over the same volume, 11.6 ms as masked fills
+ * in torch.
+ */
+int saf_free_space_observe(const saf_volume* vol, const float* depth, int32_t batch, int32_t height, int32_t width,
+                           const float* poses, const float* K, int32_t* seen, int32_t* hit, void* stream);
+int saf_volume_carve(const saf_volume* vol, const int32_t* seen, const int32_t* hit, int32_t min_views, int32_t max_support,
+                     uint8_t* carved, uint64_t* counts, void* stream);
+
+/*
  * Vertex sampling half of extract_mesh (clipfusion.py:741-760; clip_seem_fusion.py:843-878): for
  * marching-cubes vertices given in voxel-index coordinates, grid = (v + 0.5) * (1/nvox) * 2 - 1 and
  * 3-D grid_sample(align_corners=False, zeros padding) of the volume:

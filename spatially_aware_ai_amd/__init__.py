@@ -20,6 +20,9 @@ __all__ = [
     "GridAbsorb",
     "GridCoarsen",
     "GridResample",
+    "FreeSpaceEvidence",
+    "CarveResult",
+    "erode_depth",
     "label_components",
     "discover_objects",
     "evaluation",
@@ -40,7 +43,7 @@ __all__ = [
 
 def __getattr__(name):
     if name in ("ClipFusion", "Clip", "backproject_pcd", "get_pix_vecs", "scene_bounds", "lattice_box", "GridMove", "GridAbsorb",
-                "GridCoarsen", "GridResample"):
+                "GridCoarsen", "GridResample", "FreeSpaceEvidence", "CarveResult", "erode_depth"):
         from . import clipfusion as _m
 
         return getattr(_m, name)

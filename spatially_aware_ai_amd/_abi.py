@@ -203,6 +203,8 @@ PROTOTYPES = {
     "saf_volume_absorb": (C.c_int, [C.POINTER(SafVolume), C.POINTER(SafVolume), C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
     "saf_volume_coarsen": (C.c_int, [C.POINTER(SafVolume), C.POINTER(SafVolume), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
     "saf_volume_resample": (C.c_int, [C.POINTER(SafVolume), C.POINTER(SafVolume), _fp, C.c_float, _fp, _fp]),
+    "saf_free_space_observe": (C.c_int, [C.POINTER(SafVolume), _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
+    "saf_volume_carve": (C.c_int, [C.POINTER(SafVolume), _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     "saf_label_argmax": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp]),
     "saf_sample_vertices": (C.c_int, [C.POINTER(SafVolume), _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "saf_clip_tiles": (

@@ -30,6 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi
+from ._carve import CarveResult, FreeSpaceEvidence, _CarveMixin, erode_depth  # noqa: F401
 from ._frame_queue import FrameQueue, StagingRing
 from ._grid_ops import (_DT, GridAbsorb, GridCoarsen, GridMove, GridResample, _axis_tables, _GridOpsMixin,  # noqa: F401
                         _volume_struct, _xyz_world, coarse_lattice, lattice_box, resample_box, resample_matrix)
@@ -52,8 +53,9 @@ _BORROW_DEFAULT = os.environ.get("SAF_BORROW_INPUTS", "0") == "1"
 _VOLUME_BUFFERS = frozenset(("tsdf", "rgb", "clip_feat", "weight", "tsdf_weight", "labels_one_hot", "fuse_stats"))
 
 
-class _FusionVolumeMixin(_GridOpsMixin):
-    """Buffers, workspace and the C-ABI call shared by both fusion modules (``move_grid``, ``absorb``, ``coarsen`` and ``resample``: _grid_ops.py)."""
+class _FusionVolumeMixin(_GridOpsMixin, _CarveMixin):
+    """Buffers, workspace and the C-ABI call shared by both fusion modules (``move_grid``, ``absorb``, ``coarsen`` and ``resample``:
+    _grid_ops.py; ``observe_free_space`` and ``carve``: _carve.py)."""
 
     def _init_volume(self, origin, voxel_size, nvox, trunc, feat_dim, n_classes=0, keep_xyz_world=True,
                      feat_dtype=torch.float32, index_offset=(0, 0, 0), x_planes=None, device=None):

@@ -52,6 +52,7 @@ class SceneResult:
     engine: TextQueryEngine | None = None
     objects: object | None = None  # objects.ObjectDescriptors, computed by the first object_query
     object_matches: object | None = None  # objects.ObjectMatches of extend_scene(keep_identities=True)
+    carve: object | None = None  # clipfusion.CarveResult of extend_scene(carve=True)
 
     def text_query(self, clip_model, text):
         """``clip_text_query`` (clip_seem_fusion.py:482-561): RGBA heat map over the scene mesh, or None."""
@@ -176,6 +177,23 @@ def _fuse_one_by_one(fusion, dataset, config, device, num_workers):
         host["integrate"] += t2 - t1
         t_prev = t2
     return host
+
+
+def _carve_by_frames(fusion, dataset, device, num_workers, knobs, batch_size=16):
+    """Every frame of ``dataset`` observed against the volume as it stands (depth, pose and K: the backbones see nothing), then the
+    carve applied once.  ``knobs``: ``min_views``, ``max_support``, ``erode`` of ``fusion.carve``."""
+    knobs = dict(knobs or {})
+    unknown = set(knobs) - {"min_views", "max_support", "erode"}
+    if unknown:
+        raise SafError(f"carve_knobs: unknown entries {sorted(unknown)} (min_views, max_support, erode)")
+    erode = knobs.pop("erode", 1)
+    evidence = None
+    for _, depth_imgs, poses, K, _ in torch.utils.data.DataLoader(dataset, batch_size=batch_size, num_workers=num_workers):
+        evidence = fusion.observe_free_space(depth_imgs.float().to(device), poses.float().to(device), K.float().to(device), erode=erode,
+                                             evidence=evidence)
+    if evidence is None:
+        raise SafError("extend_scene(carve=True): the dataset holds no frame")
+    return fusion.carve(evidence=evidence, **knobs)
 
 
 def _after_fusion(fusion, origin, nvox, xyz, clk, class_names, class_colors, scan_version, out_dir, object_meshes,
@@ -358,7 +376,7 @@ def reconstruct_scene(dataset, config, clip_model, seg_model, class_names, class
 
 def extend_scene(result, dataset, config, clip_model, seg_model, class_names, class_colors=None, out_dir=None, max_depth=4,
                  num_workers=0, object_meshes=True, marching_cubes=None, python_lists=False, multiple=4, keep_identities=False,
-                 identity_knobs=None):
+                 identity_knobs=None, carve=False, carve_knobs=None):
     """A later version of a scan: fuse its NEW frames (``dataset`` holds only those) into ``result.fusion`` and run the stages
     behind the fusion again.  The reference's manager fuses every frame of every version into a new grid (``/reprocess_scan``,
     ``get_path(config, curr_ver, ...)``): the backbones, which cost far more than the fusion, see the whole scan again.  Here the
@@ -378,7 +396,15 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     (``objects.carry_identities``) before the mesh and the per-object meshes are built: ``scene_knowledge`` gains
     ``unchanged_objects``, ``moved_objects``, ``new_objects`` and ``missing_objects`` without a trained in-situ model, the result
     ``object_matches``, ``seconds`` ``identities``.  The fused volume is the same either way.  A float16 module is refused
-    (``describe_objects``)."""
+    (``describe_objects``).
+
+    ``carve`` (default False: nothing changes): projective fusion only ever adds, so an object that was carried out of the room
+    between the versions stays in the volume -- the new frames look through where it stood, which moves the TSDF there and leaves
+    the weights, features and label histograms alone -- and is discovered again, in place, as "unchanged".  With ``carve=True``,
+    after ``move_grid`` and before the new frames are fused, every new frame's depth is observed against the old voxels
+    (``fusion.observe_free_space``) and what enough of them see through is taken out (``fusion.carve``): depth, pose
+    and K only, no frame goes through a backbone for it.  ``carve_knobs``: ``min_views``, ``max_support`` and ``erode`` of
+    ``fusion.carve``.  ``seconds`` gains ``carve``, the result ``carve`` (the ``CarveResult``)."""
     clk = _Clock()
     clk.start()
     fusion = result.fusion
@@ -396,6 +422,10 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
         clk.lap("identities")
     fusion.move_grid(index_offset, nvox)
     clk.lap("move_grid")
+    carved = None
+    if carve:
+        carved = _carve_by_frames(fusion, dataset, device, num_workers, carve_knobs)
+        clk.lap("carve")
     host = _fuse_one_by_one(fusion, dataset, config, device, num_workers)
     fusion.flush()
     clk.lap("fuse")
@@ -404,6 +434,7 @@ def extend_scene(result, dataset, config, clip_model, seg_model, class_names, cl
     res = _after_fusion(fusion, result.origin, fusion.nvox, torch.cat((result.xyz, xyz_new)), clk, class_names, class_colors, version,
                         out_dir, object_meshes, marching_cubes, python_lists, prev=prev)
     res.seconds = clk.seconds
+    res.carve = carved
     return res
 
 

@@ -141,9 +141,15 @@ def _analytic_depth(pose: torch.Tensor, k: torch.Tensor, width: int, height: int
 SCENE_SURFACE_CLASSES = (56, 131, 131, 119, 119, 122, 100)
 
 
-def _analytic_scene(pose: torch.Tensor, k: torch.Tensor, width: int, height: int, half=1.2):
+# The scene's sphere as (centre, radius); None: the room without it.  A scan version in which the object was carried out of the
+# room, or stands elsewhere, is the same scene with another value here.
+DEFAULT_SPHERE = ((0.0, 0.0, 0.0), 0.9)
+
+
+def _analytic_scene(pose: torch.Tensor, k: torch.Tensor, width: int, height: int, half=1.2, sphere=DEFAULT_SPHERE):
     """(depth [H,W] f32, surface [H,W] int64): depth as ``_analytic_depth``; surface 0 = the sphere, 1..6 = the box
-    face the ray leaves through (-x +x -y +y -z +z).  ``half``: the box's half-size, a number or one per axis."""
+    face the ray leaves through (-x +x -y +y -z +z).  ``half``: the box's half-size, a number or one per axis.  ``sphere``:
+    (centre, radius) of the sphere, or None for the empty room (the default is the sphere the scene always had, bit for bit)."""
     dev = pose.device
     u = torch.arange(width, dtype=torch.float64, device=dev)
     v = torch.arange(height, dtype=torch.float64, device=dev)
@@ -155,14 +161,19 @@ def _analytic_scene(pose: torch.Tensor, k: torch.Tensor, width: int, height: int
     rot = pose[:3, :3].double()
     o = pose[:3, 3].double()
     d = rays_cam @ rot.T  # world-space ray per unit camera z
-    # sphere |o + s d| = 0.9
+    # sphere |o + s d - centre| = radius
     a = (d * d).sum(-1)
-    b = 2 * (d @ o)
-    c = (o @ o) - 0.9**2
-    disc = b * b - 4 * a * c
     inf = torch.full_like(a, math.inf)
-    s_sphere = torch.where(disc > 0, (-b - disc.clamp_min(0).sqrt()) / (2 * a), inf)
-    s_sphere = torch.where(s_sphere > 0, s_sphere, inf)
+    if sphere is None:
+        s_sphere = inf
+    else:
+        centre, sphere_radius = sphere
+        oc = o - torch.as_tensor(centre, dtype=torch.float64, device=dev)  # (o - 0 is o: the default sphere sits at the origin)
+        b = 2 * (d @ oc)
+        c = (oc @ oc) - sphere_radius**2
+        disc = b * b - 4 * a * c
+        s_sphere = torch.where(disc > 0, (-b - disc.clamp_min(0).sqrt()) / (2 * a), inf)
+        s_sphere = torch.where(s_sphere > 0, s_sphere, inf)
     # box exit (camera is outside the box: take the far faces, i.e. the inside of the room)
     half = torch.as_tensor(half, dtype=torch.float64, device=dev)
     inv = 1.0 / d
@@ -204,10 +215,11 @@ def make_frame(
     box_half=1.2,
     pose_kind: str = "look_at",
     k_kind: str = "centred",
+    sphere=DEFAULT_SPHERE,
 ):
     """One frame: dict of CPU f32 tensors shaped like a B=1 batch of the reference's loaders
     (clipfusion.py:190) plus the per-frame feature map and label map that stand in for the
-    CLIP / kMaX backbones."""
+    CLIP / kMaX backbones.  ``sphere``: ``_analytic_scene``'s (depth B only); it draws nothing from ``gen``."""
     c = torch.randn(3, generator=gen, dtype=torch.float32)
     c = c / c.norm() * radius
     # (the defaults draw nothing more from `gen` than they always did: the committed goldens regenerate byte for byte)
@@ -217,7 +229,7 @@ def make_frame(
     if depth_kind == "A":
         depth = torch.rand(height, width, generator=gen, dtype=torch.float32) * 2.0 + 1.5
     elif depth_kind == "B":
-        depth, surface = _analytic_scene(pose, k, width, height, box_half)
+        depth, surface = _analytic_scene(pose, k, width, height, box_half, sphere)
         if pose_kind != "look_at":  # a ray that leaves the room backwards (the camera looks away from it): no depth
             depth = torch.where(torch.isfinite(depth) & (depth > 0), depth, torch.zeros_like(depth))
     else:
@@ -296,9 +308,10 @@ class SyntheticScan(torch.utils.data.Dataset):
     ``__getitem__ -> (rgb[H,W,3], depth[H,W], pose[4,4], K[3,3], idx)`` (clipfusion.py:190).  Per frame it also holds what the
     backbones would say: a panoptic map (the class of the surface every pixel sees) and a CLIP-shaped feature map whose
     cell (i, j) is the embedding of the class at the cell's centre plus noise -- so that objects, segment colours and a text
-    query over the reconstruction mean something."""
+    query over the reconstruction mean something.  ``sphere``: ``_analytic_scene``'s -- the same seed with another sphere, or
+    none, is the same cameras in the room after the object was moved or carried out."""
 
-    def __init__(self, seed, n_frames, width, height, feat_dim, box_half=1.2, noise=0.3):
+    def __init__(self, seed, n_frames, width, height, feat_dim, box_half=1.2, noise=0.3, sphere=DEFAULT_SPHERE):
         self.imwidth, self.imheight = width, height
         self.npy, self.npx = feature_map_shape(width, height)
         self.patch, self.stride = height // 3, height // 6
@@ -309,7 +322,8 @@ class SyntheticScan(torch.utils.data.Dataset):
         cy = torch.arange(self.npy) * self.stride + self.patch // 2
         cx = torch.arange(self.npx) * self.stride + self.patch // 2
         for _ in range(n_frames):
-            f = make_frame(gen, width, height, feat_dim, self.npy, self.npx, depth_kind="B", label_kind="scene", box_half=box_half)
+            f = make_frame(gen, width, height, feat_dim, self.npy, self.npx, depth_kind="B", label_kind="scene", box_half=box_half,
+                           sphere=sphere)
             centre_cls = cls_of[f["surface"][cy][:, cx]]  # [npy, npx]
             f["feat"] = (self.emb[centre_cls].permute(2, 0, 1) + noise * f["feat"][0])[None].contiguous()
             self.frames.append(f)
