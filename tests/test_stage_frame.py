@@ -1,15 +1,22 @@
 """saf_stage_frame (csrc/saf_misc.hip): one launch copies a frame's inputs into a slot of the staging ring -- 16-byte pieces where
 source and destination allow, 4-byte copies elsewhere (images whose size is not a multiple of four pixels put every second frame
-off a 16-byte boundary), a strided gather for a permuted feature map, nothing for images the caller lends (NULL on both sides)."""
+off a 16-byte boundary), a strided gather for a permuted feature map, nothing for images the caller lends (NULL on both sides).
+
+Copies are checked exactly, and every destination lies in one flat buffer with 64 guard floats before, between and after the
+slots (tests/frame_pass_reference.py: guarded, stage_expected): the WHOLE buffer is compared, so an overrun into the next slot
+of the ring or a write to a destination that has no source is seen."""
 import ctypes as C
 
 import pytest
 import torch
 
+import frame_pass_reference as R
 from spatially_aware_ai_amd import _abi
 from spatially_aware_ai_amd._lib import check, current_stream_ptr, lib
 
 pytestmark = pytest.mark.gpu
+
+FILL = -1.0  # (the sources are in [0, 1))
 
 
 def _frame(h, w, depth, rgb, pose, K, feat, npy, npx, labels):
@@ -17,36 +24,81 @@ def _frame(h, w, depth, rgb, pose, K, feat, npy, npx, labels):
     return _abi.SafFrame(h, w, p(depth), p(rgb), p(pose), p(K), p(feat), npy, npx, p(labels), 0)
 
 
-@pytest.mark.parametrize("h,w", [(48, 64), (33, 31), (7, 5), (480, 640)])
-@pytest.mark.parametrize("lend", [False, True])
-def test_stage_frame_copies_every_segment(h, w, lend):
+def _feature_view(layout, n, ch, npy, npx, g, dev):
+    """[n, C, npy, npx] views of three storages."""
+    if layout == "yxc":
+        return torch.rand((n, npy, npx, ch), generator=g, device=dev).permute(0, 3, 1, 2)
+    if layout == "ycx":
+        return torch.rand((n, npy, ch, npx), generator=g, device=dev).permute(0, 2, 1, 3)
+    return torch.rand((n, ch, npy, npx), generator=g, device=dev)
+
+
+def _stage_and_check(h, w, n=3, feat=(40, 5, 7), layout="yxc", copy=("depth", "rgb", "feat", "labels")):
+    """Stage n frames of a batch (frame i starts i * h * w * 4 bytes into its tensors) into guarded slots; `copy` names what
+    the source frame holds besides pose and K -- every destination is offered all the same and must stay untouched without a
+    source (depth and rgb are lent together: NULL on both sides)."""
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(h * 1000 + w)
-    npy, npx, ch = 5, 7, 40
-    n = 3  # frame 1 of a batch starts h * w * 4 bytes into the tensor: off a 16-byte boundary for odd sizes
-    src = {"depth": torch.rand((n, h, w), generator=g, device=dev), "rgb": torch.rand((n, h, w, 3), generator=g, device=dev),
-           "pose": torch.rand((n, 4, 4), generator=g, device=dev), "K": torch.rand((n, 3, 3), generator=g, device=dev),
-           "feat": torch.rand((n, npy, npx, ch), generator=g, device=dev).permute(0, 3, 1, 2),  # a permuted view [n, C, npy, npx]
-           "labels": torch.rand((n, h, w), generator=g, device=dev)}
-    dst = {"depth": torch.full((n, h, w), -1.0, device=dev), "rgb": torch.full((n, h, w, 3), -1.0, device=dev),
-           "pose": torch.full((n, 4, 4), -1.0, device=dev), "K": torch.full((n, 3, 3), -1.0, device=dev),
-           "feat": torch.full((n, ch, npy, npx), -1.0, device=dev), "labels": torch.full((n, h, w), -1.0, device=dev)}
+    ch, npy, npx = feat
+    shapes = {"depth": (h, w), "rgb": (h, w, 3), "pose": (4, 4), "K": (3, 3), "feat": (ch, npy, npx), "labels": (h, w)}
+    src = {k: torch.rand((n,) + s, generator=g, device=dev) for k, s in shapes.items() if k != "feat"}
+    src["feat"] = _feature_view(layout, n, ch, npy, npx, g, dev)
+    dst = {k: R.guarded(s, FILL, dev, count=n) for k, s in shapes.items()}
+    has = lambda k: k in ("pose", "K") or k in copy
+    lent = not has("depth")
+    assert has("rgb") != lent
     for i in range(n):
-        s = _frame(h, w, None if lend else src["depth"][i], None if lend else src["rgb"][i], src["pose"][i], src["K"][i], src["feat"][i],
-                   npy, npx, None if lend else src["labels"][i])
-        d = _frame(h, w, None if lend else dst["depth"][i], None if lend else dst["rgb"][i], dst["pose"][i], dst["K"][i], dst["feat"][i],
-                   npy, npx, None if lend else dst["labels"][i])
+        sv = {k: src[k][i] if has(k) else None for k in shapes}
+        dv = {k: None if lent and k in ("depth", "rgb") else dst[k][1][i] for k in shapes}
+        s = _frame(h, w, sv["depth"], sv["rgb"], sv["pose"], sv["K"], sv["feat"], npy if has("feat") else 0, npx if has("feat") else 0, sv["labels"])
+        d = _frame(h, w, dv["depth"], dv["rgb"], dv["pose"], dv["K"], dv["feat"], npy, npx, dv["labels"])
         fs = src["feat"][i].stride()
         check(lib().saf_stage_frame(C.byref(s), ch, fs[0], fs[1], fs[2], C.byref(d), current_stream_ptr()), "saf_stage_frame")
     torch.cuda.synchronize()
-    for k in ("pose", "K"):
-        assert torch.equal(dst[k], src[k]), k
-    assert torch.equal(dst["feat"], src["feat"].contiguous())
+    for k in shapes:
+        buf, views = dst[k]
+        want = R.stage_expected(buf, views, [src[k][i] if has(k) else None for i in range(n)], FILL)
+        assert torch.equal(buf, want), f"{k}: a copy is wrong, or the guards / an unsourced destination were written"
+    return src, dst
+
+
+@pytest.mark.parametrize("h,w", [(48, 64), (33, 31), (7, 5), (480, 640)])
+@pytest.mark.parametrize("lend", [False, True])
+def test_stage_frame_copies_every_segment(h, w, lend):
+    src, dst = _stage_and_check(h, w, copy=("feat",) if lend else ("depth", "rgb", "feat", "labels"))
+    assert torch.equal(torch.stack(dst["feat"][1]), src["feat"].contiguous())
     for k in ("depth", "rgb", "labels"):
         if lend:
-            assert bool((dst[k] == -1.0).all()), f"{k} was lent, not copied"
+            assert bool((dst[k][0] == FILL).all()), f"{k} was lent, not copied"
         else:
-            assert torch.equal(dst[k], src[k]), k
+            assert torch.equal(torch.stack(dst[k][1]), src[k]), k
+
+
+@pytest.mark.parametrize("h,w", [(67, 63), (64, 65)])
+def test_stage_frame_full_workgroups_off_alignment_and_ragged_tails(h, w):
+    """(67, 63): hw = 4221 and 3 hw = 12663 have full 4096-element workgroups, and frame 1 (source and slot) is off a 16-byte
+    boundary -- the scalar branch with i0 + 4096 <= n.  (64, 65): 4160 elements, a ragged second workgroup behind a full one on
+    the vector branch."""
+    assert h * w > 4096 and ((h * w) % 4 != 0) == ((h, w) == (67, 63))
+    _stage_and_check(h, w)
+
+
+@pytest.mark.parametrize("feat", [(40, 11, 13), (512, 6, 8)], ids=str)
+@pytest.mark.parametrize("layout", ["yxc", "ycx", "contiguous"])
+def test_stage_frame_gathers_large_feature_maps(feat, layout):
+    """5720 and 24576 elements: the gather's second workgroup starts at element 4096 -- once with a ragged last workgroup, once
+    with an exact one -- from [npy, npx, C] and [npy, C, npx] storage and from a contiguous map."""
+    assert feat[0] * feat[1] * feat[2] > 4096
+    _stage_and_check(7, 5, feat=feat, layout=layout)
+
+
+@pytest.mark.parametrize("copy", [("depth", "rgb", "labels"), ("depth", "rgb", "feat"), ("labels",), ("labels", "feat"), ("depth", "rgb")],
+                         ids="+".join)
+def test_stage_frame_optional_segments(copy):
+    """Labels without a feature map, a feature map without labels, depth and rgb lent with labels copied: what has no source is
+    not written (its destination is offered all the same), what follows an absent segment is copied to the right place."""
+    _stage_and_check(33, 31, copy=copy)
+    _stage_and_check(67, 63, copy=copy, feat=(40, 11, 13))
 
 
 def test_stage_frame_rejects_half_lent_images():
@@ -56,3 +108,20 @@ def test_stage_frame_rejects_half_lent_images():
     s = _frame(4, 4, t, None, p, k, None, 0, 0, None)   # depth without rgb on the source side only ...
     d = _frame(4, 4, t, t.new_zeros((4, 4, 3)), p, k, None, 0, 0, None)
     assert lib().saf_stage_frame(C.byref(s), 0, 0, 0, 0, C.byref(d), current_stream_ptr()) == _abi.SAF_E_INVALID
+
+
+def test_stage_frame_rejects_a_feature_map_without_channels():
+    dev = torch.device("cuda", 0)
+    t, rgb = torch.zeros((4, 4), device=dev), torch.zeros((4, 4, 3), device=dev)
+    p, k = torch.zeros((4, 4), device=dev), torch.zeros((3, 3), device=dev)
+    f, fd = torch.ones((8, 2, 2), device=dev), torch.full((8, 2, 2), FILL, device=dev)
+    s = _frame(4, 4, t, rgb, p, k, f, 2, 2, None)
+    d = _frame(4, 4, t.clone(), rgb.clone(), p.clone(), k.clone(), fd, 2, 2, None)
+    assert lib().saf_stage_frame(C.byref(s), 0, 4, 2, 1, C.byref(d), current_stream_ptr()) == _abi.SAF_E_INVALID
+    no_dst = _frame(4, 4, t.clone(), rgb.clone(), p.clone(), k.clone(), None, 2, 2, None)  # ... or without a destination for it
+    assert lib().saf_stage_frame(C.byref(s), 8, 4, 2, 1, C.byref(no_dst), current_stream_ptr()) == _abi.SAF_E_INVALID
+    torch.cuda.synchronize()
+    assert bool((fd == FILL).all())
+    assert lib().saf_stage_frame(C.byref(s), 8, 4, 2, 1, C.byref(d), current_stream_ptr()) == _abi.SAF_OK
+    torch.cuda.synchronize()
+    assert bool((fd == 1.0).all())

@@ -1,13 +1,17 @@
 """Pins the tiled CLIP front-end (Clip.get_patches / Clip.img_inference_tiled,
 reference clipfusion.py:789-839) against goldens produced by the reference's own code with the ViT replaced
 by a stub encode_image (oracle/gen_golden.py::gen_tiled_clip).  The PyTorch restatement runs on the CPU; the
-fused HIP front-end (saf_clip_tiles) is checked against the same goldens in tests/test_gpu_parity.py."""
+fused HIP front-end (saf_clip_tiles) is checked against the same goldens in tests/test_gpu_parity.py, and here, every pixel of
+whole tiles, against the float64 statement of tests/frame_pass_reference.py (bound per pixel: E = 2^-21 * (p * R + 2 * M))."""
+import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import frame_pass_reference as R
 from spatially_aware_ai_amd.clipfusion import Clip
 
 
@@ -136,3 +140,119 @@ def test_integrate_with_depth_scaled_patches_matches_the_oracle(oracle):
     assert torch.equal(fz.weight.cpu(), vol.weight) and int(vol.weight.sum()) > 1000
     np.testing.assert_allclose(fz.clip_feat.cpu().numpy(), vol.clip_feat.numpy(), rtol=1e-4, atol=1e-6)
     np.testing.assert_allclose(fz.rgb.cpu().numpy(), vol.rgb.numpy(), rtol=1e-4, atol=1e-6)
+
+
+# ------------------------------------------------------------------------------------ whole tiles against the float64 statement
+# (H, W, patch, stride, out): no overlap; overlapping patches; patch 1 (all four taps are one pixel); patch 2; scale 1; downsampling;
+# a second workgroup in x (out > 256); an odd small output
+TILE_CASES = [(40, 56, 8, 8, 224), (40, 56, 24, 16, 224), (5, 7, 1, 2, 224), (6, 8, 2, 2, 224), (224, 224, 224, 1, 224),
+              (300, 300, 300, 1, 224), (40, 56, 8, 8, 300), (40, 56, 8, 8, 37)]
+_TORCH_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # SAF_F32, SAF_BF16, SAF_F16
+
+
+@functools.lru_cache(maxsize=2)
+def _tile_case(case):
+    """White noise (R is large everywhere), batch 2, and the float64 statement of its tiles -- computed once per case (the
+    statements of the larger cases are hundreds of MB: only the last two are kept)."""
+    h, w, patch, stride, out = case
+    g = torch.Generator().manual_seed(h * 1000 + patch * 10 + out)
+    rgb = torch.rand(2, 3, h, w, generator=g)
+    return rgb, R.tiles_f64(rgb.numpy(), patch, stride, out)
+
+
+def _clip_tiles(x, patch, stride, out, dtype=torch.float32, fill=None):
+    """saf_clip_tiles through the C entry (tiles_224 fixes out_size to 224), on any [B, 3, H, W] view."""
+    from spatially_aware_ai_amd._lib import current_stream_ptr, lib
+
+    bsz, _, h, w = x.shape
+    tiles = bsz * (1 + (h - patch) // stride) * (1 + (w - patch) // stride)
+    dst = torch.empty((tiles, 3, out, out), dtype=dtype, device=x.device)
+    if fill is not None:
+        dst.fill_(fill)
+    mean, std = (C.c_float * 3)(*R.CLIP_MEAN), (C.c_float * 3)(*R.CLIP_STD)
+    sb, sc, sy, sx = x.stride()
+    rc = lib().saf_clip_tiles(x.data_ptr(), bsz, h, w, sb, sc, sy, sx, patch, stride, out, mean, std, dst.data_ptr(), _TORCH_DT[dtype],
+                              current_stream_ptr())
+    return rc, dst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", TILE_CASES, ids=str)
+def test_whole_tiles_against_float64(case):
+    """Every pixel of every tile, planar and channel-last, batch 2: |got - want| <= E.  fp16 and bf16 outputs are the fp32
+    output rounded once.  Largest observed err / E on the MI355X per case (planar and channel-last alike), in the order of
+    TILE_CASES: 0.205, 0.131, 0.153, 0.199, 0.049, 0.019, 0.189, 0.159."""
+    h, w, patch, stride, out = case
+    rgb, (want, rng, mag) = _tile_case(case)
+    planar = rgb.cuda()
+    channel_last = rgb.permute(0, 2, 3, 1).contiguous().cuda().permute(0, 3, 1, 2)
+    assert channel_last.stride(1) == 1
+    for name, x in (("planar", planar), ("channel-last", channel_last)):
+        rc, got = _clip_tiles(x, patch, stride, out)
+        assert rc == 0 and got.shape == want.shape
+        ratio = R.tile_error_ratio(got.cpu().numpy(), want, rng, mag, patch)
+        print(f"tiles {case} {name}: max err / E = {ratio:.3f}")
+        assert ratio <= 1.0, (name, ratio)
+        if name == "planar":
+            ref32 = got
+        else:
+            assert torch.equal(got, ref32), "the layout changes addresses, not values"
+    for dt in (torch.bfloat16, torch.float16):
+        rc, got16 = _clip_tiles(planar, patch, stride, out, dt)
+        assert rc == 0 and torch.equal(got16, ref32.to(dt)), f"{dt} tiles are the fp32 tiles rounded once"
+    if out == 224:  # the route integrate() takes
+        clip = Clip("stub", None, backbone=StubBackbone(), tokenizer=None).cuda()
+        assert torch.equal(clip.tiles_224(planar, patch, stride), ref32)
+        assert torch.equal(clip.tiles_224(channel_last, patch, stride, dtype=torch.float16), ref32.half())
+    if patch == out:  # scale 1: w1 = h1 = 0 -- the normalised input, exactly
+        m, s = (torch.tensor(v).view(1, 3, 1, 1) for v in (R.CLIP_MEAN, R.CLIP_STD))
+        assert torch.equal(ref32.cpu(), (rgb - m) / s)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [(40, 56, 24, 16, 224), (40, 56, 8, 8, 37), (6, 8, 2, 2, 224)], ids=str)
+def test_tiles_of_a_centre_crop_view(case):
+    """A centre crop of a larger frame: stride_y != W * stride_x and a storage offset, planar and channel-last.  The tiles are
+    those of the crop's own copy, bit for bit, and the destination beyond them is left alone."""
+    h, w, patch, stride, out = case
+    rgb, (want, rng, mag) = _tile_case(case)
+    big = torch.rand(2, 3, h + 7, w + 10, generator=torch.Generator().manual_seed(5))
+    big[:, :, 3:3 + h, 6:6 + w] = rgb
+    for name, frame in (("planar", big.cuda()), ("channel-last", big.permute(0, 2, 3, 1).contiguous().cuda().permute(0, 3, 1, 2))):
+        x = frame[:, :, 3:3 + h, 6:6 + w]
+        assert x.storage_offset() != 0 and x.stride(2) != w * x.stride(3)
+        rc, got = _clip_tiles(x, patch, stride, out)
+        assert rc == 0
+        ratio = R.tile_error_ratio(got.cpu().numpy(), want, rng, mag, patch)
+        assert ratio <= 1.0, (name, ratio)
+        rc, plain = _clip_tiles(rgb.cuda(), patch, stride, out)
+        assert rc == 0 and torch.equal(got, plain)
+
+
+@pytest.mark.gpu
+def test_clip_tiles_refusals():
+    """patch > H, (W - patch) % stride != 0 and more than 65535 tiles are refused, and nothing is written."""
+    from spatially_aware_ai_amd import _abi
+    from spatially_aware_ai_amd._lib import current_stream_ptr, lib
+
+    x = torch.rand(1, 3, 40, 56, device="cuda")
+    mean, std = (C.c_float * 3)(*R.CLIP_MEAN), (C.c_float * 3)(*R.CLIP_STD)
+    dst = torch.full((66000 * 3,), 7.0, device="cuda")
+
+    def call(t, patch, stride, out=1):
+        sb, sc, sy, sx = t.stride()
+        return lib().saf_clip_tiles(t.data_ptr(), t.shape[0], t.shape[2], t.shape[3], sb, sc, sy, sx, patch, stride, out, mean, std,
+                                    dst.data_ptr(), _abi.SAF_F32, current_stream_ptr())
+
+    assert call(x, 41, 1) == _abi.SAF_E_INVALID                     # patch > H
+    assert call(x, 8, 32) == _abi.SAF_E_INVALID                     # (H - patch) % stride == 0, (W - patch) % stride != 0
+    torch.cuda.synchronize()
+    assert bool((dst == 7.0).all()), "a refused call wrote nothing"
+    assert call(x[:, :, :, :40], 8, 32) == _abi.SAF_OK              # ... and with W = 40 it is taken: 2 x 2 tiles of one pixel
+    many = torch.rand(1, 3, 256, 257, device="cuda")
+    assert call(many, 1, 1) == _abi.SAF_E_UNSUPPORTED               # 256 * 257 = 65792 tiles
+    assert call(many[:, :, :255], 1, 1) == _abi.SAF_OK              # 255 * 257 = 65535: the most one call takes
+    torch.cuda.synchronize()
+    assert bool((dst[65535 * 3:] == 7.0).all()) and bool((dst[:65535 * 3] != 7.0).all())
+    m, s = (torch.tensor(v).view(3, 1, 1) for v in (R.CLIP_MEAN, R.CLIP_STD))
+    assert torch.equal(dst[:65535 * 3].view(255, 257, 3).cpu(), ((many[0, :, :255].cpu() - m) / s).permute(1, 2, 0))
